@@ -13,11 +13,14 @@ ranks itself before anything touches the GPU): the validation batch is sharded -
 its own B images (weak scaling) and the logits are all-gathered once per step, as the validate
 driver does.
 
-Prints ONE JSON line (rank 0).  `roofline` is for the dominant kernel family, the fused
-approx GEMM/conv launches (fp8a_conv2d / fp8a_matmul), timed with HIP events on the stream
-they run on; `cpu_baseline` is the vectorised torch restatement of the reference's op sequence
-(oracle/v9_torch_port.py, cost within ~5 % of the reference on identical inputs) on a bounded
-sample of the same workload.
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times `--steps` steps and prints
+the headline (`value`, `ms_per_step`) with its configuration; `--dump-outputs DIR` also saves the
+logits of the last timed step.  `--full` adds every other figure, each from work of its own after
+the timed steps: `roofline` is for the dominant kernel family, the fused approx GEMM/conv launches
+(fp8a_conv2d / fp8a_matmul), timed with HIP events on the stream they run on (with the fallback
+and kernel-path counters of those steps); `cpu_baseline` is the vectorised torch restatement of
+the reference's op sequence (oracle/v9_torch_port.py, cost within ~5 % of the reference on
+identical inputs) on a bounded sample of the same workload.
 """
 import argparse
 import json
@@ -100,12 +103,19 @@ def parse(argv=None):
     ap.add_argument("--shard-seed", type=int, default=None,
                     help="seed offset of this process's input shard (default: its rank); lets a world-1 run "
                          "reproduce rank r's shard")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the roofline / fallback / kernel-path "
+                         "figures (HIP events around every approx launch, over --steps eager steps of their own "
+                         "after the timed ones) and the CPU baseline")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, rank 0 saves what the last timed step returned (the gathered "
+                         "logits) as DIR/logits.npy (float32)")
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--batch", type=int, default=None, help="images per GPU per step (default 512; resnet18 1024, vit_b16 64, vit_fc 256)")
     ap.add_argument("--cal-batch", type=int, default=64)
     ap.add_argument("--with-comp", action="store_true", help="withComp=True (E4M3: all-zero error table)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-graph", action="store_true",
                     help="time eager forwards (default on a GPU: the forward captured once into a HIP graph, each "
                          "timed step one replay of it -- every kernel still runs; the launch gaps go)")
@@ -321,7 +331,7 @@ def capture_forward(model, x, warm, sync, fallback_stats=None):
         graph.replay()
         return gather_logits(out)
     info["note"] = ("timed steps = replays of the captured forward (every kernel of the forward runs each step); "
-                    "roofline / fallback / path figures from the same number of eager steps after them")
+                    "with --full, roofline / fallback / path figures from the same number of eager steps after them")
     return info, replay
 
 
@@ -355,7 +365,10 @@ def run(args, dev, rank=0, world=1):
     if args.no_approx:  # scripts/image_net.sh:42-45 (--no-approx_flag --original-quantize-res)
         cfg.update(run_method=dict(approx_flag=False, quantize_after_mult_and_add=False, res_quantizer_flag=True,
                                    original_quantize_res=True))
-    model, in_shape, arch_desc = build_workload(args.arch, cfg, args.bn_stats_batches, dev)
+    # the float model's BN statistics are estimated on the CPU: on the GPU they run through MIOpen,
+    # whose algorithm choice (and so the statistics' last bits) may differ from process to process,
+    # and every run with the same arguments must time -- and dump -- the same network
+    model, in_shape, arch_desc = build_workload(args.arch, cfg, args.bn_stats_batches, torch.device("cpu"))
     model = model.to(dev).eval()
 
     # calibration (one batch) on rank 0 alone, then fixed ranges -- image_net.py:76-91; the other
@@ -373,13 +386,25 @@ def run(args, dev, rank=0, world=1):
     def step():
         return gather_logits(model(x))  # one RCCL all-gather of logits per step (N > 1)
 
-    def instrumented(fn):
-        """K steps of fn with the per-op HIP events (approx_ops._PROFILE), the product kernels'
-        HIP events (fp8a_kernel_timing) and the fallback / path counters on; returns the wall
-        time between the two barrier + synchronize brackets and the op events."""
+    def timed(fn):
+        """args.steps steps of fn between two barrier + synchronize brackets: (wall time, what the
+        last step returned)."""
         sync()
         if world > 1:
             dist.barrier()
+        out = None
+        t0 = time.perf_counter()
+        for _ in range(args.steps):
+            out = fn()
+        sync()
+        if world > 1:
+            dist.barrier()
+        return time.perf_counter() - t0, out
+
+    def instrumented(fn):
+        """--full: args.steps more steps of fn with the per-op HIP events (approx_ops._PROFILE), the
+        product kernels' HIP events (fp8a_kernel_timing) and the fallback / path counters on;
+        returns their wall time and the op events."""
         am._PROFILE = [] if cuda else None
         if cuda:
             fa._lib.fallback_stats(reset=True)  # (synchronises: outside the timed region)
@@ -387,19 +412,13 @@ def run(args, dev, rank=0, world=1):
             fa._lib.dense_stats(reset=True)
             fa._lib.kernel_time(reset=True)
             fa._lib.kernel_timing(True)  # HIP events around each GEMM's product kernel (fp8a_kernel_timing)
-        t0 = time.perf_counter()
-        for _ in range(args.steps):
-            fn()
-        sync()
-        if world > 1:
-            dist.barrier()
-        el = time.perf_counter() - t0
+        el, _ = timed(fn)
         pr, am._PROFILE = am._PROFILE or [], None
         if cuda:
             fa._lib.kernel_timing(False)
         return el, pr
 
-    graph_info = None
+    graph_info, replay = None, None
     with torch.no_grad():
         for _ in range(args.warmup):
             step()
@@ -413,35 +432,33 @@ def run(args, dev, rank=0, world=1):
                     print(f"bench.py rank {rank}: no graph timing: {json.dumps(graph_info)}", file=sys.stderr, flush=True)
                 if int(ok.item()) == 0 and graph_info.get("captured"):
                     graph_info.update(captured=False, note="another rank's capture failed: eager forwards timed")
-        if graph_info and graph_info.get("captured"):
-            # the timed steps replay the captured forward; the per-kernel HIP events and counters come
-            # from the same number of eager steps right after (a replayed graph carries no host-side
-            # per-launch events)
+        captured = bool(graph_info and graph_info.get("captured"))
+        # the timed steps: replays of the captured forward, else eager forwards; nothing else runs
+        # between the brackets (the per-kernel HIP events and counters of --full come from steps of
+        # their own afterwards: a replayed graph carries no host-side per-launch events)
+        if captured:
             fa._lib.fallback_stats(reset=True)  # (synchronises: outside the timed region)
-            sync()
-            if world > 1:
-                dist.barrier()
-            t0 = time.perf_counter()
-            for _ in range(args.steps):
-                replay()
-            sync()
-            if world > 1:
-                dist.barrier()
-            elapsed = time.perf_counter() - t0
+        elapsed, last = timed(replay if captured else step)
+        if captured:
             # the timed replays' own fallback counters (device-side: a replay counts them as an eager
             # forward does)
             graph_info["timed_replay_fallback"] = fa._lib.fallback_stats(reset=True)
+        if args.dump_outputs and rank == 0:  # what the last timed step handed its caller
+            import numpy as np
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            np.save(os.path.join(args.dump_outputs, "logits.npy"), last.float().cpu().numpy())
+        eager_elapsed, prof = elapsed, []
+        if args.full:
             eager_elapsed, prof = instrumented(step)
-            graph_info["eager_images_per_s"] = world * args.batch * args.steps / eager_elapsed
-        else:
-            elapsed, prof = instrumented(step)
-            eager_elapsed = elapsed
-    # how many launches / 64x64 output units of the timed steps left the fast path (a regression
-    # there would otherwise be invisible in the line)
-    fallback = fa._lib.fallback_stats() if cuda else None
-    paths = {k: v for k, v in fa._lib.path_stats().items() if v} if cuda else None
-    dense_fb = fa._lib.dense_stats() if cuda else None
-    ktime = fa._lib.kernel_time(reset=True) if cuda else {}
+            if captured:
+                graph_info["eager_images_per_s"] = world * args.batch * args.steps / eager_elapsed
+    # how many launches / 64x64 output units of the instrumented steps left the fast path (a
+    # regression there would otherwise be invisible in the line)
+    detail = args.full and cuda
+    fallback = fa._lib.fallback_stats() if detail else None
+    paths = {k: v for k, v in fa._lib.path_stats().items() if v} if detail else None
+    dense_fb = fa._lib.dense_stats() if detail else None
+    ktime = fa._lib.kernel_time(reset=True) if detail else {}
     if args.dump_logits:  # one more step, after every counter was read (every rank: the gather is a collective)
         import numpy as np
         from fp8_quantization_amd.distributed import quantizers
@@ -480,7 +497,8 @@ def run(args, dev, rank=0, world=1):
         k_s = kt.get("ms", 0.0) / 1e3
         k_avg_s = k_s / kt["launches"] if kt.get("launches") else 0.0
         achieved = 2.0 * kt["macs"] / k_s / 1e12 if k_s > 0 else None
-        pmc_name, pmc = pmc_summary(kernel, args.arch, args.expo_width, args.mant_width, args.batch)
+        pmc_name, pmc = (pmc_summary(kernel, args.arch, args.expo_width, args.mant_width, args.batch) if detail
+                         else (None, {}))
         traffic = pmc.get("bytes_per_launch")
         # HBM: the PMC bytes per dispatch of the kernel x its timed dispatches / its timed time
         hbm_gbs = traffic * kt["dispatches"] / k_s / 1e9 if (traffic and k_s > 0) else None
@@ -554,7 +572,7 @@ def run(args, dev, rank=0, world=1):
                 "gemm_share_of_step": op_ms / 1e3 / eager_elapsed,
             },
         }
-        if args.no_approx and cuda:
+        if args.no_approx and detail:
             gbs = op_bytes / (op_ms / 1e3) / 1e9 if op_ms > 0 else None
             # the dense GEMM kernel alone (fp8a_kernel_time's dense slot: HIP events around each
             # dn_gemm* launch; its MAC slot carries the launches' algorithmic bytes)
@@ -603,11 +621,11 @@ def run(args, dev, rank=0, world=1):
         if paths is not None:
             res["gemm_paths"] = dict(paths, note="timed steps only: approx GEMM launches per kernel path "
                                                  "(fp8a_path_stats)")
-        if world == 1 and not args.no_cpu_baseline and (args.expo_width, args.mant_width) == (4, 3) \
+        if args.full and world == 1 and not args.no_cpu_baseline and (args.expo_width, args.mant_width) == (4, 3) \
                 and not args.no_approx:
             res["cpu_baseline"] = cpu_baseline(shapes, get_error_table_NN(4, 3, args.with_comp, 3), args.cpu_columns)
             res["speedup_vs_cpu_baseline"] = res["value"] / res["cpu_baseline"]["value"]
-        if not cuda:
+        if not detail:  # (its figures come from the instrumented steps of --full on a GPU)
             res.pop("roofline")
         return res
     return None

@@ -167,7 +167,7 @@ def _flow_worker(rank, ws, port, q):
         res = json.loads(json.dumps(res)) if res is not None else None
         import bench
         bres = bench.run(bench.parse(["--arch", "mobilenet_v2", "--batch", "2", "--steps", "1", "--warmup", "1",
-                                      "--cal-batch", "2", "--bn-stats-batches", "0", "--no-cpu-baseline"]),
+                                      "--cal-batch", "2", "--bn-stats-batches", "0", "--full", "--no-cpu-baseline"]),
                          torch.device("cpu"), rank, ws)
         q.put((rank, res, mx, json.loads(json.dumps(bres)) if bres is not None else None))
     except Exception:
@@ -213,7 +213,7 @@ def test_gloo_world2_validate_and_bench_flow():
     assert b0["n_gpus"] == 2 and b0["config"]["global_batch"] == 4 and b0["value"] > 0
 
 
-def test_bench_main_gpus2_spawns_ranks(capfd):
+def test_bench_main_gpus2_spawns_ranks(capfd, tmp_path):
     """`bench.py --gpus 2` with no launcher environment starts the two ranks itself (spawned
     from a parent that touches no GPU) and rank 0 reports n_gpus = 2 -- the driver's scaling
     command form (here on the CPU rehearsal device: gloo and torch stand-ins)."""
@@ -221,10 +221,16 @@ def test_bench_main_gpus2_spawns_ranks(capfd):
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         assert k not in os.environ
     bench.main(["--gpus", "2", "--device", "cpu", "--arch", "mobilenet_v2", "--batch", "2", "--steps", "1",
-                "--warmup", "1", "--cal-batch", "2", "--bn-stats-batches", "0", "--no-cpu-baseline"],
+                "--warmup", "1", "--cal-batch", "2", "--bn-stats-batches", "0", "--no-cpu-baseline",
+                "--dump-outputs", str(tmp_path / "out")],
                worker_init=_install_standins)
     lines = [ln for ln in capfd.readouterr().out.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, lines  # rank 0 alone prints
     line = json.loads(lines[0])
     assert line["n_gpus"] == 2 and line["config"]["global_batch"] == 4 and line["config"]["parallelism"] == "dp2"
-    assert line["value"] > 0
+    assert line["value"] > 0 and line["steps"] == 1 and line["ms_per_step"] > 0
+    assert "cpu_baseline" not in line and "roofline" not in line  # (a plain run: those are --full's)
+    # --dump-outputs: rank 0 saved what the last timed step returned, the logits gathered from both ranks
+    import numpy as np
+    logits = np.load(str(tmp_path / "out" / "logits.npy"))
+    assert logits.dtype == np.float32 and logits.ndim == 2 and logits.shape[0] == 4 and np.isfinite(logits).all()

@@ -109,7 +109,7 @@ def test_bench_workload_batch1024_sampled_through_fused_chain():
     cfg = dict(expo_width=4, mant_width=3, dnsmp_factor=3, withComp=False, with_approx=True, with_s2nn2s_opt=True,
                quant_btw_mult_accu=True)
     torch.manual_seed(0)  # (bench.run's order: seed, build with 4 BN-statistics batches, calibrate on 64 images)
-    model, in_shape, _ = bench.build_workload("resnet18", cfg, 4, torch.device(DEV))
+    model, in_shape, _ = bench.build_workload("resnet18", cfg, 4, torch.device("cpu"))
     model = model.to(DEV).eval()
     calibrate_on_rank0(model, [bench.synthetic_images(64, 1234, DEV, in_shape)], quantized=True)
     x = bench.synthetic_images(1024, 10, DEV, in_shape)

@@ -46,9 +46,16 @@ def test_bench_two_ranks_on_one_gpu_match_world1_shards(tmp_path):
     shards = []
     for r in (0, 1):
         p = str(tmp_path / f"w1_{r}.npy")
-        one = _bench(["--shard-seed", str(r), "--dump-logits", p] + COMMON)
+        out = str(tmp_path / f"out_{r}")
+        one = _bench(["--shard-seed", str(r), "--dump-logits", p, "--dump-outputs", out] + COMMON)
         assert one["n_gpus"] == 1 and one["hip_graph"]["captured"]
+        assert one["steps"] == 2 and one["ms_per_step"] > 0
+        assert "roofline" not in one and "cpu_baseline" not in one  # (those are --full's)
         shards.append(np.load(p))
+        # --dump-outputs: the last timed step's (replayed) logits = the extra eager step's
+        timed = np.load(os.path.join(out, "logits.npy"))
+        assert timed.dtype == np.float32
+        assert np.array_equal(timed.view(np.uint32), shards[-1].view(np.uint32)), "timed-step logits differ"
     got = np.load(two)
     want = np.concatenate(shards)
     assert got.shape == want.shape == (8, 1000)

@@ -7,7 +7,7 @@
 # steps (each one word; ':' separates its arguments):
 #   tests[:<pytest -k expr>]    python -m pytest tests -m gpu (optionally -k EXPR), 120 s per test
 #   smoke                       __graft_entry__.smoke()
-#   bench:<name>[:<args>]       bench.py <args with ',' for spaces> -> <job>/bench_<name>.json
+#   bench:<name>[:<args>]       bench.py --full <args with ',' for spaces> -> <job>/bench_<name>.json
 #   evidence:<tag>              kernel trace + PMC passes + summary + bench line of one configuration
 #                               (tools/profile_config.sh; tags as in tools/evidence_specs.txt)
 #   py:<script>[:<args>]        python <script> <args with ',' for spaces> (probes under tools/)
@@ -34,7 +34,7 @@ for step in "$@"; do
       timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1 || { tail -20 $OUT/smoke.log; exit 1; }
       tail -1 $OUT/smoke.log ;;
     bench)
-      timeout -k 10 600 python bench.py ${a2//,/ } > $OUT/bench_$a1.json 2> $OUT/bench_$a1.err \
+      timeout -k 10 600 python bench.py --full ${a2//,/ } > $OUT/bench_$a1.json 2> $OUT/bench_$a1.err \
           || { tail -8 $OUT/bench_$a1.err; exit 1; }
       python -c "import json; d=json.load(open('$OUT/bench_$a1.json')); r=d.get('roofline') or {}; \
 print('$a1', round(d['value'],1), {k: r.get(k) for k in ('frac','op_frac','hbm_gbs','valu_busy')}, \
@@ -48,7 +48,7 @@ d.get('fallback', {}).get('exact_units'), (d.get('hip_graph') or {}).get('captur
       python tools/trace_breakdown.py $(ls gpurun_out/${JOB}_$a1/trace/*kernel_trace.csv) --forwards 5:3 \
           --out $OUT/rocprof_${ROUND}_${a1}_breakdown.txt > /dev/null || exit 1
       sed -n 2,9p $OUT/rocprof_${ROUND}_${a1}_breakdown.txt
-      timeout -k 10 600 python bench.py --arch $ARCH --expo-width $E --mant-width $M --batch $B $EXTRA \
+      timeout -k 10 600 python bench.py --full --arch $ARCH --expo-width $E --mant-width $M --batch $B $EXTRA \
           > $OUT/bench_${ROUND}_${a1}_ev.json 2> $OUT/bench_${ROUND}_$a1.err || { tail -3 $OUT/bench_${ROUND}_$a1.err; exit 1; }
       python -c "import json; d=json.load(open('$OUT/bench_${ROUND}_${a1}_ev.json')); r=d.get('roofline') or {}; \
 print('$a1', round(d['value'],1), {k: r.get(k) for k in ('frac','op_frac','hbm_gbs','valu_busy')})" ;;

@@ -10,7 +10,7 @@ R=$(pwd)
 OUT=$R/gpurun_out/$TAG
 mkdir -p $OUT
 LAUNCH_PER_STEP=21
-timeout -k 10 600 python bench.py --steps $STEPS --warmup 2 > $OUT/bench.json 2> $OUT/bench.err && \
+timeout -k 10 600 python bench.py --full --steps $STEPS --warmup 2 > $OUT/bench.json 2> $OUT/bench.err && \
 cd /tmp && export TMPDIR=/tmp && \
 timeout -k 10 600 rocprofv3 --kernel-trace --stats -f csv -d $OUT/trace -o run -- \
     python $R/bench.py --steps $STEPS --warmup 2 --no-cpu-baseline > $OUT/trace.log 2>&1 && \

@@ -30,7 +30,7 @@ AB=$R/fp8_quantization_amd/lib/ab
 
 bench_line() {  # out-dir name lib bench-args...
   local O=$1 N=$2 L=$3; shift 3
-  FP8A_LIB_PATH=$L timeout -k 10 400 python bench.py --no-cpu-baseline "$@" > $O/$N.json 2> $O/$N.err || { tail -3 $O/$N.err; return 1; }
+  FP8A_LIB_PATH=$L timeout -k 10 400 python bench.py --full --no-cpu-baseline "$@" > $O/$N.json 2> $O/$N.err || { tail -3 $O/$N.err; return 1; }
   python -c "import json; d=json.load(open('$O/$N.json')); print('$N', round(d['value'],1), (d.get('hip_graph') or {}).get('eager_images_per_s'), (d.get('roofline') or {}).get('frac'))"
 }
 
