@@ -23,6 +23,7 @@ SYMBOLS = ("fp8a_version", "fp8a_last_error", "fp8a_fallback_stats", "fp8a_path_
            "fp8a_fp8_quantize", "fp8a_matmul_qamaa", "fp8a_conv2d_qamaa", "fp8a_matmul_block_workspace_size",
            "fp8a_matmul_block", "fp8a_dense_matmul_workspace_size", "fp8a_dense_matmul",
            "fp8a_dense_conv2d_workspace_size", "fp8a_dense_conv2d", "fp8a_grouped_conv2d", "fp8a_dense_conv2d_fused", "fp8a_dense_stats", "fp8a_clock_stats",
+           "fp8a_xm_sign_stats", "fp8a_splitk_stats",
            "fp8a_word_image_bytes", "fp8a_word_image_init", "fp8a_conv2d_chain", "fp8a_conv2d_wants_image",
            "fp8a_flag_arena_slot_bytes")
 
@@ -95,6 +96,8 @@ def load():
                                      P, I, I, I, P, P, P, SZ, P], I),
         "fp8a_dense_stats": ([P, I], I),
         "fp8a_clock_stats": ([P, I], I),
+        "fp8a_xm_sign_stats": ([P, I], I),
+        "fp8a_splitk_stats": ([P, I], I),
         "fp8a_flag_arena_slot_bytes": ([P], SZ),
     }
     for name, (args, res) in sig.items():
@@ -204,6 +207,25 @@ def dense_stats(reset=False):
     out = (ctypes.c_uint64 * 2)()
     check(L.fp8a_dense_stats(ctypes.cast(out, ctypes.c_void_p), 1 if reset else 0), "fp8a_dense_stats")
     return dict(fp32_launches=int(out[0]), fp32_units=int(out[1]))
+
+
+def xm_sign_stats(reset=False):
+    """fp8a_xm_sign_stats: dict(half, full) -- matrix-core launches whose tile-table build wrote the
+    positive-sign rows only / both halves (synchronises the device).  "full" is not by itself a
+    regression: launches with a negative A word, and every launch of the fp32-staging form (it decodes
+    A inside the kernel and cannot know; ResNet-18's two 1x1 downsample launches), always count there."""
+    L = load()
+    out = (ctypes.c_uint64 * 2)()
+    check(L.fp8a_xm_sign_stats(ctypes.cast(out, ctypes.c_void_p), 1 if reset else 0), "fp8a_xm_sign_stats")
+    return dict(half=int(out[0]), full=int(out[1]))
+
+
+def splitk_stats(reset=False):
+    """fp8a_splitk_stats: GEMM launches that ran split along K (the reduction kernel wrote their output)."""
+    L = load()
+    out = (ctypes.c_uint64 * 1)()
+    check(L.fp8a_splitk_stats(ctypes.cast(out, ctypes.c_void_p), 1 if reset else 0), "fp8a_splitk_stats")
+    return int(out[0])
 
 
 def clock_stats(reset=False):

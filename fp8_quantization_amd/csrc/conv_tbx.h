@@ -420,7 +420,7 @@ __global__ __launch_bounds__(256, TBSG_WAVES) void conv_tbsg_kernel(const float 
     // for bit (emit_word) -- so the pointwise convolution after a depthwise one skips its pre-pass.
     // The next quantizer's constants from the image header (emit_prep_kernel), wave-uniform.
     float emx = 0.0f, efb = 0.0f;
-    uint32_t eemn = 0u, sehi = 0u;
+    uint32_t eemn = 0u, sehi = 0u, eneg = 0u;
     int ebR = 0;
     bool eok = true;
     if (em.w) {
@@ -476,10 +476,14 @@ __global__ __launch_bounds__(256, TBSG_WAVES) void conv_tbsg_kernel(const float 
                                                   ebR, eok);
                     wo[j] = wd;
                     sehi = max(sehi, word_sehi(wd));
+                    eneg |= wd;
                 }
             }
     }
-    if (em.w) wave_max_atomic(em.invalid + 5, sehi);  // (every lane: the loop above has ended for all)
+    if (em.w) {  // (every lane: the loop above has ended for all)
+        wave_max_atomic(em.invalid + 5, sehi);
+        wave_sign_record(em.invalid + 6, eneg);
+    }
     const bool ebad = em.w && !eok;
     if (__syncthreads_or(bad ? 1 : 0) && tid == 0) {
         atomicOr(gate, 1u);

@@ -98,7 +98,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const GemmArgs p) {
     const int64_t MN = p.M * p.N;
     const float pb = post_bias(p);
     const EmitCtx ec = emit_ctx(p);
-    uint32_t sehi = 0;
+    uint32_t sehi = 0, neg = 0;
     const int S = p.splits;
     const bool vec = p.nchw ? ((p.hw & 3) == 0) : ((p.N & 3) == 0 && (p.ldc & 3) == 0);
     const bool aligned = ((((uintptr_t)p.C) & 15) == 0) && ((((uintptr_t)p.part) & 15) == 0) && ((MN & 3) == 0) &&
@@ -135,9 +135,12 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const GemmArgs p) {
             }
             const float4 r = post4(p, o, acc, pb);
             *reinterpret_cast<float4 *>(p.C + o) = r;
-            if (p.em.w) emit4(p, ec, o, r, sehi);
+            if (p.em.w) emit4(p, ec, o, r, sehi, neg);
         }
-        if (p.em.w) wave_max_atomic(p.em.invalid + 5, sehi);
+        if (p.em.w) {
+            wave_max_atomic(p.em.invalid + 5, sehi);
+            wave_sign_record(p.em.invalid + 6, neg);
+        }
         return;
     }
     for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < MN; q += stride) {
@@ -155,9 +158,12 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const GemmArgs p) {
         }
         const float r = post1(p, o, epi(p.ep, p.ep_act, p.ep_lo, p.ep_hi, ch, acc), pb);
         p.C[o] = r;
-        if (p.em.w) emit1(p, ec, o, r, sehi);
+        if (p.em.w) emit1(p, ec, o, r, sehi, neg);
     }
-    if (p.em.w) wave_max_atomic(p.em.invalid + 5, sehi);
+    if (p.em.w) {
+        wave_max_atomic(p.em.invalid + 5, sehi);
+        wave_sign_record(p.em.invalid + 6, neg);
+    }
 }
 
 // A(m, k) for the exact kernels: matrix or implicit im2col (through the fused input quantizer
@@ -208,9 +214,10 @@ __global__ __launch_bounds__(256) void gemm_exact_kernel(const GemmArgs p) {
             const float r = post1(p, o, epi(p.ep, p.ep_act, p.ep_lo, p.ep_hi, p.coff + n, s), post_bias(p));
             p.C[o] = r;
             if (p.em.w) {
-                uint32_t sh = 0;
-                emit1(p, emit_ctx(p), o, r, sh);
+                uint32_t sh = 0, ng = 0;
+                emit1(p, emit_ctx(p), o, r, sh, ng);
                 if (sh) atomicMax(p.em.invalid + 5, sh);
+                sign_record(p.em.invalid + 6, ng);
             }
         }
         return;
@@ -266,9 +273,10 @@ __device__ __forceinline__ void gemm_exact_units(const GemmArgs &p, uint32_t f, 
             const float r = post1(p, o, epi(p.ep, p.ep_act, p.ep_lo, p.ep_hi, p.coff + n, s[j] + part[j]), pb);
             p.C[o] = r;
             if (p.em.w) {
-                uint32_t sh = 0;
-                emit1(p, ec, o, r, sh);
+                uint32_t sh = 0, ng = 0;
+                emit1(p, ec, o, r, sh, ng);
                 if (sh) atomicMax(p.em.invalid + 5, sh);
+                sign_record(p.em.invalid + 6, ng);
             }
         }
     }
@@ -609,6 +617,9 @@ static void launch_f8mx(const GemmArgs &a, hipStream_t s) {
 // 24 / 32 / 96 / 160 -> 32, multiples of 64 -> 64).  Option "xm_ncg" / FP8A_XM_NCG=<1|2|4> forces it
 // (0 = this choice; A/B runs and identity tests).
 static int g_opt_xm_ncg = getenv("FP8A_XM_NCG") ? atoi(getenv("FP8A_XM_NCG")) : 0;  // option "xm_ncg"
+// "xm_sign_rows": gemm_f8mx_kernel builds the negative-sign half of its tile table only for launches
+// whose A words address it (1, the default); 0: always both halves (the same bits, for A/B runs)
+static int g_opt_xm_sign_rows = getenv("FP8A_XM_SIGN_ROWS") ? atoi(getenv("FP8A_XM_SIGN_ROWS")) : 1;
 static int xm_ncg(int64_t N) {
     const int forced = g_opt_xm_ncg;
     if (forced == 1 || forced == 2 || forced == 4) return forced;
@@ -742,7 +753,9 @@ static int device_cus() {
 // of a full one (a half-filled round costs a full one, a 6 %-filled one 0.45).  Splitting K
 // multiplies the tile count and divides the round length, and adds a pass that writes and
 // re-reads S*M*N partial floats (charged at 2 TB/s).  Each split keeps at least 16 K-tiles.
-// FP8A_SPLITK=<S> forces S (experiments).
+// FP8A_SPLITK=<S> forces S (experiments).  g_splitk_launches: launches that ran split (their
+// splitk_reduce_kernel stores the output), host-side, fp8a_splitk_stats.
+static uint64_t g_splitk_launches = 0;
 static int choose_splits(int64_t M, int64_t N, int64_t K) {
     static int forced = -1;
     if (forced < 0) {
@@ -1132,6 +1145,7 @@ static int run_gemm(GemmArgs &a, const int32_t *table, void *ws, size_t ws_bytes
             a.wfmt = v5mx ? 4 : tt ? (tt16_form(a.Mw, a.ttf7, a.K) ? 2 : 1) : 0;
             if (a.wfmt == 1 && !g_opt_tt_band) a.ebr = nullptr;  // (gemm_tt_kernel: no band test)
             a.xncg = tt ? 4 : xm_ncg(a.N);
+            a.xm_signs = g_opt_xm_sign_rows;
             // the input's word image from the previous launch (fp8a_conv2d_chain): its words replace
             // the A pre-pass, which then runs gated (only to write the fused quantizer's bias, or to
             // re-decode x if the image arrived invalid)
@@ -1206,6 +1220,7 @@ static int run_gemm(GemmArgs &a, const int32_t *table, void *ws, size_t ws_bytes
         const int64_t q = a.M * a.N;
         const unsigned rb = (unsigned)std::min<int64_t>((q / 4 + 255) / 256 + 1, 8192);
         splitk_reduce_kernel<<<rb, 256, 0, s>>>(a);
+        ++g_splitk_launches;
         rc = hip_check("fp8a split-K reduce launch");
         if (rc) return rc;
     }
@@ -1515,6 +1530,11 @@ int fp8a_set_option(const char *name, int value) {
         g_opt_xm_ncg = value;
         return old;
     }
+    if (strcmp(name, "xm_sign_rows") == 0) {
+        const int old = g_opt_xm_sign_rows;
+        g_opt_xm_sign_rows = value != 0;
+        return old;
+    }
     if (strcmp(name, "af32_maxct") == 0) {
         const int old = g_opt_af32_maxct;
         g_opt_af32_maxct = std::max(0, value);
@@ -1694,6 +1714,27 @@ int fp8a_clock_stats(uint64_t *out, int reset) {
         for (int i = 0; i < 3; ++i) v[i] += w[i];
     }
     for (int i = 0; i < 3; ++i) out[i] = v[i];
+    return FP8A_OK;
+}
+
+int fp8a_splitk_stats(uint64_t *out, int reset) {
+    if (out == nullptr) return fail(FP8A_EINVAL, "null pointer");
+    out[0] = g_splitk_launches;
+    if (reset) g_splitk_launches = 0;
+    return FP8A_OK;
+}
+
+int fp8a_xm_sign_stats(uint64_t *out, int reset) {
+    if (out == nullptr) return fail(FP8A_EINVAL, "null pointer");
+    if (hipDeviceSynchronize() != hipSuccess) return hip_check("fp8a_xm_sign_stats");
+    unsigned long long v[2] = {0, 0};
+    int (*parts[3])(unsigned long long *, bool) = {f8mx_signs_xf0, f8mx_signs_xf1, f8mx_signs_xf2};
+    for (auto f : parts) {
+        unsigned long long w[2] = {0, 0};
+        if (f(w, reset != 0) != 0) return hip_check("fp8a_xm_sign_stats");
+        for (int i = 0; i < 2; ++i) v[i] += w[i];
+    }
+    for (int i = 0; i < 2; ++i) out[i] = v[i];
     return FP8A_OK;
 }
 
@@ -2216,7 +2257,9 @@ size_t fp8a_word_image_bytes(int64_t Bn, int64_t C, int64_t H, int64_t W, int ph
 }
 
 // The emitting launch's header: [0] valid, [1] the next quantizer's maxval, [2] its float bias,
-// [3] its 2^(1 - bias) bit pattern (the grid's min normal), [4] the next convolution's bR.
+// [3] its 2^(1 - bias) bit pattern (the grid's min normal), [4] the next convolution's bR; [5] and
+// [6] are cleared here and collected by the producers (the words' scale-exponent extreme, and
+// "a negative word was emitted": fp8approx_common.h wave_sign_record).
 __global__ void emit_prep_kernel(uint32_t *hdr, FqIn fq, const int32_t *bR) {
     const float mx = *fq.mx, fb = fq_bias(mx, fq.E, fq.M);
     hdr[0] = 0u;
@@ -2225,6 +2268,7 @@ __global__ void emit_prep_kernel(uint32_t *hdr, FqIn fq, const int32_t *bR) {
     hdr[3] = (uint32_t)(128 - (int)fb) << 23;
     hdr[4] = (uint32_t)*bR;
     hdr[5] = 0u;  // 255 - the smallest scale exponent of the emitted nonzero words (wave_max_atomic)
+    hdr[6] = 0u;  // nonzero: a word with the sign row bit was emitted (wave_sign_record)
 }
 
 __global__ void word_image_fill_kernel(uint32_t *img, int64_t words) {

@@ -153,6 +153,8 @@ struct GemmArgs {
     int ttf7;          // gemm_tt_kernel: the table has negative entries (the F7 sign rule)
     int af32;          // gemm_f8mx_kernel reads A as fp32 and decodes it while staging (no A pre-pass)
     int xncg;          // gemm_f8mx_kernel's column groups per tile (4: 128 x 64, 2: 128 x 32, 1: 256 x 16)
+    int xm_signs;      // gemm_f8mx_kernel builds the negative-sign table rows only when flag[3] says an A word
+                       // addresses them (option "xm_sign_rows"; 0: always both halves)
     const uint2 *bqw;
     const uint32_t *lutw;  // the LDS table image (XM_LUT_WORDS words), written by xm_decode_b
     // E5M2 (gemm_f8mx_kernel XF = 1): per (K-step, 16-column group) the nonzero B elements' exponent
@@ -296,7 +298,8 @@ constexpr uint32_t XM_ZERO_WORD = 253u << 23;
 
 // Word-image emission (EmitW): one word per final output value at NCHW output index o (< 2^31,
 // the host checks).  The next quantizer's constants sit in the image's header (emit_prep_kernel:
-// [1] maxval, [2] its float bias, [3] 2^(1 - bias) bits, [4] bR), made wave-uniform (SGPRs) once
+// [1] maxval, [2] its float bias, [3] 2^(1 - bias) bits, [4] bR; [5] / [6] collect the emitted words'
+// scale-exponent extreme and "a negative word was written", below), made wave-uniform (SGPRs) once
 // per epilogue: the matrix-core kernel runs at its 80-VGPR budget, and per-thread copies of them
 // (or their recomputation from maxval) in VGPRs made it spill.
 struct EmitCtx {
@@ -344,24 +347,52 @@ __device__ __forceinline__ void wave_max_atomic(uint32_t *dst, uint32_t v) {
 // gemm_f8mx.h xm_needs_halving; the header's word 5 collects it for the consumer)
 __device__ __forceinline__ uint32_t word_sehi(uint32_t w) { return w == XM_ZERO_WORD ? 0u : 255u - (w >> 23); }
 
-__device__ __forceinline__ void emit1(const GemmArgs &p, const EmitCtx &e, int64_t o, float v, uint32_t &sehi) {
+// "A negative A word was written": gemm_f8mx_kernel's tile table holds the rows of s_a = 1 (8 + m_a)
+// only for launches whose A words address them (word bit 6; a zero's word has row bits 0, -0.0
+// included).  Every writer of form-0 words ORs its words into one register and records bit 6 after
+// its stores: the A pre-pass into the launch's flag[3], an emitting producer into header word [6] of
+// the image (emit_prep_kernel clears it; the consumer's gated pre-pass copies it to flag[3]).  The
+// word only ever goes 0 -> 1 within a launch, so the record is a store, not a read-modify-write,
+// skipped once the word reads 1 (the read first, as wave_max_atomic).
+constexpr uint32_t XM_SIGN_BIT = 0x40u;
+// The A pre-pass has up to 8192 blocks that end within microseconds of each other; recording into
+// one word, their stores serialise on it (ViT-B/16: +15 us on each of 73 pre-passes).  So its blocks
+// spread over flag words XM_SIGN_W0 .. + XM_SIGN_NW - 1 (the second half of the 256-byte flag block,
+// zeroed with the rest), and gemm_f8mx_kernel ORs them with flag[3] in its one read.
+constexpr int XM_SIGN_W0 = 32, XM_SIGN_NW = 32;
+// one thread's record (the exact kernels' emission; a block's or a wave's elected thread)
+__device__ __forceinline__ void sign_record(uint32_t *dst, uint32_t words_or) {
+    if ((words_or & XM_SIGN_BIT) != 0u && __hip_atomic_load(dst, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u)
+        __hip_atomic_store(dst, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+// one ballot per wave, then its first lane's record.  Every lane of the wave must call it.
+__device__ __forceinline__ void wave_sign_record(uint32_t *dst, uint32_t words_or) {
+    const bool any = __any((words_or & XM_SIGN_BIT) != 0u) != 0;
+    if ((threadIdx.x & 63) == 0 && any) sign_record(dst, XM_SIGN_BIT);
+}
+
+__device__ __forceinline__ void emit1(const GemmArgs &p, const EmitCtx &e, int64_t o, float v, uint32_t &sehi,
+                                      uint32_t &neg) {
     uint32_t wo;
     const uint32_t wi = emit_index(p, (uint32_t)o, wo);
     bool ok = true;
     const uint32_t w = emit_word(p, e, v, ok);
     p.em.w[wi] = w;
     sehi = max(sehi, word_sehi(w));
+    neg |= w;
     if (!ok) atomicOr(p.em.invalid, 1u);
 }
 // four consecutive outputs (o % 4 == 0 in an NCHW plane of hw % 4 == 0): one 16-B store when
 // they sit in one row of the image (Wo % 4 == 0: always; the interior rows start 16-B aligned)
-__device__ __forceinline__ void emit4(const GemmArgs &p, const EmitCtx &e, int64_t o, float4 v, uint32_t &sehi) {
+__device__ __forceinline__ void emit4(const GemmArgs &p, const EmitCtx &e, int64_t o, float4 v, uint32_t &sehi,
+                                      uint32_t &neg) {
     uint32_t wo;
     const uint32_t wi = emit_index(p, (uint32_t)o, wo);
     bool ok0 = true, ok1 = true, ok2 = true, ok3 = true;
     const uint4 w = make_uint4(emit_word(p, e, v.x, ok0), emit_word(p, e, v.y, ok1), emit_word(p, e, v.z, ok2),
                                emit_word(p, e, v.w, ok3));
     sehi = max(max(sehi, max(word_sehi(w.x), word_sehi(w.y))), max(word_sehi(w.z), word_sehi(w.w)));
+    neg |= (w.x | w.y) | (w.z | w.w);
     if (wo + 3 < (uint32_t)p.em.Wo && (wi & 3u) == 0u) {
         *reinterpret_cast<uint4 *>(p.em.w + wi) = w;
     } else {
@@ -429,17 +460,17 @@ __device__ __forceinline__ void store_tile(const GemmArgs &p, int64_t split, int
     // word-image emission from each final value (the split-K reduction emits instead)
     const bool emit = EMIT && !partial && p.em.w != nullptr;
     const EmitCtx ec = EMIT ? emit_ctx(p) : EmitCtx{};
-    uint32_t sehi = 0;
+    uint32_t sehi = 0, neg = 0;
     auto fin1 = [&](int64_t o, float v) {
         if (partial) return v;
         v = post1<GELU>(q, o, v, pb);
-        if (emit) emit1(q, ec, o, v, sehi);
+        if (emit) emit1(q, ec, o, v, sehi, neg);
         return v;
     };
     auto fin4 = [&](int64_t o, float4 v) {
         if (partial) return v;
         v = post4<GELU>(q, o, v, pb);
-        if (emit) emit4(q, ec, o, v, sehi);
+        if (emit) emit4(q, ec, o, v, sehi, neg);
         return v;
     };
     if (!p.nchw) {
@@ -485,7 +516,10 @@ __device__ __forceinline__ void store_tile(const GemmArgs &p, int64_t split, int
             }
         }
     }
-    if (emit) wave_max_atomic(p.em.invalid + 5, sehi);
+    if (emit) {
+        wave_max_atomic(p.em.invalid + 5, sehi);
+        wave_sign_record(p.em.invalid + 6, neg);
+    }
 }
 
 }  // namespace fp8a

@@ -26,6 +26,10 @@ void launch_f8mx_xf2(const GemmArgs &a, hipStream_t s);
 int f8mx_clock_xf0(unsigned long long *v, bool reset);
 int f8mx_clock_xf1(unsigned long long *v, bool reset);
 int f8mx_clock_xf2(unsigned long long *v, bool reset);
+// gemm_f8mx_kernel's launches by tile-table build, {positive rows only, both halves} (g_xm_sign)
+int f8mx_signs_xf0(unsigned long long *v, bool reset);
+int f8mx_signs_xf1(unsigned long long *v, bool reset);
+int f8mx_signs_xf2(unsigned long long *v, bool reset);
 
 // k_tt.hip: the tile-table kernels on pre-decoded operands (a.wfmt 1: gemm_tt_kernel, 2:
 // gemm_tt16_kernel + the gated f32 rerun); grid = gemm_fast_kernel's 64 x 64 tile grid.

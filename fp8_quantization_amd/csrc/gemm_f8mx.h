@@ -257,6 +257,23 @@ __device__ __forceinline__ uint32_t v5_word_a(float v, const DFmt &f) {
 __device__ __forceinline__ void xm_record_se(const GemmArgs &p, uint32_t sehi) {
     if (p.Mw == 2 && p.wfmt == 0) wave_max_atomic(p.flag + 1, sehi);
 }
+// ... and for the tile-table build: "one of the words addresses a row of s_a = 1" (`neg`: the OR of
+// the thread's words).  One record per block (every thread of the block calls it), into the block's
+// word of the spread sign words (XM_SIGN_W0, fp8approx_common.h).  Nothing is recorded, read or
+// stored, when the launch builds both halves anyway (option "xm_sign_rows" = 0).
+__device__ __forceinline__ void xm_record_sign(const GemmArgs &p, uint32_t neg) {
+    if (p.wfmt != 0 || !p.xm_signs) return;
+    // Ordinary (workgroup-scope) accesses, like the words themselves: the store stays in the block's own
+    // L2 until the kernel ends, and the guarding read is served there -- agent-scope stores go through to
+    // memory and cost ~11 ns each on this one line, whichever of its words they hit (+13 us per ViT
+    // pre-pass).  The next kernel sees the word as it sees the A words; a stale 0 here costs one more
+    // store, and no 1 can be stale (an earlier kernel zeroed the block).
+    if (__syncthreads_or((neg & XM_SIGN_BIT) ? 1 : 0) && threadIdx.x == 0) {
+        uint32_t *w = p.flag + XM_SIGN_W0 + ((blockIdx.y * gridDim.x + blockIdx.x) & (XM_SIGN_NW - 1));
+        if (__hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) == 0u)
+            __hip_atomic_store(w, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    }
+}
 
 // A pre-pass, one (image | row) per blockIdx.y step.  conv: the group's channel slice of x
 // [Bn][Cin][H][W] (channels cbase..cbase+aw_c) -> words [Bn][aw_c][awH][awW], x at (awph, awpw)
@@ -276,9 +293,12 @@ __global__ __launch_bounds__(256) void xm_decode_a(const GemmArgs p) {
     // gated (the input's word image was emitted by the previous launch, fp8a_conv2d_chain): the
     // words are already there unless an element left the window (the image's header word)
     if (p.gate != nullptr && __hip_atomic_load(p.gate, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u) {
-        // (the emitting launch recorded its words' smallest scale exponent in the image header)
-        if (p.Mw == 2 && p.wfmt == 0 && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0)
-            atomicMax(p.flag + 1, p.gate[5]);
+        // (the emitting launch recorded its words' smallest scale exponent, and whether one of them
+        // is negative, in the image header)
+        if (p.wfmt == 0 && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) {
+            if (p.Mw == 2) atomicMax(p.flag + 1, p.gate[5]);
+            if (p.xm_signs && p.gate[6] != 0u) atomicOr(p.flag + 3, 1u);
+        }
         return;
     }
     const uint32_t emnA = (uint32_t)(128 - bA) << 23;
@@ -290,6 +310,7 @@ __global__ __launch_bounds__(256) void xm_decode_a(const GemmArgs p) {
     const int64_t hw = p.H * p.W;
     const int64_t rows = p.conv ? p.M / (p.Ho * p.Wo) : p.M, cols = p.conv ? p.aw_c * p.awH * p.awW : p.awld;
     uint32_t sehi = 0;  // 255 - the smallest se of this thread's nonzero E5M2 words (xm_record_se)
+    uint32_t neg = 0;   // the OR of this thread's wfmt-0 words (xm_record_sign)
     const DFmt fv5 = dfmt(p.E, p.Mw, bA, false);  // (wfmt 4: the v5 decode, clip_OF)
     auto word = [&](float v, bool &ok) {
         if (p.fqin.mx) v = fq_apply(v, fmx, fbias, p.fqin.M, p.fqin.S);
@@ -298,6 +319,7 @@ __global__ __launch_bounds__(256) void xm_decode_a(const GemmArgs p) {
         if (p.wfmt) return tt_word_a(v, p.Mw, emnA, ok);
         const uint32_t w = xm_word_a(v, p.Mw, xm_xbias(p.Mw), emnA, bR, ok);
         sehi = max(sehi, word_sehi(w));
+        neg |= w;
         return w;
     };
     const uint32_t zw = p.wfmt ? 0u : XM_ZERO_WORD;  // the word of a zero (padding, columns >= K)
@@ -353,6 +375,7 @@ __global__ __launch_bounds__(256) void xm_decode_a(const GemmArgs p) {
         if (__syncthreads_or(bad ? 1 : 0) && threadIdx.x == 0) atomicOr(p.flag, fb_bits(p, biasbad));
         if (__syncthreads_or(win ? 0 : 1) && threadIdx.x == 0) atomicOr(p.flag, 4u);  // gemm_tt16_kernel's window (A)
         xm_record_se(p, sehi);
+        xm_record_sign(p, neg);
         return;
     }
     // 16-B form: every row start 16-B aligned and the valid columns a multiple of 4 (all the
@@ -425,6 +448,7 @@ __global__ __launch_bounds__(256) void xm_decode_a(const GemmArgs p) {
     if (__syncthreads_or(bad ? 1 : 0) && threadIdx.x == 0) atomicOr(p.flag, fb_bits(p, biasbad));
     if (__syncthreads_or(win ? 0 : 1) && threadIdx.x == 0) atomicOr(p.flag, 4u);  // gemm_tt16_kernel's window (A)
     xm_record_se(p, sehi);
+    xm_record_sign(p, neg);
 }
 #else
 __global__ void xm_decode_a(const GemmArgs p);
@@ -513,6 +537,10 @@ __global__ void xm_decode_b(const GemmArgs p, int64_t kpad);
 #define FP8A_CLOCK_STAMP 0
 #endif
 __device__ unsigned long long g_clk[3];
+// Launches (the halved-block reruns apart) whose tile-table build wrote the positive-sign rows only
+// [0] / both halves [1]: thread 0 of block 0 counts; read per translation unit (k_f8mx.hip) by
+// fp8a_xm_sign_stats.
+__device__ unsigned long long g_xm_sign[2];
 #if FP8A_CLOCK_STAMP
 #define FP8A_CLK_BEGIN const uint64_t clk_t0 = __builtin_amdgcn_s_memtime(), clk_r0 = __builtin_amdgcn_s_memrealtime();
 #define FP8A_CLK_END                                                                                   \
@@ -575,6 +603,15 @@ __global__ __launch_bounds__(256, (XmWaves<AF32, EMIT>::value)) void gemm_f8mx_k
     const int64_t bid = (int64_t)blockIdx.x % tiles, split = (int64_t)blockIdx.x / tiles;
     const int64_t m0 = (bid % num_mt) * BMT;
     const int64_t n0 = (bid / num_mt) * BNT;
+    // The build writes the table rows of s_a = 1 (8 + m_a) only when an A word of the launch addresses
+    // them: the pre-pass left that in the spread sign words (xm_record_sign), the producer of the
+    // word image in flag[3] -- one load per wave, lanes 0-31 a spread word each, the rest flag[3].
+    // Wave-uniform, read once.  (AF32 decodes A while staging and cannot know: both halves.)
+    bool both = true;
+    if (!AF32 && p.xm_signs)
+        both = __any(__hip_atomic_load(p.flag + (lane < XM_SIGN_NW ? XM_SIGN_W0 + lane : 3), __ATOMIC_RELAXED,
+                                       __HIP_MEMORY_SCOPE_WORKGROUP) != 0u) != 0;  // (written by earlier kernels only)
+    if (XF != 2 && blockIdx.x == 0 && tid == 0) atomicAdd(&g_xm_sign[both ? 1 : 0], 1ull);
     if (XF == 2 && !xm_half_gate(p, m0, BMT, n0, BNT)) return;  // (a tile the plain form completed)
     const int kbeg = (int)(split * p.kchunk), kend = (int)min(p.K, (int64_t)kbeg + p.kchunk), K32 = (int)p.K;
     const int bR = *p.bR;
@@ -758,23 +795,46 @@ __global__ __launch_bounds__(256, (XmWaves<AF32, EMIT>::value)) void gemm_f8mx_k
 #pragma unroll
         for (int i = 0; i < APR; ++i)
             *reinterpret_cast<uint2 *>(&sm.aw[akp][2 * (arow + 64 * i)]) = make_uint2(wa[i][0], wa[i][1]);
-        // build: rows 2 q4, 2 q4 + 1 of both signs for the unit's two column pairs
+        // build: rows 2 q4, 2 q4 + 1 for the unit's two column pairs, of both signs -- or of s_a = +
+        // only (`both` false: no lane addresses rows 8-15, which keep stale words).  One uniform
+        // branch per tile around two copies of the unit loop.  The full copy is the build as it
+        // always was; the half copy's addends pass through an empty asm, so that the compiler
+        // cannot merge the two copies' common adds (it then hoists them above the branch and
+        // splits the ds_write_b128 -- and a branch per unit around the negative half alone left
+        // launches with signed A 1 % slower).  (Two copies of the whole K loop: 96 VGPRs and 5-12
+        // spilled in the 128 x 64 instances.)
         if (build) {
-#pragma unroll
-            for (int u = 0; u < BU; ++u) {
+            auto pk = [](uint32_t v, xm_u2 ad) { return __builtin_bit_cast(uint32_t, __builtin_bit_cast(xm_u2, v) + ad); };
+            auto unit_b = [&](int u) {
 #if XM_BDMA
-                const uint4 b = sm.bw[(bkk0 + u * BKU) * TXN + btx];
+                return sm.bw[(bkk0 + u * BKU) * TXN + btx];
 #else
-                const uint4 b = wbq[u];
+                return wbq[u];
 #endif
-                const uint2 s0 = *reinterpret_cast<const uint2 *>(lut + b.y + 8 * q4);
-                const uint2 s1 = *reinterpret_cast<const uint2 *>(lut + b.w + 8 * q4);
-                const xm_u2 a0 = __builtin_bit_cast(xm_u2, b.x), a1 = __builtin_bit_cast(xm_u2, b.z);
-                const xm_u2 n0 = __builtin_bit_cast(xm_u2, b.x ^ 0x80008000u), n1 = __builtin_bit_cast(xm_u2, b.z ^ 0x80008000u);
-                auto pk = [](uint32_t v, xm_u2 ad) { return __builtin_bit_cast(uint32_t, __builtin_bit_cast(xm_u2, v) + ad); };
-                uint32_t *d = &sm.tt[bkk0 + u * BKU][btx * 32 + q4 * 4];
-                *reinterpret_cast<uint4 *>(d) = make_uint4(pk(s0.x, a0), pk(s1.x, a1), pk(s0.y, a0), pk(s1.y, a1));
-                *reinterpret_cast<uint4 *>(d + 16) = make_uint4(pk(s0.x, n0), pk(s1.x, n1), pk(s0.y, n0), pk(s1.y, n1));
+            };
+            if (both) {
+#pragma unroll
+                for (int u = 0; u < BU; ++u) {
+                    const uint4 b = unit_b(u);
+                    const uint2 s0 = *reinterpret_cast<const uint2 *>(lut + b.y + 8 * q4);
+                    const uint2 s1 = *reinterpret_cast<const uint2 *>(lut + b.w + 8 * q4);
+                    const xm_u2 a0 = __builtin_bit_cast(xm_u2, b.x), a1 = __builtin_bit_cast(xm_u2, b.z);
+                    const xm_u2 n0 = __builtin_bit_cast(xm_u2, b.x ^ 0x80008000u), n1 = __builtin_bit_cast(xm_u2, b.z ^ 0x80008000u);
+                    uint32_t *d = &sm.tt[bkk0 + u * BKU][btx * 32 + q4 * 4];
+                    *reinterpret_cast<uint4 *>(d) = make_uint4(pk(s0.x, a0), pk(s1.x, a1), pk(s0.y, a0), pk(s1.y, a1));
+                    *reinterpret_cast<uint4 *>(d + 16) = make_uint4(pk(s0.x, n0), pk(s1.x, n1), pk(s0.y, n0), pk(s1.y, n1));
+                }
+            } else {
+#pragma unroll
+                for (int u = 0; u < BU; ++u) {
+                    uint4 b = unit_b(u);
+                    asm volatile("" : "+v"(b.x), "+v"(b.z));
+                    const uint2 s0 = *reinterpret_cast<const uint2 *>(lut + b.y + 8 * q4);
+                    const uint2 s1 = *reinterpret_cast<const uint2 *>(lut + b.w + 8 * q4);
+                    const xm_u2 a0 = __builtin_bit_cast(xm_u2, b.x), a1 = __builtin_bit_cast(xm_u2, b.z);
+                    uint32_t *d = &sm.tt[bkk0 + u * BKU][btx * 32 + q4 * 4];
+                    *reinterpret_cast<uint4 *>(d) = make_uint4(pk(s0.x, a0), pk(s1.x, a1), pk(s0.y, a0), pk(s1.y, a1));
+                }
             }
         }
         __syncthreads();

@@ -49,15 +49,27 @@ static int clock_read(unsigned long long *v, bool reset) {
     return 0;
 }
 
+static int signs_read(unsigned long long *v, bool reset) {
+    if (hipMemcpyFromSymbol(v, HIP_SYMBOL(g_xm_sign), 2 * sizeof(unsigned long long)) != hipSuccess) return -1;
+    if (reset) {
+        const unsigned long long z[2] = {0, 0};
+        if (hipMemcpyToSymbol(HIP_SYMBOL(g_xm_sign), z, sizeof(z)) != hipSuccess) return -1;
+    }
+    return 0;
+}
+
 #if FP8A_XF_PART == 0
 void launch_f8mx_xf0(const GemmArgs &a, hipStream_t s) { launch_xf<0>(a, s); }
 int f8mx_clock_xf0(unsigned long long *v, bool reset) { return clock_read(v, reset); }
+int f8mx_signs_xf0(unsigned long long *v, bool reset) { return signs_read(v, reset); }
 #elif FP8A_XF_PART == 1
 void launch_f8mx_xf1(const GemmArgs &a, hipStream_t s) { launch_xf<1>(a, s); }
 int f8mx_clock_xf1(unsigned long long *v, bool reset) { return clock_read(v, reset); }
+int f8mx_signs_xf1(unsigned long long *v, bool reset) { return signs_read(v, reset); }
 #else
 void launch_f8mx_xf2(const GemmArgs &a, hipStream_t s) { launch_xf<2>(a, s); }
 int f8mx_clock_xf2(unsigned long long *v, bool reset) { return clock_read(v, reset); }
+int f8mx_signs_xf2(unsigned long long *v, bool reset) { return signs_read(v, reset); }
 #endif
 
 }  // namespace fp8a

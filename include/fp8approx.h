@@ -75,6 +75,23 @@ int fp8a_fallback_stats(uint64_t *out, int reset);
 int fp8a_path_stats(uint64_t *out, int reset);
 
 /*
+ * The matrix-core kernel's launches by tile-table build since load (or the last reset), out[2]:
+ *   [0] launches that wrote the positive-sign rows only (no A word of the launch is negative: the
+ *       A pre-pass, or the producer of the input's word image, recorded none),
+ *   [1] launches that wrote both halves (a negative A word, the fp32-staging form, or option
+ *       "xm_sign_rows" = 0).
+ * The halved-block E5M2 rerun of a launch is not counted again.  Synchronises the device; reset != 0
+ * zeroes the counters after reading.
+ */
+int fp8a_xm_sign_stats(uint64_t *out, int reset);
+
+/*
+ * out[1]: GEMM launches since load (or the last reset) that ran split along K, i.e. whose output --
+ * and word image, when chained -- the split-K reduction wrote (host-side counter, no device sync).
+ */
+int fp8a_splitk_stats(uint64_t *out, int reset);
+
+/*
  * Diagnostics: the byte size of one slot of the flag arena of (current device, stream), 0 before
  * the stream's first eager launch.  Slots only grow (a launch that needs more allocates a larger
  * arena; the old one is retired, never freed, so launches still in flight keep valid memory).
@@ -105,6 +122,8 @@ int fp8a_kernel_time(double *out, int reset);
  * (the stem) as direct fp32 FMAs instead of the bf16 matrix-core GEMM;
  * "v5ds" (default 1; FP8A_V5DS) -- the v5 (E5M2, adder wrap) depthwise 3x3 on the staged kernel
  * with both word pre-passes fused (0: the pre-passes + the word-form kernel; same bits);
+ * "xm_sign_rows" (default 1; FP8A_XM_SIGN_ROWS) -- gemm_f8mx_kernel builds the negative-sign rows of
+ * its tile table only for launches with a negative A word (0: always, fp8a_xm_sign_stats);
  * "xm_ncg" (default 0 = by N; FP8A_XM_NCG) -- gemm_f8mx_kernel's tile width forced to 16 x 1 / 2
  * / 4 columns; "af32_maxct" (default 1, times sh x sw for a strided conv; FP8A_AF32_MAXCT) -- the most column tiles for which a 1x1
  * conv / matrix A is decoded inside gemm_f8mx_kernel instead of by its pre-pass (0 = never);

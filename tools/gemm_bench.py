@@ -1,11 +1,12 @@
 #!/usr/bin/env python
 """Per-layer throughput of the approx conv/GEMM kernel on the ResNet-18 layer shapes.
 
-    python tools/gemm_bench.py [--batch 256] [--mode w1u|none|w2s|lut] [--reps 5]
+    python tools/gemm_bench.py [--batch 256] [--mode w1u|none|w2s|lut] [--reps 5] [--nonneg-a]
 
 Times fp8a_conv2d (implicit GEMM) with HIP events on the current stream, random FP8-grid
 operands of realistic magnitude; prints one JSON line per layer and a total.
-FP8A_LIB_PATH selects an alternative build of libfp8approx.so (A/B of kernel variants).
+--nonneg-a: activations >= 0, as after a ReLU (gemm_f8mx_kernel then builds the positive table rows
+only; FP8A_XM_SIGN_ROWS=0 for the full build on the same data).  FP8A_LIB_PATH selects an alternative build of libfp8approx.so (A/B of kernel variants).
 """
 import argparse
 import json
@@ -44,6 +45,7 @@ def main():
     ap.add_argument("--mode", default="w1u", choices=sorted(MODES))
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--layers", default="")
+    ap.add_argument("--nonneg-a", action="store_true")
     args = ap.parse_args()
     import fp8_quantization_amd as fa
     from fp8_quantization_amd.error_tables import get_error_table_NN
@@ -62,6 +64,8 @@ def main():
         if args.layers and name not in args.layers.split(","):
             continue
         x = grid(rng, E, M, (args.batch, cin, h, h), bA, 0.5).to(dev)
+        if args.nonneg_a:
+            x = x.abs()
         w = grid(rng, E, M, (cout, cin, k, k), bB, 0.0).to(dev)
         bW = torch.full((cout,), bB, dtype=torch.int32, device=dev)
         args_ = dict(flags=fl, stride=(s, s), padding=(p, p))

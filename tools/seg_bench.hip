@@ -29,11 +29,14 @@ struct Stage {
     uint32_t aw[XBK / 2][AWQ];
 };
 
-enum { P_LDS = 1, P_CVT = 2, P_MFMA = 4, P_BUILD = 8, P_BAR = 16, P_STAGE = 32, P_GLOAD = 64 };
+enum { P_LDS = 1, P_CVT = 2, P_MFMA = 4, P_BUILD = 8, P_BAR = 16, P_STAGE = 32, P_GLOAD = 64, P_POS = 128, P_POSRT = 256 };
+// P_POS: the build writes the positive-sign rows only (no n0 / n1 addends, no d + 16 store), fixed
+// at compile time -- the bound.  P_POSRT: the same chosen by a wave-uniform word read once before
+// the loop (`negrows`, 0 here), i.e. the in-loop uniform branch a product kernel would carry.
 
 template <int P, int WAVES>
 __global__ __launch_bounds__(256, WAVES) void seg(const uint32_t *seed, float *out, unsigned long long *cyc, int tiles,
-                                                  const uint32_t *gbuf) {
+                                                  const uint32_t *gbuf, const uint32_t *negrows) {
     __shared__ __attribute__((aligned(16))) Stage sm;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     // fill LDS with plausible data: table words = random bf16 pairs near 1.0, A words = se << 23 | row << 3
@@ -80,6 +83,7 @@ __global__ __launch_bounds__(256, WAVES) void seg(const uint32_t *seed, float *o
             gb[u] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(grs, (int)(gB + 4096u * u), (int)(ko & 0x3FFFFFu), 0));
     };
     if (P & P_GLOAD) gload(0);
+    const bool both = (P & P_POS) ? false : (P & P_POSRT) ? __builtin_amdgcn_readfirstlane((int)negrows[0]) != 0 : true;
     __syncthreads();
     const unsigned long long t0 = __builtin_amdgcn_s_memtime();
     for (int it = 0; it < tiles; ++it) {
@@ -100,7 +104,7 @@ __global__ __launch_bounds__(256, WAVES) void seg(const uint32_t *seed, float *o
                 auto pk = [](uint32_t v, u2 ad) { return __builtin_bit_cast(uint32_t, __builtin_bit_cast(u2, v) + ad); };
                 uint32_t *d = &sm.tt[bkk[u]][btx * 32 + q4 * 4];
                 *reinterpret_cast<uint4 *>(d) = make_uint4(pk(s0.x, a0), pk(s1.x, a1), pk(s0.y, a0), pk(s1.y, a1));
-                *reinterpret_cast<uint4 *>(d + 16) = make_uint4(pk(s0.x, n0), pk(s1.x, n1), pk(s0.y, n0), pk(s1.y, n1));
+                if (both) *reinterpret_cast<uint4 *>(d + 16) = make_uint4(pk(s0.x, n0), pk(s1.x, n1), pk(s0.y, n0), pk(s1.y, n1));
             }
         }
         if (P & P_BAR) __syncthreads();
@@ -157,20 +161,20 @@ __global__ __launch_bounds__(256, WAVES) void seg(const uint32_t *seed, float *o
     if (tid == 0) cyc[blockIdx.x] = t1 - t0;
 }
 
-typedef void (*kfn)(const uint32_t *, float *, unsigned long long *, int, const uint32_t *);
+typedef void (*kfn)(const uint32_t *, float *, unsigned long long *, int, const uint32_t *, const uint32_t *);
 
 template <int P, int W>
 static void run(const char *name, int cus, const uint32_t *seed, float *out, unsigned long long *cyc, int tiles,
                 const uint32_t *gbuf) {
     const int blocks = cus * W;  // one workgroup = one wave per SIMD; W workgroups per CU
     kfn f = seg<P, W>;
-    f<<<blocks, 256>>>(seed, out, cyc, 4, gbuf);
+    f<<<blocks, 256>>>(seed, out, cyc, 4, gbuf, gbuf);
     hipDeviceSynchronize();
     hipEvent_t a, b;
     hipEventCreate(&a);
     hipEventCreate(&b);
     hipEventRecord(a);
-    f<<<blocks, 256>>>(seed, out, cyc, tiles, gbuf);
+    f<<<blocks, 256>>>(seed, out, cyc, tiles, gbuf, gbuf);
     hipEventRecord(b);
     hipEventSynchronize(b);
     float ms;
@@ -213,6 +217,16 @@ int main(int argc, char **argv) {
     run<ALLG, 6>("full + global loads", cus, seed, out, cyc, tiles, gbuf);
     run<ALL, 5>("full (stage+build+bar+lds+cvt+mfma)", cus, seed, out, cyc, tiles, gbuf);
     run<ALL, 6>("full (stage+build+bar+lds+cvt+mfma)", cus, seed, out, cyc, tiles, gbuf);
+    run<ALLG | P_POS, 5>("full + global loads, pos rows", cus, seed, out, cyc, tiles, gbuf);
+    run<ALLG | P_POS, 6>("full + global loads, pos rows", cus, seed, out, cyc, tiles, gbuf);
+    run<ALL | P_POS, 5>("full, pos rows only", cus, seed, out, cyc, tiles, gbuf);
+    run<ALL | P_POS, 6>("full, pos rows only", cus, seed, out, cyc, tiles, gbuf);
+    run<ALLG | P_POSRT, 5>("full + global loads, pos rows (rt)", cus, seed, out, cyc, tiles, gbuf);
+    run<ALLG | P_POSRT, 6>("full + global loads, pos rows (rt)", cus, seed, out, cyc, tiles, gbuf);
+    run<ALL | P_POSRT, 5>("full, pos rows only (rt)", cus, seed, out, cyc, tiles, gbuf);
+    run<ALL | P_POSRT, 6>("full, pos rows only (rt)", cus, seed, out, cyc, tiles, gbuf);
+    run<ALLG, 5>("full + global loads (repeat)", cus, seed, out, cyc, tiles, gbuf);
+    run<ALLG, 6>("full + global loads (repeat)", cus, seed, out, cyc, tiles, gbuf);
     run<ALL, 4>("full", cus, seed, out, cyc, tiles, gbuf);
     run<ALL, 2>("full", cus, seed, out, cyc, tiles, gbuf);
     run<ALL & ~P_BAR, 6>("no barriers", cus, seed, out, cyc, tiles, gbuf);
