@@ -25,7 +25,8 @@ SYMBOLS = ("fp8a_version", "fp8a_last_error", "fp8a_fallback_stats", "fp8a_path_
            "fp8a_dense_conv2d_workspace_size", "fp8a_dense_conv2d", "fp8a_grouped_conv2d", "fp8a_dense_conv2d_fused", "fp8a_dense_stats", "fp8a_clock_stats",
            "fp8a_xm_sign_stats", "fp8a_splitk_stats",
            "fp8a_word_image_bytes", "fp8a_word_image_init", "fp8a_conv2d_chain", "fp8a_conv2d_wants_image",
-           "fp8a_flag_arena_slot_bytes")
+           "fp8a_flag_arena_slot_bytes",
+           "fp8a_check_workspace_size", "fp8a_matmul_check", "fp8a_conv2d_check_workspace_size", "fp8a_conv2d_check")
 
 _lib = None
 
@@ -99,6 +100,12 @@ def load():
         "fp8a_xm_sign_stats": ([P, I], I),
         "fp8a_splitk_stats": ([P, I], I),
         "fp8a_flag_arena_slot_bytes": ([P], SZ),
+        "fp8a_check_workspace_size": ([I64, I64, I64], SZ),
+        "fp8a_matmul_check": ([P, I64, P, I64, I64, P, I64, I64, I64, I64, I, I, P, P, I64, P, P, U, P, P, P, P, SZ,
+                               P], I),
+        "fp8a_conv2d_check_workspace_size": ([I64, I64, I64, I64, I64, I, I, I, I, I, I, I, I, I], SZ),
+        "fp8a_conv2d_check": ([P, P, P, I64, I64, I64, I64, I64, I, I, I, I, I, I, I, I, I, I, I, P, P, P, P, U, P, P,
+                               P, P, SZ, P], I),
     }
     for name, (args, res) in sig.items():
         f = getattr(L, name)

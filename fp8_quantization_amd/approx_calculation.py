@@ -22,8 +22,9 @@ import torch.nn.functional as F
 from torch import nn
 
 from . import _lib
-from .approx_ops import (_bias_dev, _res_quant_params, approx_conv2d, approx_matmul, approx_matmul_block, bias_epilogue,
-                         dense_conv2d, dense_format, dense_matmul, grouped_conv2d, make_flags, make_flags_v5, qamaa_conv2d,
+from .approx_ops import (_bias_dev, _res_quant_params, approx_conv2d, approx_conv2d_check, approx_matmul,
+                         approx_matmul_block, approx_matmul_check, bias_epilogue, dense_conv2d, dense_format,
+                         dense_matmul, format_self_check, grouped_conv2d, make_flags, make_flags_v5, qamaa_conv2d,
                          qamaa_matmul)
 from .error_tables import get_comp_table_NN_v5, get_error_table_NN
 from .quantization.hijacker import QuantizationHijacker
@@ -76,11 +77,35 @@ class ApproxOpMixin:
     def _qamaa_params(self):
         return _res_quant_params(self.res_quantizer)
 
+    # the layer's last self-check (approx_ops.CheckStats), set by a forward with
+    # custom_approx_params['self_check_mode'] on
+    last_self_check = None
+
+    def _self_check_on(self):
+        """custom_approx_params['self_check_mode'] (approx_calculation.py:763-809, 935-994) with the
+        approx product on: the layer then runs unfused, and after its production launch the fused
+        check kernel runs on the same operands (v9 model only)."""
+        p = getattr(self, "custom_approx_params", None) or {}
+        return bool(p.get("self_check_mode", False)) and bool(getattr(self, "approx_flag", False)) \
+            and p.get("approx_version", 9) != 5
+
+    def _self_check(self, check_op, flags, prod, *args, **kwargs):
+        """Run the check op on the production launch's operands, keep its CheckStats and print the
+        reference's block (one per launch; the reference prints one per output column)."""
+        _, _, stats = check_op(*args, flags=flags, prod=prod, **kwargs)
+        self.last_self_check = stats
+        print(format_self_check(stats, flags))
+
     def approx_multiply(self, x, y, x_bias, y_bias, res_bias):
         """x [M, K] @ y [K, N] with the operator's approx configuration."""
         E, M, table, flags = self._approx_config()
         x_bias = self._default_bias(x_bias, E, x.device)
         res_bias = self._default_bias(res_bias, E, x.device)
+        if self._self_check_on():
+            fl = flags if y.shape[1] != 1 else flags | _lib.TB  # (single column: tensor-bias semantics, F5)
+            out = approx_matmul(x, y, E, M, x_bias, y_bias, res_bias, table, flags=fl)
+            self._self_check(approx_matmul_check, fl, out, x, y, E, M, x_bias, y_bias, res_bias, table)
+            return out
         if y.shape[1] != 1:
             if self.approx_flag:
                 return approx_matmul(x, y, E, M, x_bias, y_bias, res_bias, table, flags=flags)
@@ -131,8 +156,15 @@ class ApproxConv2dMixin(ApproxOpMixin, ChainConsumerMixin):
         _lib.check(rc, "fp8a_im2col")
         return out
 
-    supports_bn_act_epilogue = True
-    supports_input_quant_fusion = True
+    # (the self-check runs the layer unfused: the check op needs the quantized operands and the
+    # product before BN / activation / tail)
+    @property
+    def supports_bn_act_epilogue(self):
+        return not self._self_check_on()
+
+    @property
+    def supports_input_quant_fusion(self):
+        return not self._self_check_on()
 
     def run_forward(self, x, weight, bias, offsets=None, epilogue=None, qin=None, post=None, chain=None):
         """qin: the layer's input FPQuantizer when the hijacker fused it (x unquantized; the op
@@ -178,6 +210,11 @@ class ApproxConv2dMixin(ApproxOpMixin, ChainConsumerMixin):
             else:
                 out = approx_conv2d(x.detach(), weight.detach(), E, M, self._default_bias(a_bias, E, x.device),
                                     w_bias, self._default_bias(r_bias, E, x.device), table, **args)
+                if self._self_check_on():
+                    self._self_check(approx_conv2d_check, flags, out, x.detach(), weight.detach(), E, M,
+                                     self._default_bias(a_bias, E, x.device), w_bias,
+                                     self._default_bias(r_bias, E, x.device), table, stride=self.stride,
+                                     padding=self.padding, dilation=self.dilation, groups=self.groups)
         elif self.quantize_after_mult_and_add and self.out_channels // self.groups != 1:
             out = qamaa_conv2d(x.detach(), weight.detach(), *self._qamaa_params(), stride=self.stride,
                                padding=self.padding, dilation=self.dilation, groups=self.groups)
@@ -240,7 +277,7 @@ class ApproxLinearMixin(ApproxOpMixin):
         # (with autograd recording a trainable bias, the separate `out += bias` keeps its gradient)
         p = self.custom_approx_params
         b = getattr(self, "bias", None)
-        return (self.fuse_linear_block and self.approx_flag and self.out_features != 1
+        return (self.fuse_linear_block and self.approx_flag and self.out_features != 1 and not self._self_check_on()
                 and p.get("approx_version", 9) != 5 and self.get_weights_fp_bias() is not None
                 and not (b is not None and b.requires_grad and torch.is_grad_enabled()))
 

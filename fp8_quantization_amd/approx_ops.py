@@ -24,7 +24,8 @@ from .error_tables import get_error_table_NN  # noqa: F401  (re-exported, v9:555
 __all__ = ["custom_matmul_vectorize", "approx_matmul", "approx_matmul_block", "approx_terms", "approx_conv2d", "qamaa_matmul", "qamaa_conv2d",
            "quant_to_fp_any_vectorize_torch", "float_to_fpany_absint_torch", "get_error_table_NN",
            "make_flags", "make_flags_v5", "fp8_fake_quantize", "bn_act_epilogue", "dense_format", "dense_matmul",
-           "dense_conv2d", "grouped_conv2d", "dense_conv2d_fused"]
+           "dense_conv2d", "grouped_conv2d", "dense_conv2d_fused", "approx_matmul_check", "approx_conv2d_check",
+           "CheckStats", "format_self_check", "SELF_CHECK_LABELS"]
 
 
 def make_flags(with_approx=True, with_s2nn2s_opt=False, quant_btw_mult_accu=True, golden_clip_OF=False,
@@ -268,6 +269,205 @@ def approx_terms(A, B, E, M, bA, bB, bR, table=None, flags=None, **flag_kwargs):
     return T
 
 
+# ----------------------------------------------------------------------------------- self-check
+class _CheckStatsStruct(ctypes.Structure):
+    """fp8a_check_stats (include/fp8approx.h): 96 bytes, natural alignment."""
+    _fields_ = [("n_out", ctypes.c_uint64), ("sum_err", ctypes.c_double), ("sum_err2", ctypes.c_double),
+                ("sum_gold2", ctypes.c_double), ("a_norm", ctypes.c_uint64), ("a_total", ctypes.c_uint64),
+                ("b_norm", ctypes.c_uint64), ("b_total", ctypes.c_uint64), ("r_norm", ctypes.c_uint64),
+                ("r_total", ctypes.c_uint64), ("max_err", ctypes.c_float), ("prod_max_abs", ctypes.c_float),
+                ("prod_max_rel", ctypes.c_float), ("has_prod", ctypes.c_uint32)]
+
+
+CHECK_STATS_BYTES = ctypes.sizeof(_CheckStatsStruct)
+
+
+class CheckStats:
+    """The raw fields of fp8a_check_stats plus the figures the reference prints from them
+    (approx_matmul_whole_v9.py:124-157).  ``raw`` keeps the struct's bytes, ``S`` the device tensor
+    of sum_k |v_k| (the scale of the project's 1e-5 S bar) in the output's shape, when the op
+    returned one."""
+    FIELDS = tuple(n for n, _ in _CheckStatsStruct._fields_)
+
+    def __init__(self, S=None, raw=None, **fields):
+        for n in self.FIELDS:
+            setattr(self, n, fields.pop(n, 0))
+        if fields:
+            raise TypeError(f"unknown CheckStats fields: {sorted(fields)}")
+        self.S = S
+        self.raw = raw
+
+    @classmethod
+    def from_bytes(cls, buf, S=None):
+        buf = bytes(buf)
+        st = _CheckStatsStruct.from_buffer_copy(buf)
+        return cls(S=S, raw=buf, **{n: getattr(st, n) for n in cls.FIELDS})
+
+    @property
+    def max(self):
+        return self.max_err
+
+    @property
+    def mean(self):
+        return self.sum_err / self.n_out if self.n_out else 0.0
+
+    @property
+    def rmse(self):
+        return (self.sum_err2 / self.n_out) ** 0.5 if self.n_out else 0.0
+
+    @property
+    def sqnr_db(self):
+        """10 log10(sum G^2 / sum e^2): inf when the approx sum equals the golden one everywhere."""
+        import math
+        if self.sum_err2 == 0.0:
+            return math.inf
+        return 10.0 * math.log10(self.sum_gold2 / self.sum_err2) if self.sum_gold2 > 0.0 else -math.inf
+
+    @staticmethod
+    def _pct(num, den):
+        return 100.0 * num / den if den else None
+
+    @property
+    def a_norm_pct(self):
+        return self._pct(self.a_norm, self.a_total)
+
+    @property
+    def b_norm_pct(self):
+        return self._pct(self.b_norm, self.b_total)
+
+    @property
+    def r_norm_pct(self):
+        """None with with_s2nn2s_opt: the reference has no R_3d mask there (v9:122)."""
+        return self._pct(self.r_norm, self.r_total)
+
+    def as_dict(self):
+        d = {n: getattr(self, n) for n in self.FIELDS}
+        d.update(mean=self.mean, rmse=self.rmse, sqnr_db=self.sqnr_db, a_norm_pct=self.a_norm_pct,
+                 b_norm_pct=self.b_norm_pct, r_norm_pct=self.r_norm_pct)
+        return d
+
+    def __repr__(self):
+        return "CheckStats(" + ", ".join(f"{k}={v}" for k, v in self.as_dict().items()) + ")"
+
+
+# the labels of the reference's self-check block, in its order (v9:147-157)
+SELF_CHECK_LABELS = ("====== Self-Checking Mode ======", "With Approximation    =", "With S2N & N2S Opt    =",
+                     "Quant btw Mult & Accu =", "Normal Values in A_2d :", "Normal Values in B_2d :",
+                     "Normal Values in R_3d :", "MatMul Max  Error     :", "MatMul Mean Error     :",
+                     "MatMul RMSE           :")
+
+
+def format_self_check(stats, flags):
+    """The reference's self-check block (v9:147-157) from a CheckStats: same labels, same order;
+    the R_3d line only without with_s2nn2s_opt."""
+    L = SELF_CHECK_LABELS
+    s2n = bool(flags & _lib.S2N)
+    lines = ["", L[0], f"{L[1]} {bool(flags & _lib.APPROX)}", f"{L[2]} {s2n}", f"{L[3]} {bool(flags & _lib.QBMA)}",
+             f"{L[4]} {stats.a_norm}/{stats.a_total} = {stats.a_norm_pct:.1f}%",
+             f"{L[5]} {stats.b_norm}/{stats.b_total} = {stats.b_norm_pct:.1f}%"]
+    if not s2n:
+        lines.append(f"{L[6]} {stats.r_norm}/{stats.r_total} = {stats.r_norm_pct:.1f}%")
+    lines += [f"{L[7]} {stats.max_err}", f"{L[8]} {stats.mean}", f"{L[9]} {stats.rmse}"]
+    return "\n".join(lines)
+
+
+def _aligned_workspace(device, nbytes):
+    """A 256-byte aligned uint8 view of at least nbytes."""
+    buf = torch.empty(int(nbytes) + 256, dtype=torch.uint8, device=device)
+    off = (-buf.data_ptr()) % 256
+    return buf[off:off + int(nbytes)]
+
+
+def _check_prod(prod, like):
+    if prod is None:
+        return None
+    prod = _as_f32(prod).contiguous()
+    if prod.shape != like.shape or prod.device != like.device:
+        raise AssertionError(f"self-check: prod must be {tuple(like.shape)} on {like.device}")
+    return prod
+
+
+def approx_matmul_check(A, B, E, M, bA, bB, bR, table=None, flags=None, prod=None, **flag_kwargs):
+    """The fused self-check of one product (fp8a_matmul_check): returns ``(C, G, CheckStats)`` with
+    C the approx sum, G the golden sum (v9:30-36, 145) and the error / normal-value statistics of
+    the reference's self_check_mode, reduced on the GPU -- no [M, K, N] tensor.  prod: a production
+    result (approx_matmul's) to compare C against (prod_max_abs / prod_max_rel).  Operands and
+    biases as approx_matmul.  Reads the struct back with one synchronising copy."""
+    if A.dim() != 2 or B.dim() != 2 or A.shape[1] != B.shape[0]:
+        raise AssertionError(f"approx_matmul_check: shape mismatch {tuple(A.shape)} @ {tuple(B.shape)}")  # v9:20
+    if flags is None:
+        flags = make_flags(**flag_kwargs)
+    L = _lib.load()
+    A, B = _as_f32(A), _as_f32(B)
+    if A.stride(1) != 1:
+        A = A.contiguous()
+    if B.stride(0) != 1 and B.stride(1) != 1:
+        B = B.contiguous()
+    dev = A.device
+    Mr, K = A.shape
+    N = B.shape[1]
+    tab = _table_host(table, M, _uses_table(flags))
+    bA_, bB_, bR_ = _bias_dev(bA, dev), _bias_dev(bB, dev), _bias_dev(bR, dev)
+    if bB_.numel() not in (1, N):
+        raise AssertionError(f"approx_matmul_check: {bB_.numel()} column biases for {N} columns")
+    C = torch.empty((Mr, N), dtype=torch.float32, device=dev)
+    G = torch.empty_like(C)
+    prod = _check_prod(prod, C)
+    stats = torch.empty(CHECK_STATS_BYTES, dtype=torch.uint8, device=dev)
+    ws = _aligned_workspace(dev, L.fp8a_check_workspace_size(Mr, N, K))
+    rc = L.fp8a_matmul_check(_lib.dev_ptr(A), A.stride(0), _lib.dev_ptr(B), B.stride(0), B.stride(1), _lib.dev_ptr(C),
+                             N, Mr, N, K, int(E), int(M), _lib.dev_ptr(bA_), _lib.dev_ptr(bB_),
+                             0 if bB_.numel() == 1 else 1, _lib.dev_ptr(bR_), _lib.host_ptr(tab), int(flags),
+                             _lib.dev_ptr(G), _lib.dev_ptr(prod), _lib.dev_ptr(stats), _lib.dev_ptr(ws), ws.numel(),
+                             _lib.stream_ptr(dev))
+    _lib.check(rc, "fp8a_matmul_check")
+    S = ws[:Mr * N * 4].view(torch.float32).view(Mr, N)
+    return C, G, CheckStats.from_bytes(stats.cpu().numpy().tobytes(), S=S)
+
+
+def approx_conv2d_check(x, w, E, M, bA, bW, bR, table=None, flags=None, stride=(1, 1), padding=(0, 0),
+                        dilation=(1, 1), groups=1, prod=None, **flag_kwargs):
+    """The fused self-check of one convolution (fp8a_conv2d_check): ``(y, G, CheckStats)`` in NCHW,
+    the statistics over all groups; single-output-channel groups take the tensor-bias semantics as
+    approx_conv2d.  prod: approx_conv2d's result (before any conv bias) to compare y against."""
+    if flags is None:
+        flags = make_flags(**flag_kwargs)
+    flags &= ~_lib.TB
+    L = _lib.load()
+    x, w = _as_f32(x).contiguous(), _as_f32(w).contiguous()
+    dev = x.device
+    tab = _table_host(table, M, _uses_table(flags))
+    bW_ = _bias_dev(bW, dev)
+    if bW_.numel() == 1:
+        bW_ = bW_.expand(w.shape[0]).contiguous()
+    if bW_.numel() != w.shape[0]:
+        raise AssertionError(f"approx_conv2d_check: {bW_.numel()} weight biases for {w.shape[0]} output channels")
+    bA_, bR_ = _bias_dev(bA, dev), _bias_dev(bR, dev)
+    Bn, Cin, H, W = x.shape
+    Cout, cig, kh, kw = w.shape
+    if groups <= 0 or Cin % groups or Cout % groups or cig != Cin // groups:
+        raise AssertionError(f"approx_conv2d_check: weight {tuple(w.shape)} does not fit {Cin} channels in {groups} groups")
+    (sh, sw), (ph, pw), (dh, dw) = [int(v) for v in stride], [int(v) for v in padding], [int(v) for v in dilation]
+    Ho = (H + 2 * ph - dh * (kh - 1) - 1) // sh + 1
+    Wo = (W + 2 * pw - dw * (kw - 1) - 1) // sw + 1
+    geo = (Bn, Cin, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, int(groups))
+    nbytes = L.fp8a_conv2d_check_workspace_size(*geo)
+    if nbytes == 0:
+        raise AssertionError("approx_conv2d_check: empty or inconsistent convolution geometry")
+    y = torch.empty((Bn, Cout, Ho, Wo), dtype=torch.float32, device=dev)
+    G = torch.empty_like(y)
+    prod = _check_prod(prod, y)
+    stats = torch.empty(CHECK_STATS_BYTES, dtype=torch.uint8, device=dev)
+    ws = _aligned_workspace(dev, nbytes)
+    rc = L.fp8a_conv2d_check(_lib.dev_ptr(x), _lib.dev_ptr(w), _lib.dev_ptr(y), *geo, int(E), int(M),
+                             _lib.dev_ptr(bA_), _lib.dev_ptr(bW_), _lib.dev_ptr(bR_), _lib.host_ptr(tab), int(flags),
+                             _lib.dev_ptr(G), _lib.dev_ptr(prod), _lib.dev_ptr(stats), _lib.dev_ptr(ws), ws.numel(),
+                             _lib.stream_ptr(dev))
+    _lib.check(rc, "fp8a_conv2d_check")
+    S = ws[:y.numel() * 4].view(torch.float32).view(y.shape)
+    return y, G, CheckStats.from_bytes(stats.cpu().numpy().tobytes(), S=S)
+
+
 def custom_matmul_vectorize(A, B, expo_width, mant_width, custom_bias_A, custom_bias_B, custom_bias_R,
                             error_table_NN, with_approx=True, with_s2nn2s_opt=False, sim_hw_add_OFUF=False,
                             with_OF_opt=False, with_UF_opt=False, golden_clip_OF=False, quant_btw_mult_accu=True,
@@ -283,15 +483,10 @@ def custom_matmul_vectorize(A, B, expo_width, mant_width, custom_bias_A, custom_
     flags = make_flags(with_approx, with_s2nn2s_opt, quant_btw_mult_accu, golden_clip_OF, tensor_bias=all(tb))
     out = approx_matmul(A, B, expo_width, mant_width, custom_bias_A, custom_bias_B, custom_bias_R,
                         error_table_NN, flags=flags)
-    if self_check_mode:
-        golden = quant_to_fp_any_vectorize_torch(A.unsqueeze(2) * B.unsqueeze(0), expo_width, mant_width,
-                                                 custom_bias_R, clip_OF=golden_clip_OF) \
-            if quant_btw_mult_accu else A.unsqueeze(2) * B.unsqueeze(0)
-        err = (golden.sum(dim=1) - out).abs()
-        print("\n====== Self-Checking Mode ======")
-        print(f"MatMul Max  Error     : {err.max()}")
-        print(f"MatMul Mean Error     : {err.mean()}")
-        print(f"MatMul RMSE           : {torch.sqrt(torch.mean(err ** 2))}")
+    if self_check_mode:  # v9:119-157 on the fused check kernel: no [M, K, N] tensor
+        _, _, stats = approx_matmul_check(A, B, expo_width, mant_width, custom_bias_A, custom_bias_B, custom_bias_R,
+                                          error_table_NN, flags=flags, prod=out)
+        print(format_self_check(stats, flags))
     return out
 
 

@@ -28,6 +28,7 @@
 #include "gemm_tt16.h"
 #include "gemm_dense.h"
 #include "conv_tbx.h"
+#include "gemm_check.h"
 
 // (defined with C linkage below; run_gemm launches it too)
 extern "C" __global__ void fq_bias_kernel(fp8a::FqIn fq, float *bias_out, int32_t *ibias_out);
@@ -1815,6 +1816,101 @@ int fp8a_terms(const float *A, int64_t lda, const float *B, int64_t sbk, int64_t
     if (total == 0) return FP8A_OK;
     terms_kernel<<<(unsigned)((total + 255) / 256), 256, 0, (hipStream_t)stream>>>(a, T);
     return hip_check("fp8a_terms");
+}
+
+// ------------------------------------------------------------------------- fused self-check
+// fp8a_matmul_check / fp8a_conv2d_check (gemm_check.h): workspace = the dense S image (one float per
+// output), then one CheckPart per workgroup (64 x 64 tile x group).
+static int64_t check_tiles(int64_t M, int64_t N) { return ((M + CK_BM - 1) / CK_BM) * ((N + CK_BN - 1) / CK_BN); }
+static size_t check_ws_bytes(int64_t outs, int64_t M, int64_t N, int64_t groups) {
+    return align256((size_t)outs * 4) + align256(check_part_bytes(check_tiles(M, N) * groups));
+}
+
+static int run_check(GemmArgs &a, CheckArgs &c, int64_t outs, const int32_t *table, void *ws, size_t ws_bytes,
+                     hipStream_t s) {
+    int rc = check_format(a.E, a.Mw);
+    if (rc) return rc;
+    if (a.flags & F_V5) return fail(FP8A_EINVAL, "the self-check covers the v9 model only (no FP8A_V5)");
+    if (a.M <= 0 || a.N <= 0 || a.K <= 0) return fail(FP8A_EINVAL, "self-check extents must be positive");
+    if ((!a.A && !a.conv) || (a.conv && !a.X) || !a.B || !a.C || !a.bA || !a.bB || !a.bR || !c.stats)
+        return fail(FP8A_EINVAL, "null pointer");
+    if (check_tiles(a.M, a.N) >= (1ll << 31) || c.groups > 65535)
+        return fail(FP8A_EINVAL, "self-check grid too large");
+    if (ws == nullptr || (((uintptr_t)ws) & 255) != 0 || ws_bytes < check_ws_bytes(outs, a.M, a.N, c.groups))
+        return fail(FP8A_EINVAL, "self-check workspace missing, misaligned or too small");
+    if ((((uintptr_t)c.stats) & 7) != 0) return fail(FP8A_EINVAL, "stats must be 8-byte aligned");
+    int mode;
+    rc = pack_table(table, a.Mw, (a.flags & F_APPROX) != 0, a.tab, mode);
+    if (rc) return rc;
+    // a diagnostic, not for graphs; a query that fails is an error of its own (never FP8A_OK)
+    const int cap = stream_capturing(s);
+    if (cap < 0) {
+        rc = hip_check("fp8a self-check: stream capture query");
+        return rc ? rc : fail(FP8A_EHIP, "fp8a self-check: the stream capture query failed");
+    }
+    if (cap) return fail(FP8A_EINVAL, "the self-check does not run on a capturing stream");
+    c.S = (float *)ws;
+    c.part = (CheckPart *)((char *)ws + align256((size_t)outs * 4));
+    c.tiles_n = (a.N + CK_BN - 1) / CK_BN;
+    launch_check(a, c, s);
+    return hip_check("fp8a self-check launch");
+}
+
+size_t fp8a_check_workspace_size(int64_t M, int64_t N, int64_t K) {
+    if (M <= 0 || N <= 0 || K <= 0) return 0;
+    return check_ws_bytes(M * N, M, N, 1);
+}
+
+int fp8a_matmul_check(const float *A, int64_t lda, const float *B, int64_t sbk, int64_t sbn, float *C, int64_t ldc,
+                      int64_t M, int64_t N, int64_t K, int E, int Mw, const int32_t *bA, const int32_t *bB,
+                      int64_t bB_stride, const int32_t *bR, const int32_t *table, uint32_t flags, float *G,
+                      const float *Cprod, fp8a_check_stats *stats, void *workspace, size_t workspace_bytes,
+                      fp8a_stream_t stream) {
+    if (lda < K || ldc < N) return fail(FP8A_EINVAL, "leading dimension smaller than extent");
+    GemmArgs a = make_args(A, lda, B, sbk, sbn, C, ldc, M, N, K, E, Mw, bA, bB, bB_stride, bR, flags);
+    CheckArgs c{};
+    c.G = G; c.Cprod = Cprod; c.stats = stats; c.groups = 1;
+    return run_check(a, c, M * N, table, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+size_t fp8a_conv2d_check_workspace_size(int64_t Bn, int64_t Cin, int64_t H, int64_t W, int64_t Cout, int kh, int kw,
+                                        int sh, int sw, int ph, int pw, int dh, int dw, int groups) {
+    if (groups <= 0 || Cout % groups != 0 || Cin % groups != 0 || sh <= 0 || sw <= 0) return 0;
+    const int64_t Ho = (H + 2 * ph - dh * (kh - 1) - 1) / sh + 1;
+    const int64_t Wo = (W + 2 * pw - dw * (kw - 1) - 1) / sw + 1;
+    if (Ho <= 0 || Wo <= 0 || Bn <= 0 || Cout <= 0 || Cin <= 0 || kh <= 0 || kw <= 0) return 0;
+    return check_ws_bytes(Bn * Cout * Ho * Wo, Bn * Ho * Wo, Cout / groups, groups);
+}
+
+int fp8a_conv2d_check(const float *x, const float *w, float *y, int64_t Bn, int64_t Cin, int64_t H, int64_t W,
+                      int64_t Cout, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw, int groups, int E,
+                      int Mw, const int32_t *bA, const int32_t *bW, const int32_t *bR, const int32_t *table,
+                      uint32_t flags, float *G, const float *Cprod, fp8a_check_stats *stats, void *workspace,
+                      size_t workspace_bytes, fp8a_stream_t stream) {
+    int rc = check_format(E, Mw);
+    if (rc) return rc;
+    if (groups <= 0 || Cout <= 0 || Cin <= 0 || Cout % groups != 0 || Cin % groups != 0)
+        return fail(FP8A_EINVAL, "bad groups");
+    if (kh <= 0 || kw <= 0 || sh <= 0 || sw <= 0 || dh <= 0 || dw <= 0 || ph < 0 || pw < 0 || Bn <= 0 || H <= 0 || W <= 0)
+        return fail(FP8A_EINVAL, "bad convolution geometry");
+    const int64_t Ho = (H + 2 * ph - dh * (kh - 1) - 1) / sh + 1;
+    const int64_t Wo = (W + 2 * pw - dw * (kw - 1) - 1) / sw + 1;
+    if (Ho <= 0 || Wo <= 0) return fail(FP8A_EINVAL, "empty convolution output");
+    const int64_t cog = Cout / groups, cig = Cin / groups, Kg = cig * kh * kw, Mrows = Bn * Ho * Wo;
+    // single-output-channel groups: the tensor-bias semantics, as fp8a_conv2d (approx_calculation.py:800-809)
+    const uint32_t fl = (flags & ~F_TB) | ((cog == 1 && !(flags & F_V5)) ? (uint32_t)F_TB : 0u);
+    GemmArgs a = make_args(nullptr, 0, w, 1, Kg, y, 0, Mrows, cog, Kg, E, Mw, bA, bW, 1, bR, fl);
+    a.nchw = 1;
+    a.hw = Ho * Wo;
+    a.ctot = Cout;
+    a.conv = 1;
+    a.X = x;
+    a.Cin = Cin; a.H = H; a.W = W; a.Ho = Ho; a.Wo = Wo;
+    a.kh = kh; a.kw = kw; a.sh = sh; a.sw = sw; a.ph = ph; a.pw = pw; a.dh = dh; a.dw = dw;
+    CheckArgs c{};
+    c.G = G; c.Cprod = Cprod; c.stats = stats; c.groups = groups;
+    c.b_gs = cog * Kg; c.bb_gs = cog; c.cig = cig; c.cog = cog;
+    return run_check(a, c, Bn * Cout * Ho * Wo, table, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 int fp8a_im2col(const float *x, float *out, int64_t Bn, int64_t Cin, int64_t H, int64_t W, int kh, int kw, int sh,

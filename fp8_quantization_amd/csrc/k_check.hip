@@ -1,0 +1,17 @@
+// k_check.hip -- the fused self-check kernels (gemm_check.h: gemm_check_kernel and the one-workgroup
+// stats reduction) in their own translation unit.  Launcher: fp8approx_launch.h.
+#define FP8A_OWN_CHECK 1
+#include "fp8approx_launch.h"
+#include "gemm_check.h"
+
+namespace fp8a {
+
+size_t check_part_bytes(int64_t parts) { return (size_t)parts * sizeof(CheckPart); }
+
+void launch_check(const GemmArgs &a, const CheckArgs &c, hipStream_t s) {
+    const int64_t tiles = ((a.M + CK_BM - 1) / CK_BM) * c.tiles_n;
+    gemm_check_kernel<<<dim3((unsigned)tiles, (unsigned)c.groups), CK_NT, 0, s>>>(a, c);
+    check_reduce_kernel<<<1, CK_NT, 0, s>>>(c, tiles * c.groups, a.M, a.N, a.K, a.flags);
+}
+
+}  // namespace fp8a

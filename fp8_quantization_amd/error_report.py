@@ -1,0 +1,153 @@
+"""Per-layer approx-vs-golden error report (the reference's self_check_mode at model level).
+
+``layer_error_report(model, x)`` switches custom_approx_params['self_check_mode'] on for every
+approx layer of a calibrated (fixed-range) model, runs one eager forward -- every layer then runs
+unfused and follows its production launch with the fused check kernel on the same quantized
+operands (approx_ops.approx_matmul_check / approx_conv2d_check) -- and returns one row per layer:
+the max / mean / RMSE of |golden - approx| (approx_matmul_whole_v9.py:145-157), the SQNR of the
+approx sum against the golden one, the shares of normal values in A, B and the product tensor, and
+the production kernel's distance from the literal check kernel in units of the project's 1e-5 S bar.
+
+    python -m fp8_quantization_amd.error_report --arch resnet18 --batch 16 [--size 224] [--json]
+
+builds the synthetic calibrated workload of the benchmark's workload modules (random weights, BN
+statistics estimated on synthetic batches, one calibration batch, fixed ranges) and prints the table.
+"""
+import argparse
+import contextlib
+import io
+import json
+import math
+
+import torch
+
+from .approx_calculation import ApproxConv2dMixin, ApproxOpMixin
+
+__all__ = ["layer_error_report", "format_report", "build_workload", "main"]
+
+BAR = 1e-5  # the project's tolerance: |C - oracle| <= 1e-5 * sum_k |v_k|
+
+
+def approx_layers(model):
+    """(name, module) of every approx operator with the approx product on, in module order."""
+    return [(n, m) for n, m in model.named_modules()
+            if isinstance(m, ApproxOpMixin) and getattr(m, "approx_flag", False)
+            and isinstance(getattr(m, "custom_approx_params", None), dict)]
+
+
+def _row(name, mod, st):
+    if isinstance(mod, ApproxConv2dMixin):
+        kind = "conv"
+        N = mod.out_channels // mod.groups
+        K = (mod.in_channels // mod.groups) * mod.kernel_size[0] * mod.kernel_size[1]
+        M = st.n_out // mod.out_channels
+        groups = mod.groups
+    else:
+        kind = "linear"
+        N, K, groups = mod.out_features, mod.in_features, 1
+        M = st.n_out // N
+    pct = lambda v: None if v is None else float(v)  # noqa: E731
+    return dict(name=name, kind=kind, shape=(int(M), int(N), int(K)), groups=int(groups), macs=int(st.n_out) * int(K),
+                max=float(st.max_err), mean=float(st.mean), rmse=float(st.rmse), sqnr_db=float(st.sqnr_db),
+                a_norm_pct=pct(st.a_norm_pct), b_norm_pct=pct(st.b_norm_pct), r_norm_pct=pct(st.r_norm_pct),
+                prod_max_rel=float(st.prod_max_rel) / BAR)
+
+
+def layer_error_report(model, x, quiet=True):
+    """One eager forward of ``model`` on ``x`` with the self-check on in every approx layer; returns
+    the rows (dicts: name, kind, shape (M, N, K), groups, macs, max, mean, rmse, sqnr_db,
+    a_norm_pct, b_norm_pct, r_norm_pct -- None with with_s2nn2s_opt --, prod_max_rel in units of
+    1e-5).  Every layer's self_check_mode is restored afterwards.  quiet: swallow the per-launch
+    blocks the layers print.  A diagnostic, not for HIP graphs: raises RuntimeError on a capturing
+    stream."""
+    if x.is_cuda and torch.cuda.is_current_stream_capturing():
+        raise RuntimeError("layer_error_report: the self-check does not run on a capturing stream")
+    layers = approx_layers(model)
+    saved = [(m, "self_check_mode" in m.custom_approx_params, m.custom_approx_params.get("self_check_mode"))
+             for _, m in layers]
+    try:
+        for _, m in layers:
+            m.custom_approx_params["self_check_mode"] = True
+            m.last_self_check = None
+        sink = io.StringIO()
+        with torch.no_grad(), (contextlib.redirect_stdout(sink) if quiet else contextlib.nullcontext()):
+            model(x)
+        return [_row(n, m, m.last_self_check) for n, m in layers if m.last_self_check is not None]
+    finally:
+        for m, had, old in saved:
+            if had:
+                m.custom_approx_params["self_check_mode"] = old
+            else:
+                m.custom_approx_params.pop("self_check_mode", None)
+
+
+def format_report(rows):
+    def f(v, spec):
+        return "-" if v is None else format(v, spec)
+    head = (f"{'layer':44s} {'kind':6s} {'M':>8s} {'N':>5s} {'K':>5s} {'MMACs':>9s} {'max':>10s} {'mean':>10s} "
+            f"{'rmse':>10s} {'SQNR dB':>8s} {'A%':>6s} {'B%':>6s} {'R%':>6s} {'prod/1e-5':>9s}")
+    out = [head, "-" * len(head)]
+    for r in rows:
+        M, N, K = r["shape"]
+        sq = "inf" if math.isinf(r["sqnr_db"]) else f"{r['sqnr_db']:.2f}"
+        out.append(f"{r['name'][-44:]:44s} {r['kind']:6s} {M:8d} {N:5d} {K:5d} {r['macs'] / 1e6:9.1f} {r['max']:10.4g} "
+                   f"{r['mean']:10.4g} {r['rmse']:10.4g} {sq:>8s} {f(r['a_norm_pct'], '6.1f'):>6s} "
+                   f"{f(r['b_norm_pct'], '6.1f'):>6s} {f(r['r_norm_pct'], '6.1f'):>6s} {r['prod_max_rel']:9.3g}")
+    return "\n".join(out)
+
+
+def build_workload(arch, size, cfg, bn_stats_batches=4, cal_batch=64, device="cuda"):
+    """The benchmark's synthetic calibrated workload: the arch's workload module (random weights, BN
+    statistics estimated on the CPU from synthetic batches), one synthetic calibration batch, fixed
+    ranges.  Returns the model on ``device`` in eval mode."""
+    from . import resnet_workload as rw
+    bn = dict(bn_stats_batches=bn_stats_batches, device=torch.device("cpu"))
+    if arch in ("resnet18", "resnet50"):
+        fp = rw.ResNet(rw.BasicBlock, (2, 2, 2, 2)) if arch == "resnet18" else rw.ResNet(rw.Bottleneck, (3, 4, 6, 3))
+        if bn_stats_batches:
+            rw.estimate_bn_statistics(fp, bn_stats_batches, input_shape=(3, size, size), device=torch.device("cpu"))
+        model = rw.QuantizedResNet(fp, input_size=(1, 3, size, size), **rw.approx_qparams(**cfg))
+    elif arch == "mobilenet_v2":
+        from .mobilenet_workload import mobilenet_v2_approx
+        model = mobilenet_v2_approx(input_size=size, **bn, **cfg)
+    elif arch == "vit_b16":
+        from .vit_workload import vit_b16_approx
+        model = vit_b16_approx(image_size=size, **cfg)
+    else:
+        raise ValueError(f"unknown arch {arch!r}")
+    model = model.to(device).eval()
+    g = torch.Generator(device="cpu").manual_seed(1234)
+    cal = torch.randn((cal_batch, 3, size, size), generator=g).to(device)
+    model.quantized()
+    model.estimate_ranges()
+    with torch.no_grad():
+        model(cal)
+    model.fix_ranges()
+    return model
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("--arch", default="resnet18", choices=("resnet18", "resnet50", "mobilenet_v2", "vit_b16"))
+    ap.add_argument("--batch", type=int, default=16)
+    ap.add_argument("--size", type=int, default=224, help="input height = width")
+    ap.add_argument("--json", action="store_true", help="print the rows as one JSON list")
+    ap.add_argument("--expo-width", type=int, default=4)
+    ap.add_argument("--mant-width", type=int, default=3)
+    ap.add_argument("--with-comp", action="store_true", help="withComp=True (E4M3: the all-zero table)")
+    ap.add_argument("--no-s2n", action="store_true", help="with_s2nn2s_opt off (adds the R_3d share)")
+    ap.add_argument("--cal-batch", type=int, default=64)
+    ap.add_argument("--bn-stats-batches", type=int, default=4)
+    args = ap.parse_args(argv)
+    cfg = dict(expo_width=args.expo_width, mant_width=args.mant_width, dnsmp_factor=3, withComp=args.with_comp,
+               with_approx=True, with_s2nn2s_opt=not args.no_s2n, quant_btw_mult_accu=True)
+    model = build_workload(args.arch, args.size, cfg, args.bn_stats_batches, args.cal_batch)
+    g = torch.Generator(device="cpu").manual_seed(10)
+    x = torch.randn((args.batch, 3, args.size, args.size), generator=g).to("cuda")
+    rows = layer_error_report(model, x)
+    print(json.dumps(rows) if args.json else format_report(rows))
+    return rows
+
+
+if __name__ == "__main__":
+    main()

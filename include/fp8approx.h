@@ -251,6 +251,71 @@ int fp8a_terms(const float *A, int64_t lda, const float *B, int64_t sbk, int64_t
                uint32_t flags, fp8a_stream_t stream);
 
 /*
+ * Fused self-check: the reference's self_check_mode (approx_matmul_whole_v9.py:119-157) without its
+ * [M, K, N] tensors.  One literal kernel (gemm_check.h; none of the production GEMM paths) makes one
+ * pass over K and sums, per output and in the same k order, three fp32 values:
+ *   C = sum_k v_k  the approx term (what fp8a_terms returns), every v9 flag set (V5: FP8A_EINVAL);
+ *   G = sum_k g_k  the golden term fl32(a b), through Q_R (bR, golden_clip_OF) when FP8A_QBMA
+ *                  (v9:30-36) -- from this definition, for any fp32 operand, on its grid or not;
+ *   S = sum_k |v_k|  the tolerance scale of the project's 1e-5 S bar.
+ * and fills *stats (DEVICE memory) by a deterministic reduction: per-workgroup parts in the
+ * workspace, summed by one workgroup in a fixed order, no floating-point atomics -- two calls give
+ * identical bytes.  All fields are over the whole call (a convolution: all its groups).
+ *
+ * Layout (96 bytes, natural alignment, no padding):
+ *   offset  0  n_out         outputs, M N (times groups)
+ *           8  sum_err       sum of (double) e, e = fabsf(G - C) computed in fp32 (v9:146)
+ *          16  sum_err2      sum of (double) e * (double) e
+ *          24  sum_gold2     sum of (double) G * (double) G (for an SQNR)
+ *          32  a_norm        elements of the [M, K] operand with |a| >= min_norm(bA) (v9:47, 133-136);
+ *          40  a_total         a convolution's operand is its im2col matrix, per group; FP8A_TB
+ *                              launches use the tensor-bias min_norm (quirk F5)
+ *          48  b_norm        the same for [K, N], every column with its own bB
+ *          56  b_total
+ *          64  r_norm        terms with expo_a > 0, expo_b > 0 and |g| >= min_norm(bR) (v9:87, 124-126);
+ *          72  r_total         both 0 with FP8A_S2N (the reference has no such mask there)
+ *          80  max_err       max e
+ *          84  prod_max_abs  with Cprod: max |Cprod - C|                       (else 0)
+ *          88  prod_max_rel  with Cprod: max |Cprod - C| / max(S, FLT_MIN)     (else 0)
+ *          92  has_prod      1 when Cprod was given
+ */
+typedef struct fp8a_check_stats {
+    uint64_t n_out;
+    double sum_err, sum_err2, sum_gold2;
+    uint64_t a_norm, a_total, b_norm, b_total, r_norm, r_total;
+    float max_err, prod_max_abs, prod_max_rel;
+    uint32_t has_prod;
+} fp8a_check_stats;
+
+/*
+ * fp8a_matmul_check: fp8a_matmul's operands and C, plus G (NULL, or C's layout), Cprod (NULL, or a
+ * production result in C's layout to compare C against) and stats.  workspace: at least
+ * fp8a_check_workspace_size(M, N, K) bytes, 256-byte aligned; its first M N floats receive S
+ * (dense, row-major [M][N]).  fp8a_conv2d_check: fp8a_conv2d's operands and NCHW y, G / Cprod in
+ * y's layout, S in y's layout at the head of a workspace of fp8a_conv2d_check_workspace_size bytes;
+ * grouped convolutions run as one launch, single-output-channel groups with the tensor-bias
+ * semantics, as fp8a_conv2d.  Both are asynchronous, allocate nothing and never synchronise the
+ * host.  A diagnostic, not for HIP graphs: on a capturing stream they return FP8A_EINVAL before
+ * launching anything (a failed capture query is an error too).  The size queries are host-only
+ * (0 for bad arguments).
+ */
+size_t fp8a_check_workspace_size(int64_t M, int64_t N, int64_t K);
+int fp8a_matmul_check(const float *A, int64_t lda, const float *B, int64_t sbk, int64_t sbn, float *C,
+                      int64_t ldc, int64_t M, int64_t N, int64_t K, int E, int Mw, const int32_t *bA,
+                      const int32_t *bB, int64_t bB_stride, const int32_t *bR, const int32_t *table,
+                      uint32_t flags, float *G, const float *Cprod, fp8a_check_stats *stats,
+                      void *workspace, size_t workspace_bytes, fp8a_stream_t stream);
+size_t fp8a_conv2d_check_workspace_size(int64_t Bn, int64_t Cin, int64_t H, int64_t W, int64_t Cout,
+                                        int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw,
+                                        int groups);
+int fp8a_conv2d_check(const float *x, const float *w, float *y, int64_t Bn, int64_t Cin, int64_t H,
+                      int64_t W, int64_t Cout, int kh, int kw, int sh, int sw, int ph, int pw, int dh,
+                      int dw, int groups, int E, int Mw, const int32_t *bA, const int32_t *bW,
+                      const int32_t *bR, const int32_t *table, uint32_t flags, float *G,
+                      const float *Cprod, fp8a_check_stats *stats, void *workspace,
+                      size_t workspace_bytes, fp8a_stream_t stream);
+
+/*
  * Replaces QCustomBNConv2dTorch.run_forward (approx_calculation.py:822-917) minus the conv
  * bias: x NCHW [Bn, Cin, H, W], w [Cout, Cin/groups, kh, kw], y NCHW [Bn, Cout, Ho, Wo].
  * bW: device int32 per output channel (weight_quantizer.custom_bias).  Groups whose output
