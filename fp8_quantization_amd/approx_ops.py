@@ -25,7 +25,7 @@ __all__ = ["custom_matmul_vectorize", "approx_matmul", "approx_matmul_block", "a
            "quant_to_fp_any_vectorize_torch", "float_to_fpany_absint_torch", "get_error_table_NN",
            "make_flags", "make_flags_v5", "fp8_fake_quantize", "bn_act_epilogue", "dense_format", "dense_matmul",
            "dense_conv2d", "grouped_conv2d", "dense_conv2d_fused", "approx_matmul_check", "approx_conv2d_check",
-           "CheckStats", "format_self_check", "SELF_CHECK_LABELS"]
+           "CheckStats", "format_self_check", "SELF_CHECK_LABELS", "fp8_mse_losses"]
 
 
 def make_flags(with_approx=True, with_s2nn2s_opt=False, quant_btw_mult_accu=True, golden_clip_OF=False,
@@ -871,6 +871,32 @@ def fp8_fake_quantize(x, maxval, n_bits, mantissa_bits, sign_bits=1, per_row=Fal
     # the same bias as int32, written by the same kernel: the approx ops take it as is (_bias_dev)
     bias._fp8a_i32 = ibias
     return out, bias
+
+
+def fp8_mse_losses(x, grid, mbit_list, n_bits, sign_bits, per_channel):
+    """The FP8 MSE range search's losses in one pass over x (fp8a_fp8_mse_search, csrc/fq_mse.h):
+
+        sse[m][i][r] = sum over row r of (x - fp8_fake_quantize(x, grid[i][r], mbit_list[m]))^2
+
+    x viewed as [rows][inner], rows = x.shape[0] if per_channel else 1; grid float32 [n_cand][rows].
+    Returns a float64 [n_mbits][n_cand][rows] device tensor (a candidate with maxval 0: NaN)."""
+    L = _lib.load()
+    if not x.is_cuda:
+        raise RuntimeError("fp8approx kernels need HIP device tensors (no CPU fallback)")
+    x = _as_f32(x).contiguous()
+    rows = x.shape[0] if per_channel else 1
+    inner = x.numel() // max(rows, 1)
+    grid = _as_f32(grid).to(x.device).reshape(-1, rows).contiguous()
+    n_cand = grid.shape[0]
+    mb = (ctypes.c_int32 * len(mbit_list))(*[int(m) for m in mbit_list])
+    sse = torch.empty((len(mbit_list), n_cand, rows), dtype=torch.float64, device=x.device)
+    nbytes = int(L.fp8a_fp8_mse_workspace_size(rows, inner, n_cand, len(mbit_list)))
+    ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=x.device)
+    rc = L.fp8a_fp8_mse_search(_lib.dev_ptr(x), rows, inner, _lib.dev_ptr(grid), n_cand,
+                               ctypes.cast(mb, ctypes.c_void_p), len(mbit_list), int(n_bits), int(sign_bits),
+                               _lib.dev_ptr(sse), _lib.dev_ptr(ws), nbytes, _lib.stream_ptr(x.device))
+    _lib.check(rc, "fp8a_fp8_mse_search")
+    return sse
 
 
 # ----------------------------------------------------------------------------------- qamaa

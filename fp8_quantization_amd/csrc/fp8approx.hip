@@ -29,6 +29,7 @@
 #include "gemm_dense.h"
 #include "conv_tbx.h"
 #include "gemm_check.h"
+#include "fq_mse.h"
 
 // (defined with C linkage below; run_gemm launches it too)
 extern "C" __global__ void fq_bias_kernel(fp8a::FqIn fq, float *bias_out, int32_t *ibias_out);
@@ -1524,6 +1525,10 @@ int fp8a_kernel_time(double *out, int reset) {
     return FP8A_OK;
 }
 
+// "mse_group": fp8a_fp8_mse_search runs the grouped form of the search kernel (fq_mse.h; same bytes,
+// 2.0-2.6 x faster on the DESIGN.md 3u tensors)
+static int g_opt_mse_group = getenv("FP8A_MSE_GROUP") ? atoi(getenv("FP8A_MSE_GROUP")) != 0 : 1;
+
 int fp8a_set_option(const char *name, int value) {
     if (name == nullptr) return fail(FP8A_EINVAL, "null pointer");
     if (strcmp(name, "xm_ncg") == 0) {
@@ -1584,6 +1589,11 @@ int fp8a_set_option(const char *name, int value) {
     if (strcmp(name, "dw3") == 0) {
         const int old = g_opt_dw3;
         g_opt_dw3 = value;
+        return old;
+    }
+    if (strcmp(name, "mse_group") == 0) {
+        const int old = g_opt_mse_group;
+        g_opt_mse_group = value != 0;
         return old;
     }
     return fail(FP8A_EINVAL, std::string("unknown option ") + name);
@@ -2669,6 +2679,46 @@ int fp8a_fp8_quantize(const float *x, int64_t rows, int64_t inner, const float *
     fp8_quantize_kernel<<<(unsigned)blocks, 256, 0, (hipStream_t)stream>>>(x, rows, inner, maxval, per_row, E,
                                                                            Mbits, sign_bits, out, bias_out, ibias_out);
     return hip_check("fp8a_fp8_quantize");
+}
+
+// FP8 MSE range search (fq_mse.h).  Workspace: the candidates' MseCand [rows][n_mbits * n_cand], then the
+// workgroups' parts, doubles [rows][parts][n_mbits * n_cand].
+static bool mse_shape_ok(int64_t rows, int64_t inner, int n_cand, int n_mbits) {
+    return rows > 0 && inner > 0 && n_cand > 0 && n_mbits >= 1 && n_mbits <= MSE_MAX_MBITS &&
+           (int64_t)n_cand * n_mbits <= MSE_MAX_CANDS && rows <= (int64_t)1 << 24 &&
+           inner <= ((int64_t)1 << 62) / rows;
+}
+
+size_t fp8a_fp8_mse_workspace_size(int64_t rows, int64_t inner, int n_cand, int n_mbits) {
+    if (!mse_shape_ok(rows, inner, n_cand, n_mbits)) return 0;
+    const size_t nc = (size_t)n_cand * n_mbits;
+    return (size_t)rows * nc * sizeof(MseCand) + (size_t)rows * (size_t)mse_parts(rows, inner) * nc * sizeof(double);
+}
+
+int fp8a_fp8_mse_search(const float *x, int64_t rows, int64_t inner, const float *grid, int n_cand,
+                        const int32_t *mbits, int n_mbits, int n_bits, int sign_bits, double *sse, void *workspace,
+                        size_t workspace_bytes, fp8a_stream_t stream) {
+    if (!mse_shape_ok(rows, inner, n_cand, n_mbits)) return fail(FP8A_EINVAL, "bad MSE search shape");
+    if (sign_bits < 0 || sign_bits > 1 || n_bits - sign_bits < 1 || n_bits > 16)
+        return fail(FP8A_EINVAL, "bad FP8 quantizer format");
+    if (mbits == nullptr) return fail(FP8A_EINVAL, "null pointer");
+    MseArgs a{};
+    for (int m = 0; m < n_mbits; ++m) {
+        if (mbits[m] < 1 || mbits[m] > n_bits - sign_bits) return fail(FP8A_EINVAL, "mantissa width outside [1, n_bits - sign_bits]");
+        a.mbits[m] = mbits[m];
+    }
+    if (workspace_bytes < fp8a_fp8_mse_workspace_size(rows, inner, n_cand, n_mbits))
+        return fail(FP8A_EINVAL, "workspace too small");
+    if (x == nullptr || grid == nullptr || sse == nullptr || workspace == nullptr || ((uintptr_t)workspace & 15) != 0)
+        return fail(FP8A_EINVAL, "null or misaligned pointer");
+    a.x = x; a.rows = rows; a.inner = inner; a.grid = grid;
+    a.n_cand = n_cand; a.n_mbits = n_mbits; a.n_bits = n_bits; a.sign_bits = sign_bits;
+    a.parts = mse_parts(rows, inner);
+    a.cand = static_cast<MseCand *>(workspace);
+    a.part = reinterpret_cast<double *>(a.cand + (size_t)rows * n_cand * n_mbits);
+    a.sse = sse;
+    launch_mse(a, g_opt_mse_group != 0, (hipStream_t)stream);
+    return hip_check("fp8a_fp8_mse_search");
 }
 
 // The config-1 layer (approx_flag off) in one launch family: fq_in on the loaded input, the exact

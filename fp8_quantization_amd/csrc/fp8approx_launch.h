@@ -46,4 +46,9 @@ struct CheckArgs;
 void launch_check(const GemmArgs &a, const CheckArgs &c, hipStream_t s);
 size_t check_part_bytes(int64_t parts);
 
+// k_mse.hip: the FP8 MSE candidate search (fq_mse.h) -- the candidate pre-kernel, the search kernel
+// (group: the grouped form, option "mse_group") and the ordered reduction of the workgroups' parts.
+struct MseArgs;
+void launch_mse(const MseArgs &a, bool group, hipStream_t s);
+
 }  // namespace fp8a

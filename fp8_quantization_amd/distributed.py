@@ -63,13 +63,14 @@ def broadcast_model_state(model, src=0):
                 off += n
 
 
-_HDR = 16  # per quantizer: maxval numel, sign_bits, ndim, 5 dims; custom_bias numel (-1: None), ndim, 5 dims
+# per quantizer: maxval numel, sign_bits, ndim, 5 dims; custom_bias numel (-1: None), ndim, 5 dims; mantissa width
+_HDR = 16
 
 
 def broadcast_quant_state(model, src=0):
     """Make every rank's FP8 ranges identical to rank `src`'s with two broadcasts in all: one
     int64 header [quantizers, 16] (maxval element count, sign_bits and shape; custom_bias element
-    count and shape) and one float32 buffer of every quantizer's maxval and custom_bias.  Ranks that
+    count and shape; the mantissa width, which the MSE range estimator's vote may have moved) and one float32 buffer of every quantizer's maxval and custom_bias.  Ranks that
     never calibrated receive the calibrated (e.g. per-channel) shapes.
 
     custom_bias travels too: an activation / weight quantizer rewrites it on every forward, but the
@@ -99,6 +100,7 @@ def broadcast_quant_state(model, src=0):
             hdr[i, :3 + len(shp)] = torch.tensor([q.maxval.numel(), int(q.sign_bits), len(shp)] + shp)
             hdr[i, 8:10 + len(cshp)] = torch.tensor([cb.numel() if isinstance(cb, torch.Tensor) else -1, len(cshp)]
                                                     + cshp)
+            hdr[i, 15] = int(q._mbits_int)
     hdr = hdr.to(dev)
     dist.broadcast(hdr, src)
     hdr = hdr.cpu()
@@ -121,6 +123,8 @@ def broadcast_quant_state(model, src=0):
         n, sb, nd = h[0], h[1], h[2]
         q.maxval = flat[off:off + n].clone().view(h[3:3 + nd])
         q.sign_bits = sb
+        if rank != src and h[15] != q._mbits_int:
+            q.mantissa_bits = torch.tensor(float(h[15]), device=q.mantissa_bits.device)
         off += n
         cn, cnd = h[8], h[9]
         if cn >= 0:

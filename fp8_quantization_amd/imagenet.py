@@ -159,6 +159,11 @@ def parse(argv=None):
     ap.add_argument("--no-approx", action="store_true", help="approx_flag off (quantized, exact products)")
     ap.add_argument("--no-s2n", action="store_true")
     ap.add_argument("--no-qbma", action="store_true")
+    methods = ["current_minmax", "allminmax", "running_minmax", "MSE"]  # RangeEstimators (click_options.py:544-577)
+    ap.add_argument("--weight-quant-method", default="current_minmax", choices=methods)
+    ap.add_argument("--act-quant-method", default="allminmax", choices=methods)
+    ap.add_argument("--fp8-mse-include-mantissa-bits", action="store_true",
+                    help="the MSE estimator also votes on the mantissa width")
     ap.add_argument("--output", default=None, help="also write the result JSON here")
     return ap.parse_args(argv)
 
@@ -236,7 +241,9 @@ def datasets(args):
 def approx_cfg(args):
     cfg = dict(expo_width=args.expo_width, mant_width=args.mant_width, dnsmp_factor=args.dnsmp_factor,
                withComp=args.with_comp, with_approx=True, with_s2nn2s_opt=not args.no_s2n,
-               quant_btw_mult_accu=not args.no_qbma)
+               quant_btw_mult_accu=not args.no_qbma, weight_range_method=args.weight_quant_method,
+               act_range_method=args.act_quant_method,
+               mse_include_mantissa_bits=args.fp8_mse_include_mantissa_bits)
     if args.no_approx:
         # the reference's canonical no-approx run (scripts/image_net.sh:42-45): exact product, then
         # the res quantizer through the original_quantize_res branch

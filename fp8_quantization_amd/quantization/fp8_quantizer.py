@@ -3,7 +3,9 @@
 quantize_to_fp8_ste_MM keeps its signature and return value (values, float bias); the
 per-element arithmetic is the HIP kernel fp8a_fp8_quantize.  FPQuantizer keeps the
 reference's attribute surface: n_bits, mantissa_bits (tensor), maxval (tensor), sign_bits,
-custom_bias (set by every forward), set_quant_range / fix_ranges.
+custom_bias (set by every forward), set_quant_range / fix_ranges.  mantissa_bits is assignable (the
+MSE range estimator stores its winning width there, range_estimators.FP_MSE_Estimator): the integer
+width forward hands to the kernels follows the assignment.
 """
 import torch
 from torch import nn
@@ -35,7 +37,6 @@ class FPQuantizer(nn.Module):
         default_maxval = (2 - 2 ** (-mantissa_bits)) * 2 ** (2 ** self.ebits - 1 - self.default_bias)
         self.maxval = torch.Tensor([maxval if maxval is not None else default_maxval])
         self.mantissa_bits = torch.Tensor([float(mantissa_bits)])
-        self._mbits_int = int(mantissa_bits)
         self.set_maxval = set_maxval
         self.learning_maxval = learn_maxval
         self.learning_mantissa_bits = learn_mantissa_bits
@@ -43,6 +44,24 @@ class FPQuantizer(nn.Module):
         self.allow_unsigned = allow_unsigned
         self.sign_bits = 1
         self.custom_bias = None
+
+    @property
+    def mantissa_bits(self):
+        return self._mantissa_bits
+
+    @mantissa_bits.setter
+    def mantissa_bits(self, value):
+        # the reference keeps a float tensor and rounds it in every forward (round_ste_func,
+        # fp8_quantizer.py:111); the kernels take an integer width, read once per assignment
+        if not isinstance(value, torch.Tensor):
+            value = torch.Tensor([float(value)])
+        self._mantissa_bits = value
+        self._mbits_int = int(round(float(value.detach().reshape(-1)[0])))
+
+    def _make_unsigned(self, x_min):
+        if isinstance(x_min, torch.Tensor):
+            return self.allow_unsigned and bool(torch.all(x_min >= 0))
+        return self.allow_unsigned and x_min >= 0
 
     @property
     def is_initialized(self):
@@ -58,7 +77,7 @@ class FPQuantizer(nn.Module):
         return res
 
     def set_quant_range(self, x_min, x_max):
-        if self.allow_unsigned and bool(torch.all(torch.as_tensor(x_min) >= 0)):
+        if self._make_unsigned(x_min):
             self.sign_bits = 0
         if self.set_maxval:
             if not isinstance(x_max, torch.Tensor):

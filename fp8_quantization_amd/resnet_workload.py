@@ -23,22 +23,32 @@ from .quantization.base_quantized_classes import FP32Acts, QuantizedActivation
 def approx_qparams(expo_width=4, mant_width=3, dnsmp_factor=3, withComp=False, with_approx=True,
                    with_s2nn2s_opt=True, quant_btw_mult_accu=True, golden_clip_OF=False, n_bits=8, run_method=None,
                    zero_table_ext=None, approx_version=9, sim_hw_add_OFUF=False, with_OF_opt=False,
-                   with_UF_opt=False):
+                   with_UF_opt=False, weight_range_method="current_minmax", weight_range_options=None,
+                   act_range_method="allminmax", act_range_options=None, mse_include_mantissa_bits=False):
     """qparams exactly as the reference scripts build them (utils/click_options.py:544-606,
     scripts/generated_scripts.py): per-channel current_minmax weights, allminmax activations,
     quantize_input, FP8 quantizer with set_maxval, approx + res_quantizer run method.
 
     Extensions (not in the reference): zero_table_ext (None = on exactly for formats the
     reference has no error table for, E5M2: error_tables.get_error_table_NN) and approx_version 5
-    (the v5 integer-adder model with live sim_hw_add_OFUF / with_OF_opt / with_UF_opt)."""
+    (the v5 integer-adder model with live sim_hw_add_OFUF / with_OF_opt / with_UF_opt).
+
+    weight_range_method / act_range_method: a RangeEstimators name (current_minmax, allminmax,
+    running_minmax, MSE: the reference's --weight-quant-method / --act-quant-method) or an estimator
+    class, with their options; mse_include_mantissa_bits lets the MSE estimator vote on the
+    mantissa width too (--fp8-mse-include-mantissa-bits)."""
+    def estimator(m):
+        return getattr(RangeEstimators, m).cls if isinstance(m, str) else m
     if zero_table_ext is None:
         zero_table_ext = (expo_width, mant_width) not in ((4, 3), (3, 4), (2, 5))
     return dict(
         method=FPQuantizer, act_method=FPQuantizer, n_bits=n_bits, n_bits_act=n_bits, per_channel_weights=True,
-        weight_range_method=RangeEstimators.current_minmax.cls, weight_range_options={},
-        act_range_method=RangeEstimators.allminmax.cls, act_range_options={}, quantize_input=True,
+        weight_range_method=estimator(weight_range_method), weight_range_options=dict(weight_range_options or {}),
+        act_range_method=estimator(act_range_method), act_range_options=dict(act_range_options or {}),
+        quantize_input=True,
         fp8_kwargs=dict(maxval=None, mantissa_bits=mant_width, set_maxval=True, learn_maxval=False,
-                        learn_mantissa_bits=False, mse_include_mantissa_bits=False, allow_unsigned=False),
+                        learn_mantissa_bits=False, mse_include_mantissa_bits=bool(mse_include_mantissa_bits),
+                        allow_unsigned=False),
         custom_approx_params=dict(expo_width=expo_width, mant_width=mant_width, dnsmp_factor=dnsmp_factor,
                                   withComp=withComp, with_approx=with_approx, with_s2nn2s_opt=with_s2nn2s_opt,
                                   sim_hw_add_OFUF=sim_hw_add_OFUF, with_OF_opt=with_OF_opt, with_UF_opt=with_UF_opt,

@@ -129,7 +129,10 @@ int fp8a_kernel_time(double *out, int reset);
  * conv / matrix A is decoded inside gemm_f8mx_kernel instead of by its pre-pass (0 = never);
  * "tt16_mink" (default 64; FP8A_TT16_MINK) -- the smallest K of an E3M4 launch (unsigned error
  * table) on the packed-f16 tile-table kernel (shorter K: the f32 form); "tt_band" (default 1;
- * FP8A_TT_BAND) -- gemm_tt_kernel's band / zero wave-tile forms (0 = the general form everywhere).
+ * FP8A_TT_BAND) -- gemm_tt_kernel's band / zero wave-tile forms (0 = the general form everywhere);
+ * "mse_group" (default 1; FP8A_MSE_GROUP) -- fp8a_fp8_mse_search evaluates candidates that share a
+ * bias together: the unclamped quantizer once per run, the clamp per candidate (0: every candidate
+ * through the whole quantizer).
  * All of these change the schedule only: the outputs are bit-identical.  Returns the previous value, or FP8A_EINVAL
  * for an unknown name.  Not synchronised with launches in flight on other threads.
  */
@@ -535,6 +538,24 @@ int fp8a_im2col(const float *x, float *out, int64_t Bn, int64_t Cin, int64_t H, 
 int fp8a_fp8_quantize(const float *x, int64_t rows, int64_t inner, const float *maxval,
                       int per_row, int n_bits, int Mbits, int sign_bits, float *out,
                       float *bias_out, int32_t *ibias_out, fp8a_stream_t stream);
+
+/*
+ * Candidate search of the FP8 MSE range estimator (FP_MSE_Estimator, range_estimators.py:285-369):
+ * for x viewed as [rows, inner] (rows = channels per channel, else 1), candidate maxvals grid
+ * (device float [n_cand][rows]) and mantissa widths mbits (HOST int32 [n_mbits], 1 <= n_mbits <= 7,
+ * each in [1, n_bits - sign_bits]; n_mbits * n_cand <= 1024),
+ *   sse[m][i][r] = sum over inner of (x - fq(x; maxval = grid[i][r], Mbits = mbits[m]))^2
+ * with fq = fp8a_fp8_quantize's arithmetic bit for bit and the difference and the square single
+ * fp32 operations; summed deterministically (fp32 over at most 16 terms, then double; two calls
+ * return identical bytes).  A candidate with maxval = 0 (non-finite bias) gives NaN.  One pass over
+ * x for all candidates.  fp8a_fp8_mse_workspace_size is host-only and returns 0 for bad arguments;
+ * the workspace must be 16-byte aligned.  FP8A_EINVAL before any launch for bad shapes, widths,
+ * pointers or a workspace that is too small.
+ */
+size_t fp8a_fp8_mse_workspace_size(int64_t rows, int64_t inner, int n_cand, int n_mbits);
+int fp8a_fp8_mse_search(const float *x, int64_t rows, int64_t inner, const float *grid, int n_cand,
+                        const int32_t *mbits, int n_mbits, int n_bits, int sign_bits, double *sse,
+                        void *workspace, size_t workspace_bytes, fp8a_stream_t stream);
 
 #ifdef __cplusplus
 }
