@@ -27,7 +27,7 @@ SYMBOLS = ("fp8a_version", "fp8a_last_error", "fp8a_fallback_stats", "fp8a_path_
            "fp8a_word_image_bytes", "fp8a_word_image_init", "fp8a_conv2d_chain", "fp8a_conv2d_wants_image",
            "fp8a_flag_arena_slot_bytes",
            "fp8a_check_workspace_size", "fp8a_matmul_check", "fp8a_conv2d_check_workspace_size", "fp8a_conv2d_check",
-           "fp8a_fp8_mse_workspace_size", "fp8a_fp8_mse_search")
+           "fp8a_fp8_mse_workspace_size", "fp8a_fp8_mse_search", "fp8a_fq_selfcheck")
 
 _lib = None
 
@@ -109,6 +109,7 @@ def load():
                                P, P, SZ, P], I),
         "fp8a_fp8_mse_workspace_size": ([I64, I64, I, I], SZ),
         "fp8a_fp8_mse_search": ([P, I64, I64, P, I, P, I, I, I, P, P, SZ, P], I),
+        "fp8a_fq_selfcheck": ([F, I, I, I, I, I, ctypes.c_uint64, ctypes.c_uint64, P, P], I),
     }
     for name, (args, res) in sig.items():
         f = getattr(L, name)
@@ -208,6 +209,18 @@ def set_option(name, value):
         check(rc, "fp8a_set_option")
     _option_gen += 1
     return rc
+
+
+def fq_selfcheck(maxval, E, M, sign_bits, mode=0, bR=0, first=0, count=1 << 32, device=None):
+    """fp8a_fq_selfcheck: the "fq_fast" forms against the literal ones over the fp32 bit patterns
+    first .. first + count - 1; dict(mismatches, first_bad (None: none), fast, per_element)."""
+    out = (ctypes.c_uint64 * 3)()
+    check(load().fp8a_fq_selfcheck(float(maxval), int(E), int(M), int(sign_bits), int(mode), int(bR), int(first),
+                                   int(count), ctypes.cast(out, ctypes.c_void_p), stream_ptr(device)),
+          "fp8a_fq_selfcheck")
+    bad = int(out[1])
+    return dict(mismatches=int(out[0]), first_bad=None if bad == 2 ** 64 - 1 else bad, fast=bool(out[2] & 1),
+                per_element=bool(out[2] & 2))
 
 
 def dense_stats(reset=False):

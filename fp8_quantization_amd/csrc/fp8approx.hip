@@ -97,70 +97,18 @@ __device__ unsigned long long g_fallback[4];
 // Sums the split-K partials in split order (deterministic) and writes the output mapping.
 // Partial layout: row-major [M][N] (rowmajor output) or [img][N][hw] (NCHW output).
 __global__ __launch_bounds__(256) void splitk_reduce_kernel(const GemmArgs p) {
+    // (the fast forms where the launch's one test allows: sc.fqf, StoreCtx; the per-value work is
+    // splitk_finish4 / splitk_finish1, fp8approx_common.h, shared with the in-launch sum)
+    const StoreCtx sc = store_ctx<true>(p);
     const int64_t MN = p.M * p.N;
-    const float pb = post_bias(p);
-    const EmitCtx ec = emit_ctx(p);
     uint32_t sehi = 0, neg = 0;
-    const int S = p.splits;
-    const bool vec = p.nchw ? ((p.hw & 3) == 0) : ((p.N & 3) == 0 && (p.ldc & 3) == 0);
-    const bool aligned = ((((uintptr_t)p.C) & 15) == 0) && ((((uintptr_t)p.part) & 15) == 0) && ((MN & 3) == 0) &&
-                         ((((uintptr_t)p.res) & 15) == 0);
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    if (vec && aligned) {
-        for (int64_t q4 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q4 < MN / 4; q4 += stride) {
-            const int64_t q = q4 * 4;
-            float4 acc = *reinterpret_cast<const float4 *>(p.part + q);
-            for (int sp = 1; sp < S; ++sp) {
-                const float4 v = *reinterpret_cast<const float4 *>(p.part + sp * MN + q);
-                acc.x += v.x; acc.y += v.y; acc.z += v.z; acc.w += v.w;
-            }
-            int64_t o;
-            if (p.nchw) {
-                const int64_t img = q / (p.N * p.hw), rem = q - img * p.N * p.hw, n = rem / p.hw, pix = rem - n * p.hw;
-                o = (img * p.ctot + p.coff + n) * p.hw + pix;
-                if (p.ep) {  // the 4 values share channel coff + n (hw % 4 == 0)
-                    const int64_t ch = p.coff + n;
-                    acc.x = epi(p.ep, p.ep_act, p.ep_lo, p.ep_hi, ch, acc.x);
-                    acc.y = epi(p.ep, p.ep_act, p.ep_lo, p.ep_hi, ch, acc.y);
-                    acc.z = epi(p.ep, p.ep_act, p.ep_lo, p.ep_hi, ch, acc.z);
-                    acc.w = epi(p.ep, p.ep_act, p.ep_lo, p.ep_hi, ch, acc.w);
-                }
-            } else {
-                const int64_t m = q / p.N, n = q - m * p.N;
-                o = m * p.ldc + n;
-                if (p.ep) {
-                    acc.x = epi(p.ep, p.ep_act, p.ep_lo, p.ep_hi, p.coff + n, acc.x);
-                    acc.y = epi(p.ep, p.ep_act, p.ep_lo, p.ep_hi, p.coff + n + 1, acc.y);
-                    acc.z = epi(p.ep, p.ep_act, p.ep_lo, p.ep_hi, p.coff + n + 2, acc.z);
-                    acc.w = epi(p.ep, p.ep_act, p.ep_lo, p.ep_hi, p.coff + n + 3, acc.w);
-                }
-            }
-            const float4 r = post4(p, o, acc, pb);
-            *reinterpret_cast<float4 *>(p.C + o) = r;
-            if (p.em.w) emit4(p, ec, o, r, sehi, neg);
-        }
-        if (p.em.w) {
-            wave_max_atomic(p.em.invalid + 5, sehi);
-            wave_sign_record(p.em.invalid + 6, neg);
-        }
-        return;
-    }
-    for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < MN; q += stride) {
-        float acc = p.part[q];
-        for (int sp = 1; sp < S; ++sp) acc += p.part[sp * MN + q];
-        int64_t o, ch;
-        if (p.nchw) {
-            const int64_t img = q / (p.N * p.hw), rem = q - img * p.N * p.hw, n = rem / p.hw, pix = rem - n * p.hw;
-            o = (img * p.ctot + p.coff + n) * p.hw + pix;
-            ch = p.coff + n;
-        } else {
-            const int64_t m = q / p.N, n = q - m * p.N;
-            o = m * p.ldc + n;
-            ch = p.coff + n;
-        }
-        const float r = post1(p, o, epi(p.ep, p.ep_act, p.ep_lo, p.ep_hi, ch, acc), pb);
-        p.C[o] = r;
-        if (p.em.w) emit1(p, ec, o, r, sehi, neg);
+    if (splitk_vec(p)) {
+        for (int64_t q4 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q4 < MN / 4; q4 += stride)
+            splitk_finish4<true, true, true>(p, sc, q4 * 4, sehi, neg);
+    } else {
+        for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < MN; q += stride)
+            splitk_finish1<true, true, true>(p, sc, q, sehi, neg);
     }
     if (p.em.w) {
         wave_max_atomic(p.em.invalid + 5, sehi);
@@ -622,6 +570,11 @@ static int g_opt_xm_ncg = getenv("FP8A_XM_NCG") ? atoi(getenv("FP8A_XM_NCG")) : 
 // "xm_sign_rows": gemm_f8mx_kernel builds the negative-sign half of its tile table only for launches
 // whose A words address it (1, the default); 0: always both halves (the same bits, for A/B runs)
 static int g_opt_xm_sign_rows = getenv("FP8A_XM_SIGN_ROWS") ? atoi(getenv("FP8A_XM_SIGN_ROWS")) : 1;
+// "fq_fast": the matrix-core path's fake quantizers (the post quantizer, the emitted words' quantizer,
+// the fused input quantizer of the A pre-pass, the split-K reduction; not the fp32 staging) run
+// fq_apply_fast and the emitted word is formed from the quantized value's bits (fq_word), wherever the
+// uniform guards hold (fp8approx_common.h); 0 restores the literal forms.  Same bits either way.
+static int g_opt_fq_fast = getenv("FP8A_FQ_FAST") ? atoi(getenv("FP8A_FQ_FAST")) != 0 : 1;
 static int xm_ncg(int64_t N) {
     const int forced = g_opt_xm_ncg;
     if (forced == 1 || forced == 2 || forced == 4) return forced;
@@ -758,12 +711,15 @@ static int device_cus() {
 // FP8A_SPLITK=<S> forces S (experiments).  g_splitk_launches: launches that ran split (their
 // splitk_reduce_kernel stores the output), host-side, fp8a_splitk_stats.
 static uint64_t g_splitk_launches = 0;
+// "splitk" (FP8A_SPLITK): the forced split count (0: chosen per launch).  "splitk_fixup" (default 0;
+// FP8A_SPLITK_FIXUP): the split E4M3 matrix-core launches sum their partials inside the launch (the tile's
+// last-arriving block, gemm_f8mx.h) instead of in splitk_reduce_kernel; same bits.  Off by default: it
+// measured slower than the separate pass on every workload (the last block reads S x 32 KB serially while
+// the reduce kernel streams at the memory rate).
+static int g_opt_splitk = getenv("FP8A_SPLITK") ? std::max(0, atoi(getenv("FP8A_SPLITK"))) : 0;
+static int g_opt_splitk_fixup = getenv("FP8A_SPLITK_FIXUP") ? atoi(getenv("FP8A_SPLITK_FIXUP")) != 0 : 0;
 static int choose_splits(int64_t M, int64_t N, int64_t K) {
-    static int forced = -1;
-    if (forced < 0) {
-        const char *e = getenv("FP8A_SPLITK");
-        forced = e ? std::max(0, atoi(e)) : 0;
-    }
+    const int forced = g_opt_splitk;
     const int64_t kt = (K + BK - 1) / BK;
     if (forced > 0) return (int)std::max<int64_t>(1, std::min<int64_t>(forced, kt));
     const int64_t tiles = ((M + BM - 1) / BM) * ((N + BN - 1) / BN);
@@ -810,9 +766,15 @@ static size_t unit_bytes(int64_t M, int64_t N) {
 }
 static size_t head_bytes(int64_t M, int64_t N) { return FLAG_BYTES + unit_bytes(M, N); }
 
+// (the partial tiles, then the in-launch sum's arrival counters: one word per output tile, sized for the
+// smallest tile -- 128 rows or 16 columns -- of gemm_f8mx_kernel)
+static int64_t splitk_counter_words(int64_t M, int64_t N) { return ((M + 63) / 64) * ((N + 15) / 16); }
+static size_t splitk_part_bytes(int S, int64_t M, int64_t N) {
+    return align256((size_t)S * (size_t)M * (size_t)N * sizeof(float));
+}
 static size_t splitk_bytes(int64_t M, int64_t N, int64_t K) {
     const int S = choose_splits(M, N, K);
-    return S > 1 ? align256((size_t)S * (size_t)M * (size_t)N * sizeof(float)) : 0;
+    return S > 1 ? splitk_part_bytes(S, M, N) + align256((size_t)splitk_counter_words(M, N) * 4) : 0;
 }
 
 
@@ -1148,6 +1110,13 @@ static int run_gemm(GemmArgs &a, const int32_t *table, void *ws, size_t ws_bytes
             if (a.wfmt == 1 && !g_opt_tt_band) a.ebr = nullptr;  // (gemm_tt_kernel: no band test)
             a.xncg = tt ? 4 : xm_ncg(a.N);
             a.xm_signs = g_opt_xm_sign_rows;
+            // the in-launch split-K sum: the E4M3 matrix-core kernel (the E5M2 form's halved-block rerun
+            // writes a tile's partials a second time, after its counter has run out: it keeps the reduce pass)
+            a.skcnt = nullptr;
+            if (a.splits > 1 && g_opt_splitk_fixup && a.wfmt == 0 && a.Mw == 3) {
+                a.skcnt = (uint32_t *)((char *)ws + head + splitk_part_bytes(a.splits, a.M, a.N));
+                a.sk_words = splitk_counter_words(a.M, a.N);
+            }
             // the input's word image from the previous launch (fp8a_conv2d_chain): its words replace
             // the A pre-pass, which then runs gated (only to write the fused quantizer's bias, or to
             // re-decode x if the image arrived invalid)
@@ -1218,7 +1187,9 @@ static int run_gemm(GemmArgs &a, const int32_t *table, void *ws, size_t ws_bytes
     }
     rc = hip_check("fp8a fast gemm launch");
     if (rc) return rc;
-    if (a.splits > 1) {
+    if (a.splits > 1 && a.aw != nullptr && a.skcnt != nullptr) {
+        ++g_splitk_launches;  // (summed inside the launch)
+    } else if (a.splits > 1) {
         const int64_t q = a.M * a.N;
         const unsigned rb = (unsigned)std::min<int64_t>((q / 4 + 255) / 256 + 1, 8192);
         splitk_reduce_kernel<<<rb, 256, 0, s>>>(a);
@@ -1541,6 +1512,21 @@ int fp8a_set_option(const char *name, int value) {
         g_opt_xm_sign_rows = value != 0;
         return old;
     }
+    if (strcmp(name, "splitk_fixup") == 0) {
+        const int old = g_opt_splitk_fixup;
+        g_opt_splitk_fixup = value != 0;
+        return old;
+    }
+    if (strcmp(name, "splitk") == 0) {
+        const int old = g_opt_splitk;
+        g_opt_splitk = std::max(0, value);
+        return old;
+    }
+    if (strcmp(name, "fq_fast") == 0) {
+        const int old = g_opt_fq_fast;
+        g_opt_fq_fast = value != 0;
+        return old;
+    }
     if (strcmp(name, "af32_maxct") == 0) {
         const int old = g_opt_af32_maxct;
         g_opt_af32_maxct = std::max(0, value);
@@ -1597,6 +1583,67 @@ int fp8a_set_option(const char *name, int value) {
         return old;
     }
     return fail(FP8A_EINVAL, std::string("unknown option ") + name);
+}
+
+// fp8a_fq_selfcheck: the fast quantizer / word forms against the literal ones, pattern by pattern
+__global__ __launch_bounds__(256) void fq_selfcheck_kernel(float mx, int E, int M, int S, int mode, int bR, uint64_t first,
+                                                           uint64_t count, unsigned long long *out) {
+    const float bias = fq_bias(mx, E, M);
+    const bool fast = fq_fast_ok(mx, bias, M);
+    const FqFast k = fast ? fq_fast_k(mx, bias, M) : FqFast{};
+    const uint32_t emn = fast ? k.emn : 0x3F800000u;
+    const int xb = xm_xbias(M), kse = 254 + xb - bR;
+    const bool chk = fast && (mode == 2 || fq_word_chk(mx, bias, M, kse));
+    unsigned long long bad = 0, lowest = ~0ull;
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < count; i += stride) {
+        const uint32_t bits = (uint32_t)(first + i);
+        const float v = __uint_as_float(bits);
+        const float ql = fq_apply(v, mx, bias, M, S);
+        const float qf = fast ? fq_apply_f<true>(v, mx, bias, M, S, k) : ql;
+        bool diff;
+        if (mode == 0) {
+            diff = __float_as_uint(ql) != __float_as_uint(qf);
+        } else {
+            bool okl = true, okf = true;
+            const uint32_t wl = xm_word_a(ql, M, xb, emn, bR, okl);
+            const uint32_t wf = fast ? fq_word(qf, M, kse, chk, okf) : xm_word_a(qf, M, xb, emn, bR, okf);
+            diff = wl != wf || okl != okf;
+        }
+        if (diff) {
+            ++bad;
+            lowest = min(lowest, (unsigned long long)bits);
+        }
+    }
+    if (bad) {
+        atomicAdd(out, bad);
+        atomicMin(out + 1, lowest);
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) out[2] = (fast ? 1ull : 0ull) | (chk ? 2ull : 0ull);
+}
+
+int fp8a_fq_selfcheck(float maxval, int E, int M, int sign_bits, int mode, int bR, uint64_t first, uint64_t count,
+                      uint64_t *out, fp8a_stream_t stream) {
+    if (out == nullptr) return fail(FP8A_EINVAL, "null pointer");
+    if (E < 1 || M < 1 || M > 6 || mode < 0 || mode > 2 || (mode != 0 && M != 3 && M != 2))
+        return fail(FP8A_EFORMAT, "fp8a_fq_selfcheck: bad format or mode");
+    if (first > 0xFFFFFFFFull || count > (1ull << 32) - first) return fail(FP8A_EINVAL, "pattern range beyond 2^32");
+    hipStream_t s = (hipStream_t)stream;
+    unsigned long long *d = nullptr;
+    const unsigned long long init[3] = {0ull, ~0ull, 0ull};
+    if (hipMalloc(&d, sizeof(init)) != hipSuccess) return hip_check("fp8a_fq_selfcheck");
+    unsigned long long h[3] = {0, 0, 0};
+    bool ok = hipMemcpyAsync(d, init, sizeof(init), hipMemcpyHostToDevice, s) == hipSuccess;
+    if (ok && count > 0) {
+        const unsigned blocks = (unsigned)std::min<uint64_t>((count + 255) / 256, 8192);
+        fq_selfcheck_kernel<<<blocks, 256, 0, s>>>(maxval, E, M, sign_bits, mode, bR, first, count, d);
+    }
+    ok = ok && hipMemcpyAsync(h, d, sizeof(h), hipMemcpyDeviceToHost, s) == hipSuccess &&
+         hipStreamSynchronize(s) == hipSuccess;
+    (void)hipFree(d);
+    if (!ok) return hip_check("fp8a_fq_selfcheck");
+    for (int i = 0; i < 3; ++i) out[i] = h[i];
+    return FP8A_OK;
 }
 
 int fp8a_fallback_stats(uint64_t *out, int reset) {
@@ -1794,6 +1841,7 @@ static GemmArgs make_args(const float *A, int64_t lda, const float *B, int64_t s
     a.bA = bA; a.bB = bB; a.bBs = bBs; a.bR = bR;
     a.flags = flags; a.nchw = 0; a.hw = 1; a.ctot = N; a.coff = 0;
     a.splits = 1; a.kchunk = K; a.part = nullptr;
+    a.fq_fast = g_opt_fq_fast;
     return a;
 }
 

@@ -74,6 +74,45 @@ __device__ __forceinline__ float fq_apply(float v, float mx, float bias, int M, 
     return fq_apply_lit(fminf(fmaxf(v, sign_bits ? -mx : 0.0f), mx), bias, M);
 }
 
+// The fast form of fq_apply_lit (option "fq_fast"): the same value, bit for bit, as
+//     q = (xc + C) - C,  C = 1.5 * 2^(k + 23),  k = max(floor(log2 |xc|), 1 - bias) - M.
+// The float add rounds to nearest-even at bit k (C is an even multiple of 2^k and |xc| < 2^(k+M+1)
+// keeps the sum inside C's binade); the subtraction is exact.  C's bits are
+//     max(exponent field of xc, emn) + cadd,  emn = bits(2^(1 - bias)),  cadd = (23 - M) << 23 | 0x400000
+// (a zero or float-subnormal xc has field 0 and takes emn, as ls = 1 does).  The sum loses the sign
+// of a negative xc that rounds to zero, which the literal form keeps (rint(-0.3) = -0.0): xc's sign
+// bit is copied onto q.  Six operations (and, max, add, add, sub, bfi) for the literal form's ~30.
+// Valid while every reachable k keeps 2^k and 2^(k+24) normal floats and the literal form's own
+// arithmetic on bias is exact: fq_fast_ok, a conservative window on the quantizer's constants (wave
+// uniform, tested once per launch / epilogue).  Outside it -- the literal form's k < -126 / k < -149
+// arms, a NaN or infinite bias (maxval <= 0 or not finite) -- callers keep the literal form.
+struct FqFast {
+    uint32_t emn, cadd;
+    float mx;  // the quantizer's maxval, read once (the literal callers re-read it from memory per value)
+};
+__device__ __forceinline__ bool fq_fast_ok(float mx, float bias, int M) {
+    return bias >= -100.0f && bias <= 120.0f && mx >= 0x1p-100f && mx <= 0x1p64f && M >= 1 && M <= 6;
+}
+__device__ __forceinline__ FqFast fq_fast_k(float mx, float bias, int M) {  // (fq_fast_ok holds)
+    return FqFast{(uint32_t)(128 - (int)bias) << 23, ((uint32_t)(23 - M) << 23) | 0x00400000u, mx};
+}
+__device__ __forceinline__ float fq_apply_fast(float xc, const FqFast &k) {
+    const uint32_t u = __float_as_uint(xc);
+    const float C = __uint_as_float(max(u & 0x7F800000u, k.emn) + k.cadd);
+    const float q = (xc + C) - C;
+    return __uint_as_float((__float_as_uint(q) & 0x7FFFFFFFu) | (u & 0x80000000u));
+}
+// fq_apply; FQF = true: the fast form where the caller's uniform test allowed it (k.emn != 0; k.mx = maxval
+// either way), the literal one else -- one uniform branch per value; false: the literal form only
+template <bool FQF>
+__device__ __forceinline__ float fq_apply_f(float v, float mx, float bias, int M, int sign_bits, const FqFast &k) {
+    if (FQF) {  // (k.emn = 0: the guard failed, uniform)
+        const float xc = fminf(fmaxf(v, sign_bits ? -k.mx : 0.0f), k.mx);
+        return k.emn ? fq_apply_fast(xc, k) : fq_apply_lit(xc, bias, M);
+    }
+    return fq_apply_lit(fminf(fmaxf(v, sign_bits ? -mx : 0.0f), mx), bias, M);
+}
+
 // Word-image hand-off (round 4, fp8a_conv2d_chain): a convolution's store also writes the NEXT
 // convolution's pre-decoded A operand -- its zero-bordered word image (gemm_f8mx.h: the word of
 // fq_next(y) for every output element y) -- so the next launch skips its xm_decode_a pass (which
@@ -124,10 +163,15 @@ struct GemmArgs {
     int64_t nur, nuc;
     // split-K: block b works on tile b % tiles over k in [s*kchunk, (s+1)*kchunk), s = b / tiles;
     // with splits > 1 it writes its partial tile to part + s*M*N (the output layout with
-    // ctot = N, coff = 0, ldc = N) and splitk_reduce_kernel sums the splits in order
+    // ctot = N, coff = 0, ldc = N) and splitk_reduce_kernel sums the splits in order -- or, with skcnt
+    // (option "splitk_fixup", gemm_f8mx_kernel's E4M3 launches), the tile's last-arriving block does, in
+    // the same order, inside the launch: skcnt[tile] counts the arrivals (sk_words words after the
+    // partials in the workspace, zeroed by xm_decode_b ahead of every launch)
     int splits;
     int64_t kchunk;
     float *part;
+    uint32_t *skcnt;
+    int64_t sk_words;
     // implicit-GEMM convolution: A(m, k) gathered from NCHW x (no im2col image), m = (b, ho, wo),
     // k = (c, ky, kx) within the group -- the reference's im2col order (approx_calculation.py:745)
     int conv;
@@ -156,6 +200,8 @@ struct GemmArgs {
     int xncg;          // gemm_f8mx_kernel's column groups per tile (4: 128 x 64, 2: 128 x 32, 1: 256 x 16)
     int xm_signs;      // gemm_f8mx_kernel builds the negative-sign table rows only when flag[3] says an A word
                        // addresses them (option "xm_sign_rows"; 0: always both halves)
+    int fq_fast;       // option "fq_fast": the matrix-core path's quantizers and emitted words take their fast
+                       // forms (fq_apply_fast, fq_word) where the uniform guards allow; 0: the literal forms
     const uint2 *bqw;
     const uint32_t *lutw;  // the LDS table image (XM_LUT_WORDS words), written by xm_decode_b
     // E5M2 (gemm_f8mx_kernel XF = 1): per (K-step, 16-column group) the nonzero B elements' exponent
@@ -242,27 +288,30 @@ __device__ __forceinline__ float gelu_erf(float x) {
 
 // GELU = false compiles the GELU tail out (the word-emitting store of gemm_f8mx_kernel, whose
 // registers are at its occupancy budget; the host never pairs GELU with emission).
-template <bool GELU = true>
-__device__ __forceinline__ float post_tail(const GemmArgs &p, float v, float pb) {
+// FQF = true: the post quantizer in its fast form where pk says so (pk.emn != 0: StoreCtx, store_ctx tested
+// fq_fast_ok), maxval read from pk.mx either way; false: the literal form only.
+template <bool GELU = true, bool FQF = false>
+__device__ __forceinline__ float post_tail(const GemmArgs &p, float v, float pb, const FqFast &pk = FqFast{}) {
     if (p.post_act == 1) v = fminf(fmaxf(v, p.post_lo), p.post_hi);
     else if (GELU && p.post_act == 2) v = gelu_erf(v);
-    if (p.post_fq.mx) v = fq_apply(v, *p.post_fq.mx, pb, p.post_fq.M, p.post_fq.S);
+    if (p.post_fq.mx) v = fq_apply_f<FQF>(v, FQF ? pk.mx : *p.post_fq.mx, pb, p.post_fq.M, p.post_fq.S, pk);
     return v;
 }
 
-template <bool GELU = true>
-__device__ __forceinline__ float post1(const GemmArgs &p, int64_t o, float v, float pb) {
+template <bool GELU = true, bool FQF = false>
+__device__ __forceinline__ float post1(const GemmArgs &p, int64_t o, float v, float pb, const FqFast &pk = FqFast{}) {
     if (p.res) v += p.res[o];
-    return post_tail<GELU>(p, v, pb);
+    return post_tail<GELU, FQF>(p, v, pb, pk);
 }
 
-template <bool GELU = true>
-__device__ __forceinline__ float4 post4(const GemmArgs &p, int64_t o, float4 v, float pb) {
+template <bool GELU = true, bool FQF = false>
+__device__ __forceinline__ float4 post4(const GemmArgs &p, int64_t o, float4 v, float pb, const FqFast &pk = FqFast{}) {
     if (p.res) {
         const float4 r = *reinterpret_cast<const float4 *>(p.res + o);
         v.x += r.x; v.y += r.y; v.z += r.z; v.w += r.w;
     }
-    return make_float4(post_tail<GELU>(p, v.x, pb), post_tail<GELU>(p, v.y, pb), post_tail<GELU>(p, v.z, pb), post_tail<GELU>(p, v.w, pb));
+    return make_float4(post_tail<GELU, FQF>(p, v.x, pb, pk), post_tail<GELU, FQF>(p, v.y, pb, pk),
+                       post_tail<GELU, FQF>(p, v.z, pb, pk), post_tail<GELU, FQF>(p, v.w, pb, pk));
 }
 
 // y = x * scale + shift with scale = gamma * invstd, shift = beta - mean * scale (ATen's eval
@@ -296,6 +345,8 @@ __host__ __device__ constexpr int xm_xbias(int Mw);
 // Nonzero words keep se <= 252, so a zero word is the one with se = 253, and the E5M2 halved form's
 // se + 1 (254: 2^127) still flushes it to 0.
 constexpr uint32_t XM_ZERO_WORD = 253u << 23;
+// A word bits 3-6: the tile-table row (8 s_a + m_a) * 8 = its byte offset in a column block
+constexpr uint32_t XM_ROW_SHIFT = 3, XM_ROW_MASK = 0x78u;
 
 // Word-image emission (EmitW): one word per final output value at NCHW output index o (< 2^31,
 // the host checks).  The next quantizer's constants sit in the image's header (emit_prep_kernel:
@@ -307,6 +358,9 @@ struct EmitCtx {
     float mx, fb;
     uint32_t emn;
     int bR;
+    FqFast k;   // the fast forms' constants (emit_ctx_fast)
+    int kse;
+    bool chk;
 };
 __device__ __forceinline__ EmitCtx emit_ctx(const GemmArgs &p) {
     EmitCtx e{};
@@ -318,13 +372,78 @@ __device__ __forceinline__ EmitCtx emit_ctx(const GemmArgs &p) {
     e.bR = __builtin_amdgcn_readfirstlane((int)p.em.invalid[4]);
     return e;
 }
+
+// xm_word_a(q) (gemm_f8mx.h) for a q that the (M, bias) quantizer just produced, from q's bits: q is on
+// the decode's grid by construction when the decode's M and min-normal are the quantizer's (fq_word_ok),
+// so the grid test drops out, the scale exponent is kse - (exponent field of q), kse = 254 + xb - bR, and
+// the row is q's sign and top M mantissa bits.  What is left of `ok` is the exactness window and the
+// scale range; chk = false when the quantizer's reachable exponents -- the smallest subnormal
+// 2^(1 - bias - M) up to one binade above maxval's (its rounding can carry) -- lie inside both, and then
+// no element is tested (uniform, once per epilogue).  The same word and the same ok as xm_word_a's.
+__device__ __forceinline__ bool fq_word_ok(int fqM, float fbias, int Mw, uint32_t emn) {
+    return fqM == Mw && emn == ((uint32_t)(128 - (int)fbias) << 23);  // (after fq_fast_ok)
+}
+__device__ __forceinline__ bool fq_word_chk(float mx, float fbias, int Mw, int kse) {
+    const int lo = 128 - (int)fbias - Mw, hi = (int)(__float_as_uint(mx) >> 23) + 1;  // exponent fields
+    return !(lo >= max(65, kse - 252) && hi <= min(176, kse - 1));
+}
+__device__ __forceinline__ uint32_t fq_word(float q, int Mw, int kse, bool chk, bool &ok) {
+    const uint32_t u = __float_as_uint(q), ua = u & 0x7FFFFFFFu;
+    int se = kse - (int)(ua >> 23);
+    if (chk) {
+        ok = ua == 0u || (ua >= 0x20800000u && ua <= 0x58800000u && se >= 1 && se <= 252);
+        se = min(max(se, 1), 252);
+    } else {
+        ok = true;
+    }
+    const uint32_t mc = (ua >> (23 - Mw)) & ((1u << Mw) - 1u);  // row 8 s_a + m_a, as xm_word_a places it
+    return ua == 0u ? XM_ZERO_WORD : (((uint32_t)se << 23) | (((u >> 31) * 8u + mc) << XM_ROW_SHIFT));
+}
+// FQF (emission): the next quantizer passes fq_fast_ok and, for form-0 words, fq_word_ok
+__device__ __forceinline__ bool emit_fast_ok(const GemmArgs &p, const EmitCtx &e) {
+    return fq_fast_ok(e.mx, e.fb, p.em.fq.M) && (p.em.form != 0 || fq_word_ok(p.em.fq.M, e.fb, p.em.Mw, e.emn));
+}
+__device__ __forceinline__ void emit_ctx_fast(const GemmArgs &p, EmitCtx &e) {  // (emit_fast_ok holds)
+    e.k = fq_fast_k(e.mx, e.fb, p.em.fq.M);
+    e.kse = 254 + xm_xbias(p.em.Mw) - e.bR;
+    e.chk = fq_word_chk(e.mx, e.fb, p.em.Mw, e.kse);
+}
+// What a final store needs of its quantizers, computed once per block (wave-uniform): the post
+// quantizer's bias, the emission's header constants, and the store's one test (option "fq_fast"): fqf =
+// every quantizer the store runs -- the post quantizer, the emitted words' -- passes its guard; then pk /
+// ec hold the fast forms' constants, else the store keeps the literal forms throughout.
+struct StoreCtx {
+    float pb;
+    FqFast pk;
+    EmitCtx ec;
+    bool fqf;
+};
+template <bool EMIT>
+__device__ __forceinline__ StoreCtx store_ctx(const GemmArgs &p, bool fast_allowed = true) {
+    StoreCtx c{};
+    c.pb = post_bias(p);
+    if (EMIT) c.ec = emit_ctx(p);
+    const bool emit = EMIT && p.em.w != nullptr;
+    const float pmx = p.post_fq.mx ? *p.post_fq.mx : 0.0f;
+    c.fqf = fast_allowed && p.fq_fast && (!p.post_fq.mx || fq_fast_ok(pmx, c.pb, p.post_fq.M)) &&
+            (!emit || emit_fast_ok(p, c.ec));
+    c.pk.mx = pmx;  // (emn = 0: the literal forms, with maxval still read once)
+    c.ec.k.mx = c.ec.mx;
+    if (c.fqf) {
+        if (p.post_fq.mx) c.pk = fq_fast_k(pmx, c.pb, p.post_fq.M);
+        if (emit) emit_ctx_fast(p, c.ec);
+    }
+    return c;
+}
+template <bool FQF = false>
 __device__ __forceinline__ uint32_t emit_word(const GemmArgs &p, const EmitCtx &e, float v, bool &ok) {
-    const float q = fq_apply(v, e.mx, e.fb, p.em.fq.M, p.em.fq.S);
+    const float q = fq_apply_f<FQF>(v, e.mx, e.fb, p.em.fq.M, p.em.fq.S, e.k);
     if (p.em.form) {  // tbx_decode_a's word of q (a value off the grid / outside the window: invalid)
         const uint32_t u = __float_as_uint(q), ua = u & 0x7FFFFFFFu, M = (uint32_t)p.em.Mw;
         ok = ok && (ua == 0u || ((ua & ((1u << (23 - M)) - 1u)) == 0u && ua >= 0x20800000u && ua <= 0x58800000u));
         return ua == 0u ? 0u : ((u & 0xFF800000u) | (((ua >> (23 - M)) & ((1u << M) - 1u)) << 3));
     }
+    if (FQF && e.k.emn) return fq_word(q, p.em.Mw, e.kse, e.chk, ok);
     return xm_word_a(q, p.em.Mw, xm_xbias(p.em.Mw), e.emn, e.bR, ok);
 }
 // word index of NCHW output index o
@@ -372,12 +491,13 @@ __device__ __forceinline__ void wave_sign_record(uint32_t *dst, uint32_t words_o
     if ((threadIdx.x & 63) == 0 && any) sign_record(dst, XM_SIGN_BIT);
 }
 
+template <bool FQF = false>
 __device__ __forceinline__ void emit1(const GemmArgs &p, const EmitCtx &e, int64_t o, float v, uint32_t &sehi,
                                       uint32_t &neg) {
     uint32_t wo;
     const uint32_t wi = emit_index(p, (uint32_t)o, wo);
     bool ok = true;
-    const uint32_t w = emit_word(p, e, v, ok);
+    const uint32_t w = emit_word<FQF>(p, e, v, ok);
     p.em.w[wi] = w;
     sehi = max(sehi, word_sehi(w));
     neg |= w;
@@ -385,13 +505,14 @@ __device__ __forceinline__ void emit1(const GemmArgs &p, const EmitCtx &e, int64
 }
 // four consecutive outputs (o % 4 == 0 in an NCHW plane of hw % 4 == 0): one 16-B store when
 // they sit in one row of the image (Wo % 4 == 0: always; the interior rows start 16-B aligned)
+template <bool FQF = false>
 __device__ __forceinline__ void emit4(const GemmArgs &p, const EmitCtx &e, int64_t o, float4 v, uint32_t &sehi,
                                       uint32_t &neg) {
     uint32_t wo;
     const uint32_t wi = emit_index(p, (uint32_t)o, wo);
     bool ok0 = true, ok1 = true, ok2 = true, ok3 = true;
-    const uint4 w = make_uint4(emit_word(p, e, v.x, ok0), emit_word(p, e, v.y, ok1), emit_word(p, e, v.z, ok2),
-                               emit_word(p, e, v.w, ok3));
+    const uint4 w = make_uint4(emit_word<FQF>(p, e, v.x, ok0), emit_word<FQF>(p, e, v.y, ok1),
+                               emit_word<FQF>(p, e, v.z, ok2), emit_word<FQF>(p, e, v.w, ok3));
     sehi = max(max(sehi, max(word_sehi(w.x), word_sehi(w.y))), max(word_sehi(w.z), word_sehi(w.w)));
     neg |= (w.x | w.y) | (w.z | w.w);
     if (wo + 3 < (uint32_t)p.em.Wo && (wi & 3u) == 0u) {
@@ -441,14 +562,25 @@ __device__ __forceinline__ bool stage_decode(float x, int M, uint32_t emn, bool 
 // EMIT = false compiles the word-image emission out (gemm_f8mx_kernel's non-emitting instances:
 // the emission code alone pushed that kernel past its 80-VGPR budget).
 // GELU = false: the GELU tail compiled out as well (gemm_f8mx_kernel's emitting instances).
-template <bool EMIT = true, bool GELU = true>
+// FQF = true: the post quantizer and the emission take their fast forms where sc.fqf says so (a uniform
+// choice per value around the literal code: ONE copy of the store, so that no instance of
+// gemm_f8mx_kernel allocates more registers than its literal-only store did); false: no fast code.
+// sc: the block's StoreCtx (unsplit launches; a split launch stores raw partials and reads none of it).
+// -DFP8A_RAW_STORE_DIAG=1 (diagnostic build only, tools/gemm_bench.py --emit: DESIGN.md 3v): the emitting
+// instances store the raw fp32 accumulators and nothing else -- no BN / activation, residual, quantizer, word
+// or header record -- which bounds what the emitting store can cost.  Its results are wrong; it never ships.
+#ifndef FP8A_RAW_STORE_DIAG
+#define FP8A_RAW_STORE_DIAG 0
+#endif
+template <bool EMIT = true, bool GELU = true, bool FQF = false>
 __device__ __forceinline__ void store_tile(const GemmArgs &p, int64_t split, int64_t m0, int64_t n0, int ty, int tx,
-                                           float (&acc)[TM][TN]) {
+                                           float (&acc)[TM][TN], const StoreCtx &sc) {
+    constexpr bool RAW = FP8A_RAW_STORE_DIAG && EMIT;
     const bool partial = p.splits > 1;
     float *const C = partial ? p.part + split * p.M * p.N : p.C;
     const int64_t ldc = partial ? p.N : p.ldc, ctot = partial ? p.N : p.ctot, coff = partial ? 0 : p.coff;
     const int64_t nb = n0 + tx * TN;
-    if (!partial && p.ep != nullptr) {  // fused BN + activation (split-K applies it in the reduction)
+    if (!partial && !RAW && p.ep != nullptr) {  // fused BN + activation (split-K applies it in the reduction)
 #pragma unroll
         for (int j = 0; j < TN; ++j) {
             const int64_t ch = p.coff + min<int64_t>(nb + j, p.N - 1);
@@ -456,22 +588,23 @@ __device__ __forceinline__ void store_tile(const GemmArgs &p, int64_t split, int
             for (int i = 0; i < TM; ++i) acc[i][j] = epi(p.ep, p.ep_act, p.ep_lo, p.ep_hi, ch, acc[i][j]);
         }
     }
-    const float pb = partial ? 0.0f : post_bias(p);
+    const float pb = sc.pb;
     const GemmArgs &q = p;
     // word-image emission from each final value (the split-K reduction emits instead)
-    const bool emit = EMIT && !partial && p.em.w != nullptr;
-    const EmitCtx ec = EMIT ? emit_ctx(p) : EmitCtx{};
+    const bool emit = EMIT && !RAW && !partial && p.em.w != nullptr;
+    const EmitCtx &ec = sc.ec;
+    const FqFast &pk = sc.pk;
     uint32_t sehi = 0, neg = 0;
     auto fin1 = [&](int64_t o, float v) {
-        if (partial) return v;
-        v = post1<GELU>(q, o, v, pb);
-        if (emit) emit1(q, ec, o, v, sehi, neg);
+        if (partial || RAW) return v;
+        v = post1<GELU, FQF>(q, o, v, pb, pk);
+        if (emit) emit1<FQF>(q, ec, o, v, sehi, neg);
         return v;
     };
     auto fin4 = [&](int64_t o, float4 v) {
-        if (partial) return v;
-        v = post4<GELU>(q, o, v, pb);
-        if (emit) emit4(q, ec, o, v, sehi, neg);
+        if (partial || RAW) return v;
+        v = post4<GELU, FQF>(q, o, v, pb, pk);
+        if (emit) emit4<FQF>(q, ec, o, v, sehi, neg);
         return v;
     };
     if (!p.nchw) {
@@ -521,6 +654,119 @@ __device__ __forceinline__ void store_tile(const GemmArgs &p, int64_t split, int
         wave_max_atomic(p.em.invalid + 5, sehi);
         wave_sign_record(p.em.invalid + 6, neg);
     }
+}
+
+// The final values of a split launch from its partial tiles (layout: row-major [M][N], or [img][N][hw] for an
+// NCHW output), at partial index q: the splits summed in split order from slab 0, then BN / activation, the
+// block tail and the emission -- four consecutive values (q % 4 == 0, the vector form's conditions:
+// splitk_vec) or one.  splitk_reduce_kernel runs them over the whole output, the in-launch sum
+// (gemm_f8mx_kernel) over its tile: one definition, so the two give the same bits.
+__device__ __forceinline__ bool splitk_vec(const GemmArgs &p) {
+    const bool vec = p.nchw ? ((p.hw & 3) == 0) : ((p.N & 3) == 0 && (p.ldc & 3) == 0);
+    return vec && ((((uintptr_t)p.C) & 15) == 0) && ((((uintptr_t)p.part) & 15) == 0) && (((p.M * p.N) & 3) == 0) &&
+           ((((uintptr_t)p.res) & 15) == 0);
+}
+template <bool EMIT, bool GELU, bool FQF>
+__device__ __forceinline__ void splitk_finish4(const GemmArgs &p, const StoreCtx &sc, int64_t q, uint32_t &sehi,
+                                               uint32_t &neg) {
+    const int64_t MN = p.M * p.N;
+    float4 acc = *reinterpret_cast<const float4 *>(p.part + q);
+    for (int sp = 1; sp < p.splits; ++sp) {
+        const float4 v = *reinterpret_cast<const float4 *>(p.part + sp * MN + q);
+        acc.x += v.x; acc.y += v.y; acc.z += v.z; acc.w += v.w;
+    }
+    int64_t o;
+    if (p.nchw) {
+        const int64_t img = q / (p.N * p.hw), rem = q - img * p.N * p.hw, n = rem / p.hw, pix = rem - n * p.hw;
+        o = (img * p.ctot + p.coff + n) * p.hw + pix;
+        if (p.ep) {  // the 4 values share channel coff + n (hw % 4 == 0)
+            const int64_t ch = p.coff + n;
+            acc.x = epi(p.ep, p.ep_act, p.ep_lo, p.ep_hi, ch, acc.x);
+            acc.y = epi(p.ep, p.ep_act, p.ep_lo, p.ep_hi, ch, acc.y);
+            acc.z = epi(p.ep, p.ep_act, p.ep_lo, p.ep_hi, ch, acc.z);
+            acc.w = epi(p.ep, p.ep_act, p.ep_lo, p.ep_hi, ch, acc.w);
+        }
+    } else {
+        const int64_t m = q / p.N, n = q - m * p.N;
+        o = m * p.ldc + n;
+        if (p.ep) {
+            acc.x = epi(p.ep, p.ep_act, p.ep_lo, p.ep_hi, p.coff + n, acc.x);
+            acc.y = epi(p.ep, p.ep_act, p.ep_lo, p.ep_hi, p.coff + n + 1, acc.y);
+            acc.z = epi(p.ep, p.ep_act, p.ep_lo, p.ep_hi, p.coff + n + 2, acc.z);
+            acc.w = epi(p.ep, p.ep_act, p.ep_lo, p.ep_hi, p.coff + n + 3, acc.w);
+        }
+    }
+    const float4 r = post4<GELU, FQF>(p, o, acc, sc.pb, sc.pk);
+    *reinterpret_cast<float4 *>(p.C + o) = r;
+    if (EMIT && p.em.w) emit4<FQF>(p, sc.ec, o, r, sehi, neg);
+}
+template <bool EMIT, bool GELU, bool FQF>
+__device__ __forceinline__ void splitk_finish1(const GemmArgs &p, const StoreCtx &sc, int64_t q, uint32_t &sehi,
+                                               uint32_t &neg) {
+    const int64_t MN = p.M * p.N;
+    float acc = p.part[q];
+    for (int sp = 1; sp < p.splits; ++sp) acc += p.part[sp * MN + q];
+    int64_t o, ch;
+    if (p.nchw) {
+        const int64_t img = q / (p.N * p.hw), rem = q - img * p.N * p.hw, n = rem / p.hw, pix = rem - n * p.hw;
+        o = (img * p.ctot + p.coff + n) * p.hw + pix;
+        ch = p.coff + n;
+    } else {
+        const int64_t m = q / p.N, n = q - m * p.N;
+        o = m * p.ldc + n;
+        ch = p.coff + n;
+    }
+    const float r = post1<GELU, FQF>(p, o, epi(p.ep, p.ep_act, p.ep_lo, p.ep_hi, ch, acc), sc.pb, sc.pk);
+    p.C[o] = r;
+    if (EMIT && p.em.w) emit1<FQF>(p, sc.ec, o, r, sehi, neg);
+}
+// ... over the BMT x BNT tile at (m0, n0), by the NT threads of its last-arriving block (every thread calls it)
+template <bool EMIT, bool GELU, int BMT, int BNT, int NT>
+__device__ __forceinline__ void splitk_finish_tile(const GemmArgs &p, int64_t m0, int64_t n0, int tid) {
+    const StoreCtx sc = store_ctx<EMIT>(p);
+    uint32_t sehi = 0, neg = 0;
+    if (splitk_vec(p)) {
+        // NCHW: quads of 4 consecutive pixels (rows), lanes along the rows; row-major: quads of 4 columns
+#pragma unroll 1
+        for (int e = tid; e < BMT * BNT / 4; e += NT) {
+            int64_t m, n;
+            if (p.nchw) {
+                m = m0 + 4 * (e % (BMT / 4));
+                n = n0 + e / (BMT / 4);
+            } else {
+                m = m0 + e / (BNT / 4);
+                n = n0 + 4 * (e % (BNT / 4));
+            }
+            if (m >= p.M || n >= p.N) continue;
+            const int64_t img = m / p.hw, pix = m - img * p.hw;
+            const int64_t q = p.nchw ? (img * p.N + n) * p.hw + pix : m * p.N + n;
+            splitk_finish4<EMIT, GELU, true>(p, sc, q, sehi, neg);
+        }
+    } else {
+#pragma unroll 1
+        for (int e = tid; e < BMT * BNT; e += NT) {
+            const int64_t m = m0 + (p.nchw ? e % BMT : e / BNT), n = n0 + (p.nchw ? e / BMT : e % BNT);
+            if (m >= p.M || n >= p.N) continue;
+            const int64_t img = m / p.hw, pix = m - img * p.hw;
+            splitk_finish1<EMIT, GELU, true>(p, sc, p.nchw ? (img * p.N + n) * p.hw + pix : m * p.N + n, sehi, neg);
+        }
+    }
+    if (EMIT && p.em.w) {
+        wave_max_atomic(p.em.invalid + 5, sehi);
+        wave_sign_record(p.em.invalid + 6, neg);
+    }
+}
+
+// (the kernels that keep the literal forms: the context per call, as before)
+template <bool EMIT = true, bool GELU = true>
+__device__ __forceinline__ void store_tile(const GemmArgs &p, int64_t split, int64_t m0, int64_t n0, int ty, int tx,
+                                           float (&acc)[TM][TN]) {
+    StoreCtx sc{};
+    if (p.splits <= 1) {
+        sc.pb = post_bias(p);
+        if (EMIT) sc.ec = emit_ctx(p);
+    }
+    store_tile<EMIT, GELU, false>(p, split, m0, n0, ty, tx, acc, sc);
 }
 
 }  // namespace fp8a

@@ -70,7 +70,8 @@ typedef __bf16 xm_b2 __attribute__((ext_vector_type(2)));
 
 constexpr int XM_NPAIR = 81;
 constexpr int XM_LUT_WORDS = XM_NPAIR * 8;  // [pair][m_a] u32 (s_a = +), 2.5 KiB
-constexpr uint32_t XM_ROW_SHIFT = 3, XM_ROW_MASK = 0x78u;  // A word bits 3-6: row * 8 = byte offset in a column block
+// (XM_ROW_SHIFT / XM_ROW_MASK, A word bits 3-6: fp8approx_common.h, next to the word-image emission)
+static_assert(XM_SIGN_BIT == (8u << XM_ROW_SHIFT) && XM_ROW_MASK == (15u << XM_ROW_SHIFT), "A word row field");
 constexpr int XBK = 8;                         // K-steps per staged tile
 constexpr int XM_TTK = 16 * 32 + 16;           // tile-table words per K-step: [tx 16][row 16][j 2] + bank shift
 // (XM_ZERO_WORD, the word of A = 0: fp8approx.hip, next to the word-image emission)
@@ -312,7 +313,20 @@ __global__ __launch_bounds__(256) void xm_decode_a(const GemmArgs p) {
     uint32_t sehi = 0;  // 255 - the smallest se of this thread's nonzero E5M2 words (xm_record_se)
     uint32_t neg = 0;   // the OR of this thread's wfmt-0 words (xm_record_sign)
     const DFmt fv5 = dfmt(p.E, p.Mw, bA, false);  // (wfmt 4: the v5 decode, clip_OF)
+    // fqf (uniform, one test per launch; option "fq_fast"): the fused input quantizer in its fast form
+    // and the word from the quantized value's bits (fq_apply_fast / fq_word, fp8approx_common.h) -- E4M3 /
+    // E5M2 words of a quantizer that passes the guards
+    const bool fqf = p.fq_fast && p.fqin.mx && p.wfmt == 0 && p.fqin.M == p.Mw && fq_fast_ok(fmx, fbias, p.fqin.M);
+    const FqFast fk = fqf ? fq_fast_k(fmx, fbias, p.fqin.M) : FqFast{};
+    const int kse = 254 + xm_xbias(p.Mw) - bR;
+    const bool chk = fqf && fq_word_chk(fmx, fbias, p.Mw, kse);
     auto word = [&](float v, bool &ok) {
+        if (fqf) {
+            const uint32_t w = fq_word(fq_apply_f<true>(v, fmx, fbias, p.fqin.M, p.fqin.S, fk), p.Mw, kse, chk, ok);
+            sehi = max(sehi, word_sehi(w));
+            neg |= w;
+            return w;
+        }
         if (p.fqin.mx) v = fq_apply(v, fmx, fbias, p.fqin.M, p.fqin.S);
         if (p.wfmt == 4) return v5_word_a(v, fv5);
         if (p.wfmt == 2) return tt16_word_a(v, emnA, bA, ok, win);
@@ -468,6 +482,10 @@ __global__ __launch_bounds__(256) void xm_decode_b(const GemmArgs p, int64_t kpa
     if (blockIdx.x == 0)  // the table image every GEMM workgroup copies into LDS
         for (int e = threadIdx.x; e < XM_LUT_WORDS; e += blockDim.x) const_cast<uint32_t *>(p.lutw)[e] = xm_lut_word(p.tab, e, p.Mw);
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    // the in-launch split-K sum's arrival counters: zero ahead of every GEMM launch (this kernel always
+    // precedes it in the stream / graph; no memset node, no reliance on the last arriver's reset)
+    if (p.skcnt != nullptr)
+        for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < p.sk_words; i += stride) p.skcnt[i] = 0u;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
         const int64_t k = i / hq, q = i - k * hq;
         float c[2];
@@ -585,7 +603,10 @@ template <> struct XmWaves<false, false> { static constexpr int value = XM_WAVES
 // checks and the fallback marks included -- instead of by the xm_decode_a pre-pass.  That pass
 // writes and re-reads 8 B per A element through HBM; staging-time decoding costs ~25 VALU
 // operations per element per column tile, the cheaper choice up to a few column tiles (run_gemm).
-template <int NCG, int RB, bool AF32, int XF, bool EMIT>
+// FIX: the instances that carry the in-launch split-K sum (below; E4M3 launches with p.skcnt).  They are
+// separate instantiations because the sum's few scalar values that live across the K loop spill into vector
+// lanes and cost 1-3 VGPRs: the FIX = false instances, every unsplit launch's, are compiled without it.
+template <int NCG, int RB, bool AF32, int XF, bool EMIT, bool FIX = false>
 __global__ __launch_bounds__(256, (XmWaves<AF32, EMIT>::value)) void gemm_f8mx_kernel(const GemmArgs p) {
     using Cf = XmCfg<NCG, RB>;
     constexpr int XM = XmFmt<XF>::M, XB = XmFmt<XF>::XB;
@@ -960,6 +981,7 @@ __global__ __launch_bounds__(256, (XmWaves<AF32, EMIT>::value)) void gemm_f8mx_k
     // epilogue mapping with consecutive lanes on consecutive pixels
     const float f8S = __uint_as_float((uint32_t)min(max(127 + XB - bR, 1), 254) << 23);
     float *ct = smu.ct;
+    const StoreCtx sc = p.splits == 1 ? store_ctx<EMIT>(p) : StoreCtx{};  // (a split launch stores raw partials)
     const int ety = tid & 15, etx = tid >> 4, cb = etx % (BNT / 4), sub = etx / (BNT / 4);
 #pragma unroll
     for (int h = 0; h < BMT / SR; ++h) {
@@ -979,7 +1001,34 @@ __global__ __launch_bounds__(256, (XmWaves<AF32, EMIT>::value)) void gemm_f8mx_k
         for (int i = 0; i < TM; ++i)
 #pragma unroll
             for (int j = 0; j < TN; ++j) acc[i][j] = ct[(64 * sub + ety * TM + i) * CP + cb * TN + j];
-        store_tile<EMIT, !EMIT>(p, split, m0 + SR * h + 64 * sub, n0, ety, cb, acc);  // (GELU tails: run_gemm never emits)
+        // (GELU tails: run_gemm never emits.)  One copy of the store; sc says, uniformly, whether its
+        // quantizers and words take the fast forms (option "fq_fast", every guard passed) or the literal ones
+        store_tile<EMIT, !EMIT, true>(p, split, m0 + SR * h + 64 * sub, n0, ety, cb, acc, sc);
+    }
+    // In-launch split-K sum (p.skcnt: option "splitk_fixup", E4M3).  Every split block publishes its partial
+    // tile -- stores drained, barrier, one agent-scope release by thread 0, one relaxed agent-scope ticket on
+    // the tile's counter (zeroed by xm_decode_b ahead of this launch) -- and the block that draws the last
+    // ticket takes one agent-scope acquire and finishes the tile: it sums all S slabs in split order from
+    // slab 0, its own included, and runs the final store, with splitk_reduce_kernel's own functions on the
+    // tile's elements (the same adds in the same order: the same bits).  No block waits for another.  The
+    // finish is a compact loop (a float4 per thread step), not a third copy of the unrolled store: the
+    // accumulators are dead here and its registers stay far below the K loop's.
+    if (FIX && p.skcnt != nullptr) {  // (uniform)
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this block's slab stores have left
+        __syncthreads();
+        if (tid == 0) {
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            const uint32_t t = __hip_atomic_fetch_add(p.skcnt + bid, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            const bool mine = t == (uint32_t)p.splits - 1u;
+            if (mine) {
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            }
+            ct[0] = mine ? 1.0f : 0.0f;  // "I am last", through the staging LDS (no second __shared__ object)
+        }
+        __syncthreads();
+        if (ct[0] != 0.0f) splitk_finish_tile<EMIT, !EMIT, BMT, BNT, NT>(p, m0, n0, tid);  // (uniform)
     }
     FP8A_CLK_END
 }

@@ -17,8 +17,20 @@ static void launch_shape(const GemmArgs &a, hipStream_t s) {
     const int64_t xt = ((a.M + Cf::BMT - 1) / Cf::BMT) * ((a.N + Cf::BNT - 1) / Cf::BNT);
     const dim3 g((unsigned)(xt * a.splits));
     // (the emitting instances only where this launch writes the next convolution's word image
-    // from its own store: unsplit, fp8a_conv2d_chain)
-    const bool emit = a.em.w != nullptr && a.splits == 1;
+    // from its own store: unsplit, or split with the in-launch sum -- fp8a_conv2d_chain)
+    const bool emit = a.em.w != nullptr && (a.splits == 1 || a.skcnt != nullptr);
+    if constexpr (XF == 0) {
+        if (a.skcnt != nullptr) {  // split, summed inside the launch: the FIX instances
+            if (a.af32) {
+                if (emit) gemm_f8mx_kernel<NCG, RB, true, XF, true, true><<<g, Cf::NT, 0, s>>>(a);
+                else gemm_f8mx_kernel<NCG, RB, true, XF, false, true><<<g, Cf::NT, 0, s>>>(a);
+            } else {
+                if (emit) gemm_f8mx_kernel<NCG, RB, false, XF, true, true><<<g, Cf::NT, 0, s>>>(a);
+                else gemm_f8mx_kernel<NCG, RB, false, XF, false, true><<<g, Cf::NT, 0, s>>>(a);
+            }
+            return;
+        }
+    }
     if (a.af32) {
         if (emit) gemm_f8mx_kernel<NCG, RB, true, XF, true><<<g, Cf::NT, 0, s>>>(a);
         else gemm_f8mx_kernel<NCG, RB, true, XF, false><<<g, Cf::NT, 0, s>>>(a);

@@ -132,11 +132,36 @@ int fp8a_kernel_time(double *out, int reset);
  * FP8A_TT_BAND) -- gemm_tt_kernel's band / zero wave-tile forms (0 = the general form everywhere);
  * "mse_group" (default 1; FP8A_MSE_GROUP) -- fp8a_fp8_mse_search evaluates candidates that share a
  * bias together: the unclamped quantizer once per run, the clamp per candidate (0: every candidate
- * through the whole quantizer).
+ * through the whole quantizer);
+ * "fq_fast" (default 1; FP8A_FQ_FAST) -- the matrix-core path's fake quantizers (post quantizer,
+ * emitted words, the A pre-pass's fused input quantizer, split-K reduction) as one rounding float add, and the emitted
+ * A word from the quantized value's bits, where the quantizer's constants pass a uniform guard (0: the
+ * literal forms everywhere; fp8a_fq_selfcheck compares the two over every fp32 bit pattern).
+ * "splitk" (default 0 = chosen per launch; FP8A_SPLITK) -- the split count along K forced (tests, sweeps);
+ * "splitk_fixup" (default 0; FP8A_SPLITK_FIXUP) -- a split E4M3 matrix-core launch sums its partial tiles
+ * inside the launch (the tile's last-arriving block, one counter word per tile in the workspace after the
+ * partials, zeroed by the launch's own pre-pass) instead of in a separate reduction kernel (0, the default:
+ * the in-launch sum measured slower).
  * All of these change the schedule only: the outputs are bit-identical.  Returns the previous value, or FP8A_EINVAL
  * for an unknown name.  Not synchronised with launches in flight on other threads.
  */
 int fp8a_set_option(const char *name, int value);
+
+/*
+ * Self-check of the "fq_fast" forms against the literal ones on the device, over the fp32 bit patterns
+ * first .. first + count - 1 (as inputs v of the per-tensor quantizer (maxval, E, M, sign_bits)), compared
+ * as bits.  mode 0: fq_apply_fast against fq_apply_lit (both after the clamp).  mode 1: the A word formed
+ * from the quantized value's bits (mantissa width M = 3 or 2, result bias bR) against
+ * xm_word_a(fq_apply_lit(..)), the word and its ok bit.  mode 2: as 1 with the per-element window test
+ * forced on.  A quantizer outside the guard compares the literal form with itself (what the kernels
+ * then run).  out (host): [0] mismatches, [1] the lowest mismatching pattern (all ones: none),
+ * [2] bit 0: the guard passed (the fast forms ran), bit 1: the word's window test ran per element.
+ * A test hook, not a production entry: every call allocates and frees a few device words and
+ * synchronises the stream before it returns (its host-side buffers live only that long), so it must
+ * not be called while the stream is being captured into a graph.
+ */
+int fp8a_fq_selfcheck(float maxval, int E, int M, int sign_bits, int mode, int bR, uint64_t first, uint64_t count,
+                      uint64_t *out, fp8a_stream_t stream);
 
 /*
  * The exact (non-approx) product on the matrix core -- the reference's `x @ y` of FP8-quantized

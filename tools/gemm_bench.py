@@ -7,6 +7,11 @@ Times fp8a_conv2d (implicit GEMM) with HIP events on the current stream, random 
 operands of realistic magnitude; prints one JSON line per layer and a total.
 --nonneg-a: activations >= 0, as after a ReLU (gemm_f8mx_kernel then builds the positive table rows
 only; FP8A_XM_SIGN_ROWS=0 for the full build on the same data).  FP8A_LIB_PATH selects an alternative build of libfp8approx.so (A/B of kernel variants).
+--emit: the layer as ResNet-18 runs it inside a block -- BN + ReLU in the store and the next convolution's word
+image emitted (gemm_f8mx_kernel's emitting instance) -- for the store's A/B against the raw-store diagnostic
+build (lib/libfp8approx_rawstore.so, -DFP8A_RAW_STORE_DIAG=1: --build-diag makes it and the clock-stamp build).
+With a clock-stamp build (FP8A_LIB_PATH=.../libfp8approx_clk.so) each line also carries the clock the kernel
+held and its products per SIMD-cycle (MACs / (time x clock x 4 SIMDs x CUs)).
 """
 import argparse
 import json
@@ -46,7 +51,14 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--layers", default="")
     ap.add_argument("--nonneg-a", action="store_true")
+    ap.add_argument("--emit", action="store_true")
+    ap.add_argument("--build-diag", action="store_true")
     args = ap.parse_args()
+    if args.build_diag:  # (host only)
+        from fp8_quantization_amd import build_native as bn
+        for name, d in (("rawstore", "-DFP8A_RAW_STORE_DIAG=1"), ("clk", "-DFP8A_CLOCK_STAMP=1")):
+            print(bn.build(force=True, out=os.path.join(bn.OUT_DIR, f"libfp8approx_{name}.so"), extra=bn.EXTRA + [d]))
+        return
     import fp8_quantization_amd as fa
     from fp8_quantization_amd.error_tables import get_error_table_NN
     dev = "cuda:0"
@@ -69,7 +81,18 @@ def main():
         w = grid(rng, E, M, (cout, cin, k, k), bB, 0.0).to(dev)
         bW = torch.full((cout,), bB, dtype=torch.int32, device=dev)
         args_ = dict(flags=fl, stride=(s, s), padding=(p, p))
+        if args.emit:
+            from fp8_quantization_amd.approx_ops import bn_act_epilogue, new_word_image
+            ho = (h + 2 * p - k) // s + 1
+            ep = bn_act_epilogue(torch.zeros(cout), torch.ones(cout), torch.ones(cout), torch.zeros(cout), 0.0,
+                                 torch.nn.ReLU())
+            img = new_word_image(args.batch, cout, ho, ho, 1, 1, dev)
+            nq = (torch.tensor([4.0], device=dev), 8, M, 1)
+            nbR = torch.tensor([bR], dtype=torch.int32, device=dev)
+            args_.update(epilogue=(ep[0].to(dev),) + tuple(ep[1:]), chain=(None, (img, (1, 1), nq, nbR, M)))
+        clk = "clk" in os.path.basename(os.environ.get("FP8A_LIB_PATH", ""))
         y = fa.approx_conv2d(x, w, E, M, bA, bW, bR, tab, **args_)
+        y = y[0] if isinstance(y, tuple) else y
         torch.cuda.synchronize()
         ts = []
         for _ in range(args.reps):
@@ -80,11 +103,21 @@ def main():
             b.synchronize()
             ts.append(a.elapsed_time(b) / 1e3)
         t = float(np.median(ts))
+        extra = {}
+        if clk:  # the clock over one more launch, and the kernel's products per SIMD-cycle at it
+            from fp8_quantization_amd import _lib
+            _lib.clock_stats(reset=True)
+            fa.approx_conv2d(x, w, E, M, bA, bW, bR, tab, **args_)
+            st = _lib.clock_stats(reset=True)
+            cus = torch.cuda.get_device_properties(0).multi_processor_count
+            extra = dict(ghz=st["ghz"], workgroups=st["workgroups"])
         macs = y.shape[0] * y.shape[2] * y.shape[3] * cout * cin * k * k
         tot_t += t * COUNT[name]
         tot_mac += macs * COUNT[name]
+        if extra.get("ghz"):
+            extra["products_per_simd_cycle"] = macs / (t * extra["ghz"] * 1e9 * 4 * cus)
         print(json.dumps(dict(layer=name, M=y.shape[0] * y.shape[2] * y.shape[3], K=cin * k * k, N=cout,
-                              ms=t * 1e3, tmacs=macs / t / 1e12)), flush=True)
+                              ms=t * 1e3, tmacs=macs / t / 1e12, **extra)), flush=True)
     print(json.dumps(dict(total_ms=tot_t * 1e3, tmacs=tot_mac / tot_t / 1e12, mode=args.mode,
                           lib=os.environ.get("FP8A_LIB_PATH", "default"))), flush=True)
 
