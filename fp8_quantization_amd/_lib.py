@@ -27,7 +27,8 @@ SYMBOLS = ("fp8a_version", "fp8a_last_error", "fp8a_fallback_stats", "fp8a_path_
            "fp8a_word_image_bytes", "fp8a_word_image_init", "fp8a_conv2d_chain", "fp8a_conv2d_wants_image",
            "fp8a_flag_arena_slot_bytes",
            "fp8a_check_workspace_size", "fp8a_matmul_check", "fp8a_conv2d_check_workspace_size", "fp8a_conv2d_check",
-           "fp8a_fp8_mse_workspace_size", "fp8a_fp8_mse_search", "fp8a_fq_selfcheck")
+           "fp8a_fp8_mse_workspace_size", "fp8a_fp8_mse_search", "fp8a_fq_selfcheck",
+           "fp8a_bn_train_workspace_size", "fp8a_bn_train")
 
 _lib = None
 
@@ -110,6 +111,8 @@ def load():
         "fp8a_fp8_mse_workspace_size": ([I64, I64, I, I], SZ),
         "fp8a_fp8_mse_search": ([P, I64, I64, P, I, P, I, I, I, P, P, SZ, P], I),
         "fp8a_fq_selfcheck": ([F, I, I, I, I, I, ctypes.c_uint64, ctypes.c_uint64, P, P], I),
+        "fp8a_bn_train_workspace_size": ([I64, I64, I64], SZ),
+        "fp8a_bn_train": ([P, P, I64, I64, I64, P, P, F, F, P, P, P, P, P, I, F, F, P, I, I, I, P, P, P, SZ, P], I),
     }
     for name, (args, res) in sig.items():
         f = getattr(L, name)

@@ -25,7 +25,7 @@ __all__ = ["custom_matmul_vectorize", "approx_matmul", "approx_matmul_block", "a
            "quant_to_fp_any_vectorize_torch", "float_to_fpany_absint_torch", "get_error_table_NN",
            "make_flags", "make_flags_v5", "fp8_fake_quantize", "bn_act_epilogue", "dense_format", "dense_matmul",
            "dense_conv2d", "grouped_conv2d", "dense_conv2d_fused", "approx_matmul_check", "approx_conv2d_check",
-           "CheckStats", "format_self_check", "SELF_CHECK_LABELS", "fp8_mse_losses"]
+           "CheckStats", "format_self_check", "SELF_CHECK_LABELS", "fp8_mse_losses", "bn_train"]
 
 
 def make_flags(with_approx=True, with_s2nn2s_opt=False, quant_btw_mult_accu=True, golden_clip_OF=False,
@@ -829,16 +829,10 @@ def bn_act_epilogue(running_mean, running_var, gamma, beta, eps, activation=None
     channel (scale = gamma / sqrt(var + eps), shift = beta - mean * scale, the transform ATen's
     eval batch norm applies) and ReLU / ReLU6 / Hardtanh as a clamp.  Returns None when the
     activation is not a clamp (the caller then runs it unfused)."""
-    if activation is None:
-        act, lo, hi = 0, 0.0, 0.0
-    elif type(activation) is nn.ReLU:
-        act, lo, hi = 1, 0.0, float("inf")
-    elif type(activation) is nn.ReLU6:
-        act, lo, hi = 1, 0.0, 6.0
-    elif type(activation) is nn.Hardtanh:
-        act, lo, hi = 1, float(activation.min_val), float(activation.max_val)
-    else:
+    clamp = _clamp_of(activation)
+    if clamp is None:
         return None
+    act, lo, hi = clamp
     with torch.no_grad():
         invstd = 1.0 / torch.sqrt(running_var.float() + eps)
         scale = invstd * gamma.float() if gamma is not None else invstd
@@ -846,6 +840,99 @@ def bn_act_epilogue(running_mean, running_var, gamma, beta, eps, activation=None
         if beta is not None:
             shift = shift + beta.float()
         return torch.stack((scale, shift), dim=1).contiguous(), act, lo, hi
+
+
+def _clamp_of(activation):
+    """bn_act_epilogue's activation -> (act, lo, hi) mapping; None when the activation is not a clamp."""
+    if activation is None:
+        return 0, 0.0, 0.0
+    if type(activation) is nn.ReLU:
+        return 1, 0.0, float("inf")
+    if type(activation) is nn.ReLU6:
+        return 1, 0.0, 6.0
+    if type(activation) is nn.Hardtanh:
+        return 1, float(activation.min_val), float(activation.max_val)
+    return None
+
+
+def bn_train(x, gamma, beta, running_mean, running_var, momentum, eps, activation=None, out_quantizer=None,
+             out=None, stats_only=False):
+    """Training-mode batch norm over dim 1 of x ([N, C, ...] or [B, F]) on the deterministic kernels of
+    csrc/bn_train.h (fp8a_bn_train): batch statistics from shifted double sums in a fixed order, the
+    running buffers updated IN PLACE (None: not updated), then y = clamp(x * scale + shift) and the
+    optional per-tensor output quantizer ``(maxval, n_bits, mantissa_bits, sign_bits)``, bit for bit
+    fp8_fake_quantize on the unquantized result.
+
+    activation: None / ReLU / ReLU6 / Hardtanh as in bn_act_epilogue; any other activation returns
+    None (the caller runs batch norm without it and the activation afterwards).  out: the output
+    tensor (may be x: in place); stats_only: no output is written and y is None.
+
+    Returns (y, save_mean, save_var [biased], scale_shift [C, 2], q_bias or None)."""
+    L = _lib.load()
+    clamp = _clamp_of(activation)
+    if clamp is None:
+        return None
+    act, lo, hi = clamp
+    if not x.is_cuda:
+        raise RuntimeError("fp8approx kernels need HIP device tensors (no CPU fallback)")
+    if x.dim() < 2:
+        raise ValueError(f"bn_train: expected at least 2 dims, got {x.dim()}")
+    if x.dtype != torch.float32 or not x.is_contiguous():
+        if out is x:
+            raise AssertionError("bn_train: in place needs a contiguous float32 tensor")
+        x = _as_f32(x).contiguous()
+    dev = x.device
+    N, C = x.shape[0], x.shape[1]
+    inner = x.numel() // max(N * C, 1)
+    if N == 0 or C == 0 or inner == 0:
+        raise AssertionError("bn_train: empty input")
+    if N * inner == 1:
+        raise ValueError(f"Expected more than 1 value per channel when training, got input size {tuple(x.shape)}")
+
+    def par(t, what):
+        if t is None:
+            return None
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != C or t.device != dev:
+            raise AssertionError(f"bn_train: {what} must be a contiguous float32 [{C}] tensor on {dev}")
+        return t.detach()
+    gamma, beta = par(gamma, "gamma"), par(beta, "beta")
+    running_mean, running_var = par(running_mean, "running_mean"), par(running_var, "running_var")
+    if stats_only:
+        y = None
+    elif out is None:
+        y = torch.empty_like(x)
+    else:
+        if out.shape != x.shape or out.dtype != torch.float32 or not out.is_contiguous() or out.device != dev:
+            raise AssertionError("bn_train: out must match x (contiguous float32)")
+        y = out
+    save_mean = torch.empty(C, dtype=torch.float32, device=dev)
+    save_var = torch.empty(C, dtype=torch.float32, device=dev)
+    ss = torch.empty((C, 2), dtype=torch.float32, device=dev)
+    mx, nb, mb, sb = (None, 0, 0, 0)
+    qb = qib = None
+    if out_quantizer is not None:
+        if y is None:
+            raise AssertionError("bn_train: an output quantizer needs an output")
+        mx, nb, mb, sb = _quantizer_args(out_quantizer)
+        if mx.device != dev:
+            mx = mx.to(dev)
+        qb = torch.empty(1, dtype=torch.float32, device=dev)
+        qib = torch.empty(1, dtype=torch.int32, device=dev)
+    nbytes = int(L.fp8a_bn_train_workspace_size(N, C, inner))
+    ws = _workspace(dev, nbytes)
+    rc = L.fp8a_bn_train(_lib.dev_ptr(x), _lib.dev_ptr(y), N, C, inner, _lib.dev_ptr(gamma), _lib.dev_ptr(beta),
+                         float(eps), float(momentum), _lib.dev_ptr(running_mean), _lib.dev_ptr(running_var),
+                         _lib.dev_ptr(save_mean), _lib.dev_ptr(save_var), _lib.dev_ptr(ss), act, lo, hi,
+                         _lib.dev_ptr(mx), nb, mb, sb, _lib.dev_ptr(qb), _lib.dev_ptr(qib), _lib.dev_ptr(ws), nbytes,
+                         _lib.stream_ptr(dev))
+    _lib.check(rc, "fp8a_bn_train")
+    if running_mean is not None:  # the kernel wrote them: caches keyed on _version (the eval epilogue) see it
+        torch.autograd.graph.increment_version(running_mean)
+    if running_var is not None:
+        torch.autograd.graph.increment_version(running_var)
+    if qb is not None:
+        qb._fp8a_i32 = qib
+    return y, save_mean, save_var, ss, qb
 
 
 # ----------------------------------------------------------------------------------- FP8 fake quant

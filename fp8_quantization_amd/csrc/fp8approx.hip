@@ -30,6 +30,7 @@
 #include "conv_tbx.h"
 #include "gemm_check.h"
 #include "fq_mse.h"
+#include "bn_train.h"
 
 // (defined with C linkage below; run_gemm launches it too)
 extern "C" __global__ void fq_bias_kernel(fp8a::FqIn fq, float *bias_out, int32_t *ibias_out);
@@ -2767,6 +2768,51 @@ int fp8a_fp8_mse_search(const float *x, int64_t rows, int64_t inner, const float
     a.sse = sse;
     launch_mse(a, g_opt_mse_group != 0, (hipStream_t)stream);
     return hip_check("fp8a_fp8_mse_search");
+}
+
+// Training-mode batch norm (bn_train.h).  Workspace: the (S, Q) double pairs [C][parts].
+static bool bn_shape_ok(int64_t N, int64_t C, int64_t inner) {
+    return N > 0 && C > 0 && inner > 0 && inner < ((int64_t)1 << 31) - BN_TILE && C <= (int64_t)1 << 24 &&
+           N <= ((int64_t)1 << 40) / inner && N * inner <= ((int64_t)1 << 60) / C;
+}
+
+size_t fp8a_bn_train_workspace_size(int64_t N, int64_t C, int64_t inner) {
+    if (!bn_shape_ok(N, C, inner)) return 0;
+    return (size_t)C * (size_t)bn_parts(N, C, inner) * sizeof(double2);
+}
+
+int fp8a_bn_train(const float *x, float *y, int64_t N, int64_t C, int64_t inner, const float *gamma,
+                  const float *beta, float eps, float momentum, float *running_mean, float *running_var,
+                  float *save_mean, float *save_var, float *scale_shift, int act, float lo, float hi,
+                  const float *q_maxval, int q_n_bits, int q_mbits, int q_sign_bits, float *q_bias, int32_t *q_ibias,
+                  void *workspace, size_t workspace_bytes, fp8a_stream_t stream) {
+    if (!bn_shape_ok(N, C, inner)) return fail(FP8A_EINVAL, "bad batch-norm shape");
+    if (N * inner == 1)  // torch: ValueError
+        return fail(FP8A_EFORMAT, "Expected more than 1 value per channel when training");
+    if (act != 0 && act != 1) return fail(FP8A_EINVAL, "bn_train: act is 0 or 1");
+    BnArgs a{};
+    if (q_maxval) {
+        const int qE = q_n_bits - q_sign_bits - q_mbits;
+        if (q_mbits < 1 || qE < 1 || q_sign_bits < 0 || q_sign_bits > 1) return fail(FP8A_EFORMAT, "bad FP8 quantizer format");
+        if (y == nullptr) return fail(FP8A_EINVAL, "bn_train: an output quantizer needs an output");
+        a.q = FqIn{q_maxval, qE, q_mbits, q_sign_bits};
+    }
+    if (workspace_bytes < fp8a_bn_train_workspace_size(N, C, inner)) return fail(FP8A_EINVAL, "workspace too small");
+    if (x == nullptr || save_mean == nullptr || save_var == nullptr || scale_shift == nullptr || workspace == nullptr ||
+        ((uintptr_t)workspace & 15) != 0 || ((uintptr_t)scale_shift & 7) != 0)
+        return fail(FP8A_EINVAL, "null or misaligned pointer");
+    a.x = x; a.y = y; a.N = N; a.C = C; a.inner = inner; a.n = N * inner;
+    a.parts = bn_parts(N, C, inner);
+    a.part = static_cast<double2 *>(workspace);
+    a.gamma = gamma; a.beta = beta; a.eps = eps; a.momentum = momentum;
+    a.running_mean = running_mean; a.running_var = running_var;
+    a.save_mean = save_mean; a.save_var = save_var;
+    a.ss = reinterpret_cast<float2 *>(scale_shift);
+    a.act = act; a.lo = lo; a.hi = hi;
+    a.q_bias = q_bias; a.q_ibias = q_ibias;
+    a.vec = inner % 4 == 0 && (((uintptr_t)x | (uintptr_t)y) & 15) == 0;
+    launch_bn_train(a, (hipStream_t)stream);
+    return hip_check("fp8a_bn_train");
 }
 
 // The config-1 layer (approx_flag off) in one launch family: fq_in on the loaded input, the exact

@@ -1,7 +1,7 @@
 // fp8approx_common.h -- definitions shared by the translation units of libfp8approx.so
 // (fp8approx.hip: the C-ABI, the host dispatch and the small kernels; k_fast.hip, k_f8mx.hip,
 // k_tt.hip, k_v5.hip: the GEMM kernel families; k_check.hip: the fused self-check; k_mse.hip: the MSE
-// range search -- compiled in parallel by build_native.py).
+// range search; k_bn.hip: training-mode batch norm -- compiled in parallel by build_native.py).
 // Launch arguments, operand decode, the shared epilogue (store_tile) and the word-image emission.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -51,4 +51,9 @@ size_t check_part_bytes(int64_t parts);
 struct MseArgs;
 void launch_mse(const MseArgs &a, bool group, hipStream_t s);
 
+// k_bn.hip: training-mode batch norm (bn_train.h) -- the statistics kernel (by inner: lanes along inner
+// or along channels), the per-channel finalize and, with a.y, the apply kernel.
+struct BnArgs;
+void launch_bn_train(const BnArgs &a, hipStream_t s);
+
 }  // namespace fp8a

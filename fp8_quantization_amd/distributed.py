@@ -135,6 +135,30 @@ def broadcast_quant_state(model, src=0):
             off += cn
 
 
+def allreduce_bn_sums(sums, batch_count, group=None):
+    """The BN re-estimation's collective (bn_reestimate.reestimate_bn_stats): every layer's summed
+    per-batch statistics -- `sums`, a list of float32 tensors, the same shapes on every rank -- and
+    this rank's batch count packed into ONE flat float32 buffer, all-reduced once (SUM) and copied
+    back in place.  Returns the total batch count.  The all-reduce leaves every rank the same bytes,
+    so the division that follows does too.  (A batch count is exact in float32 below 2^24.)"""
+    if not (dist.is_available() and dist.is_initialized()):
+        return batch_count
+    if dist.get_world_size(group) == 1:
+        return batch_count
+    dev = torch.device("cuda", torch.cuda.current_device()) if dist.get_backend(group) == "nccl" \
+        else torch.device("cpu")
+    with torch.no_grad():
+        flat = torch.cat([t.detach().reshape(-1).to(device=dev, dtype=torch.float32) for t in sums] +
+                         [torch.tensor([float(batch_count)], dtype=torch.float32, device=dev)])
+        dist.all_reduce(flat, op=dist.ReduceOp.SUM, group=group)
+        off = 0
+        for t in sums:
+            n = t.numel()
+            t.copy_(flat[off:off + n].view(t.shape))
+            off += n
+        return int(round(float(flat[off])))
+
+
 def calibrate_on_rank0(model, batches, src=0, quantized=False):
     """The reference's calibration (image_net.py:76-91: estimate_ranges, forward the
     calibration batches, fix_ranges) run by rank `src` alone; every other rank takes rank

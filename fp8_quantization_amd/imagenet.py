@@ -17,8 +17,15 @@ Restates image_net.py:59-202 of the reference without click / ignite / torchvisi
     cross-entropy loss;
   * multi-GPU: one process per GPU; rank 0 calibrates, its FP8 ranges are broadcast, the
     evaluated batches are sharded over ranks and the logits all-gathered (RCCL) for scoring.
-BN re-estimation (a QAT utility that needs the train split) is not run: the reference's
-`--no-reestimate-bn-stats` protocol.
+  * BN re-estimation (`--reestimate-bn-stats`, image_net.py:165-168 and utils/qat_utils.py:60-108):
+    after calibration, `--bn-batches` train batches (default: the reference's int(0.002 * number of
+    train batches)) run through the model with every BN-fused layer in training mode at momentum 1,
+    and the layers' running statistics become the mean of the per-batch ones
+    (bn_reestimate.reestimate_bn_stats, on the deterministic kernels of csrc/bn_train.h; sharded
+    over ranks with one all-reduce).  The reference's default is to re-estimate; here the default
+    is `--no-reestimate-bn-stats`, so a plain run computes what it always did.  The batches are the
+    FIRST N of the train loader in loader order, where the reference draws them from its shuffled
+    train loader: a fixed set makes two runs (and any number of ranks) give identical statistics.
 Without a dataset (`--synthetic N`), random images / labels exercise the same path.
 """
 import argparse
@@ -164,6 +171,12 @@ def parse(argv=None):
     ap.add_argument("--act-quant-method", default="allminmax", choices=methods)
     ap.add_argument("--fp8-mse-include-mantissa-bits", action="store_true",
                     help="the MSE estimator also votes on the mantissa width")
+    ap.add_argument("--reestimate-bn-stats", action=argparse.BooleanOptionalAction, default=False,
+                    help="re-estimate the BN statistics on train batches before evaluating "
+                         "(the reference's default is yes; here the default is no)")
+    ap.add_argument("--bn-batches", type=int, default=None,
+                    help="train batches of the BN re-estimation (default: int(0.002 * number of train batches), "
+                         "the reference's)")
     ap.add_argument("--output", default=None, help="also write the result JSON here")
     return ap.parse_args(argv)
 
@@ -186,6 +199,16 @@ def validate(model, val, train, args, dev, rank=0, ws=1, source=""):
             if i >= args.num_est_batches - 1:
                 break
     calibrate_on_rank0(model, cal_batches())
+    bn_batches = None
+    if args.reestimate_bn_stats:
+        from .bn_reestimate import reestimate_bn_stats
+        bn_batches = bn_batch_count(args, train)
+        if bn_batches < 1:
+            raise ValueError(f"--reestimate-bn-stats: int(0.002 * {_n_batches(train, args.batch_size)} train batches)"
+                             " = 0 batches; give --bn-batches")
+        # the first N train batches in loader order (every rank walks them and runs its own)
+        reestimate_bn_stats(model, _loader(train, args.batch_size, args.num_workers, list(range(
+            min(len(train), bn_batches * args.batch_size)))), num_batches=bn_batches)
 
     # evaluated batches (mini_test or all), sharded over ranks; each global step every rank
     # runs one batch (or none) and the packed logits / labels are all-gathered once
@@ -224,13 +247,24 @@ def validate(model, val, train, args, dev, rank=0, ws=1, source=""):
         return None
     return dict(arch=args.arch, data=source, images=seen, top_1_accuracy=correct1 / max(1, seen),
                 top_5_accuracy=correct5 / max(1, seen), loss=loss_sum / max(1, seen), images_per_s=seen / elapsed,
-                n_gpus=ws, evaluate_param="mini_test" if args.mini_test else "full_test")
+                n_gpus=ws, evaluate_param="mini_test" if args.mini_test else "full_test",
+                reestimate_bn_stats=bool(args.reestimate_bn_stats), bn_batches=bn_batches)
+
+
+def _n_batches(ds, batch):
+    return (len(ds) + batch - 1) // batch
+
+
+def bn_batch_count(args, train):
+    """--bn-batches, or the reference's int(0.002 * len(train_loader)) (image_net.py:167)."""
+    return args.bn_batches if args.bn_batches is not None else int(0.002 * _n_batches(train, args.batch_size))
 
 
 def datasets(args):
     if args.synthetic:
         val = SyntheticImages(args.synthetic, args.image_size)
-        train = SyntheticImages(args.batch_size * args.num_est_batches, args.image_size, seed=1)
+        n_train = max(args.num_est_batches, (args.bn_batches or 0) if args.reestimate_bn_stats else 0)
+        train = SyntheticImages(args.batch_size * n_train, args.image_size, seed=1)
         return val, train, f"synthetic ({args.synthetic} random images)"
     val = NumericImageFolder(os.path.join(args.images_dir, "val"), args.image_size)
     tdir = os.path.join(args.images_dir, "train")

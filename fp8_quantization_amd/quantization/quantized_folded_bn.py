@@ -14,6 +14,11 @@ Config-1 form (round 4): with approx_flag off and original_quantize_res (BASELIN
 PTQ run) the whole layer -- input quantizer, exact product, res quantizer, eval batch norm, clamp,
 output quantizer -- runs as one fused exact convolution (fp8a_dense_conv2d_fused), leaving each
 quantizer the custom_bias its own forward would.
+
+Training mode (the BN re-estimation protocol, bn_reestimate.py): the fused stores above do not run
+(they need the eval statistics); with ``fuse_bn_train`` (default on, FP8A_FUSE_BN_TRAIN=0 turns it
+off) F.batch_norm(training=True), a clamp activation and the layer's own output quantizer run as
+approx_ops.bn_train -- statistics that are identical bit for bit run to run, which MIOpen's are not.
 """
 import os
 
@@ -27,6 +32,10 @@ from .hijacker import QuantizationHijacker
 
 class BNFusedHijacker(QuantizationHijacker):
     fuse_bn_act = os.environ.get("FP8A_FUSE_BN", "1") != "0"
+    # training mode (BN re-estimation, bn_reestimate.py): the batch statistics, the running-buffer
+    # update, the normalization, a clamp activation and the layer's own output quantizer on the
+    # deterministic kernels of csrc/bn_train.h; False / FP8A_FUSE_BN_TRAIN=0: F.batch_norm as before
+    fuse_bn_train = os.environ.get("FP8A_FUSE_BN_TRAIN", "1") != "0"
 
     def __init__(self, *args, **kwargs):
         kwargs.pop("bias", None)
@@ -167,9 +176,39 @@ class BNFusedHijacker(QuantizationHijacker):
             res, qa = self._core(x, epilogue=ep, post=post, chain=chain)
             return self._epilogue(res, qa, activation_done=True)
         res, qa = self._core(x)
+        if self._bn_train_fused(res):
+            return self._forward_bn_train(res, qa)
         res = F.batch_norm(res, self.running_mean, self.running_var, self.gamma, self.beta, self.training,
                            self.momentum, self.epsilon)
         return self._epilogue(res, qa)
+
+    def _bn_train_fused(self, res):
+        """Whether the training-mode batch norm of this forward runs on approx_ops.bn_train: training
+        mode, a HIP tensor, a float momentum (None is torch's cumulative average: not modelled) and no
+        gradient to record (the kernels have no backward)."""
+        return (self.fuse_bn_train and self.training and res.is_cuda and isinstance(self.momentum, float)
+                and res.dim() >= 2 and not (torch.is_grad_enabled() and res.requires_grad))
+
+    def _forward_bn_train(self, res, qa):
+        """F.batch_norm(training) + activation (+ this layer's own output quantizer) as bn_train, in
+        place on the product.  A clamp activation and the output quantizer (under
+        _own_output_quantizer's conditions) go into the apply kernel; any other activation runs after
+        it, unfused, and the quantizer after that."""
+        from ..approx_ops import bn_train
+        inplace = res.dtype == torch.float32 and res.is_contiguous()
+        own = None
+        if isinstance(self, _ConvNd):  # (the store's conditions speak of channels per group)
+            own = self._own_output_quantizer()
+        qt = None if own is None else (own.maxval, own.n_bits, own._mbits_int, own.sign_bits)
+        args = (res.detach(), self.gamma, self.beta, self.running_mean, self.running_var, self.momentum, self.epsilon)
+        r = bn_train(*args, activation=self.activation_function, out_quantizer=qt, out=res.detach() if inplace else None)
+        if r is None:  # not a clamp: batch norm alone, then the reference's order
+            y = bn_train(*args, out=res.detach() if inplace else None)[0]
+            return self._epilogue(y, qa)
+        if own is not None:
+            own.custom_bias = r[4]  # what the quantizer's own forward leaves (fp8_quantizer.py)
+            return r[0]
+        return self._epilogue(r[0], qa, activation_done=True)
 
     def get_bn_dim(self):
         if isinstance(self, nn.Linear):

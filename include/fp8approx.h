@@ -582,6 +582,32 @@ int fp8a_fp8_mse_search(const float *x, int64_t rows, int64_t inner, const float
                         const int32_t *mbits, int n_mbits, int n_bits, int sign_bits, double *sse,
                         void *workspace, size_t workspace_bytes, fp8a_stream_t stream);
 
+/*
+ * Training-mode batch norm on deterministic kernels (csrc/bn_train.h): x viewed as [N][C][inner]
+ * (fp32, contiguous; inner = H * W for a convolution, 1 for a linear layer's [B, F]), n = N * inner
+ * values per channel.  Per channel, from shifted double sums (shift = the channel's first value):
+ *   save_mean, save_var (BIASED variance, the one that normalizes), fp32 [C];
+ *   scale_shift [C][2]: scale = gamma / sqrt(var + eps), shift = beta - mean * scale, each computed
+ *   in double and rounded to fp32 once (gamma NULL: 1, beta NULL: 0);
+ *   running_mean = (1 - momentum) running_mean + momentum mean, running_var likewise with the
+ *   unbiased variance var n / (n - 1), in double, rounded once (NULL: not updated).
+ * y != NULL: y = x * scale + shift as one fused multiply-add (fp8a_conv2d_bn_act's form), then the
+ * clamp [lo, hi] when act = 1, then -- q_maxval != NULL (device float [1]) -- fp8a_fp8_quantize's
+ * arithmetic bit for bit, its bias written to q_bias (float [1]) / q_ibias (int32 [1]) when not NULL.
+ * y may be x.  y == NULL: statistics only.  The reduction order is fixed and its split depends on the
+ * shape alone: two calls return identical bytes.  FP8A_EFORMAT for n == 1 (torch's ValueError
+ * "Expected more than 1 value per channel when training") and a bad quantizer format; FP8A_EINVAL
+ * for empty extents, null pointers, a workspace that is too small or not 16-byte aligned.
+ * fp8a_bn_train_workspace_size is host-only and returns 0 for bad arguments.
+ */
+size_t fp8a_bn_train_workspace_size(int64_t N, int64_t C, int64_t inner);
+int fp8a_bn_train(const float *x, float *y, int64_t N, int64_t C, int64_t inner,
+                  const float *gamma, const float *beta, float eps, float momentum,
+                  float *running_mean, float *running_var, float *save_mean, float *save_var,
+                  float *scale_shift, int act, float lo, float hi, const float *q_maxval,
+                  int q_n_bits, int q_mbits, int q_sign_bits, float *q_bias, int32_t *q_ibias,
+                  void *workspace, size_t workspace_bytes, fp8a_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
