@@ -571,6 +571,10 @@ static int g_opt_xm_ncg = getenv("FP8A_XM_NCG") ? atoi(getenv("FP8A_XM_NCG")) : 
 // "xm_sign_rows": gemm_f8mx_kernel builds the negative-sign half of its tile table only for launches
 // whose A words address it (1, the default); 0: always both halves (the same bits, for A/B runs)
 static int g_opt_xm_sign_rows = getenv("FP8A_XM_SIGN_ROWS") ? atoi(getenv("FP8A_XM_SIGN_ROWS")) : 1;
+// "xm_pipe": gemm_f8mx_kernel's word-staged E4M3 / E5M2 launches run the instances whose K loop issues
+// its LDS reads one stage ahead of the conversions that use them (1, the default; gemm_f8mx.h PIPE,
+// DESIGN.md 3x); 0: the loop without it (the same conversions and MFMAs in the same order: the same bits)
+static int g_opt_xm_pipe = getenv("FP8A_XM_PIPE") ? atoi(getenv("FP8A_XM_PIPE")) != 0 : 1;
 // "fq_fast": the matrix-core path's fake quantizers (the post quantizer, the emitted words' quantizer,
 // the fused input quantizer of the A pre-pass, the split-K reduction; not the fp32 staging) run
 // fq_apply_fast and the emitted word is formed from the quantized value's bits (fq_word), wherever the
@@ -1111,6 +1115,7 @@ static int run_gemm(GemmArgs &a, const int32_t *table, void *ws, size_t ws_bytes
             if (a.wfmt == 1 && !g_opt_tt_band) a.ebr = nullptr;  // (gemm_tt_kernel: no band test)
             a.xncg = tt ? 4 : xm_ncg(a.N);
             a.xm_signs = g_opt_xm_sign_rows;
+            a.xm_pipe = g_opt_xm_pipe;
             // the in-launch split-K sum: the E4M3 matrix-core kernel (the E5M2 form's halved-block rerun
             // writes a tile's partials a second time, after its counter has run out: it keeps the reduce pass)
             a.skcnt = nullptr;
@@ -1511,6 +1516,11 @@ int fp8a_set_option(const char *name, int value) {
     if (strcmp(name, "xm_sign_rows") == 0) {
         const int old = g_opt_xm_sign_rows;
         g_opt_xm_sign_rows = value != 0;
+        return old;
+    }
+    if (strcmp(name, "xm_pipe") == 0) {
+        const int old = g_opt_xm_pipe;
+        g_opt_xm_pipe = value != 0;
         return old;
     }
     if (strcmp(name, "splitk_fixup") == 0) {

@@ -606,8 +606,35 @@ template <> struct XmWaves<false, false> { static constexpr int value = XM_WAVES
 // FIX: the instances that carry the in-launch split-K sum (below; E4M3 launches with p.skcnt).  They are
 // separate instantiations because the sum's few scalar values that live across the K loop spill into vector
 // lanes and cost 1-3 VGPRs: the FIX = false instances, every unsplit launch's, are compiled without it.
-template <int NCG, int RB, bool AF32, int XF, bool EMIT, bool FIX = false>
+// PIPE (option "xm_pipe"; the word-staged E4M3 / E5M2 instances): the math loop reads LDS one
+// stage ahead of the conversions, inside the wave.  1: block b + 1's A word pair is read before block b's
+// conversions (block 0's right after the barrier).  2: also the four table reads of the next K-step -- (b, 1)
+// after (b, 0), (b + 1, 0) after (b, 1) -- go out, into the other of two 4 x u64 buffers, before the eight
+// conversions of the current one, so the wait in front of a conversion is lgkmcnt(4) or looser instead of a
+// drained queue.  Nothing is read across the tile's closing barrier (the next tile's table and words do not
+// exist before it): the pipeline fills after one barrier and drains before the next.  Per 16-row block the
+// same conversions in the same element order and one MFMA per block in block order: every accumulator takes
+// the same adds in the same order as with PIPE = 0, the same bits.
+// XmPipe: the form an instance takes, by its registers (DESIGN.md §3x has the table).  Form 2 costs 14 VGPRs:
+// the plain 128 x 64 instance goes 82 -> 96, still 5 waves.  The narrow tiles run at 7-8 waves on 62-71
+// VGPRs and would fall to 5-6 with it -- a wave is worth more than the second stage -- so they take form 1
+// (+2 VGPRs, the same waves), and the 256 x 16 split-sum instances (71 / 72 VGPRs, at the edge of 7 waves)
+// none.  The 128 x 64 emitting and split-sum instances hold form 1 inside their parents' registers and
+// spills; with form 2 they spill 2-5 more VGPRs (outside the K loop) and the emitting one measured slower.
+// (XM_PIPE_EMIT64 / XM_PIPE_PLAIN64: the two 128 x 64 choices as build-time switches, for A/B builds.)
+#ifndef XM_PIPE_EMIT64
+#define XM_PIPE_EMIT64 1
+#endif
+template <int NCG, bool EMIT, bool FIX> struct XmPipe { static constexpr int value = 1; };
+#ifndef XM_PIPE_PLAIN64
+#define XM_PIPE_PLAIN64 2
+#endif
+template <> struct XmPipe<4, false, false> { static constexpr int value = XM_PIPE_PLAIN64; };
+template <> struct XmPipe<4, true, false> { static constexpr int value = XM_PIPE_EMIT64; };
+template <bool EMIT> struct XmPipe<1, EMIT, true> { static constexpr int value = 0; };
+template <int NCG, int RB, bool AF32, int XF, bool EMIT, bool FIX = false, int PIPE = 0>
 __global__ __launch_bounds__(256, (XmWaves<AF32, EMIT>::value)) void gemm_f8mx_kernel(const GemmArgs p) {
+    static_assert(PIPE == 0 || (!AF32 && XF != 2), "PIPE: the word-staged plain forms only");
     using Cf = XmCfg<NCG, RB>;
     constexpr int XM = XmFmt<XF>::M, XB = XmFmt<XF>::XB;
     constexpr int NT = Cf::NT, BMT = Cf::BMT, BNT = Cf::BNT, TTK = Cf::TTK, APR = Cf::APR;
@@ -891,8 +918,69 @@ __global__ __launch_bounds__(256, (XmWaves<AF32, EMIT>::value)) void gemm_f8mx_k
                 const uint32_t tok1 = (uint32_t)min(max(140 + (int)(r1 >> 8) - 128 + p.xm_vmin, 0), 252);
                 thr = thi0 | (thi1 << 8) | (tok0 << 16) | (tok1 << 24);
             }
+            if constexpr (PIPE != 0) {
+                // one K-step's table reads (one v_and_or_b32, four ds_read_b64) / its eight conversions
+                auto tread = [&](uint32_t aword, int h, uint2(&v)[4]) {
+                    uint32_t a;
+                    asm("v_and_or_b32 %0, %1, %2, %3" : "=v"(a) : "v"(aword), "s"(XM_ROW_MASK), "v"(base));
+                    __builtin_assume((a & 7u) == 0u);
+                    xm_lds_u64 *ttk = (xm_lds_u64 *)(tt0 + h * TTK * 4);
 #pragma unroll
-            for (int b = 0; b < RB; ++b) {
+                    for (int c = 0; c < 4; ++c) {
+                        const uint64_t w = ttk[(a >> 3) + 16 * c];
+                        v[c] = make_uint2((uint32_t)w, (uint32_t)(w >> 32));
+                    }
+                };
+                auto conv = [&](const uint2(&v)[4], uint32_t aword, int h) {
+                    const float sc = __uint_as_float(aword);
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) {
+                        xm_s2 cv;
+                        if (XF) {
+                            asm("v_cvt_scalef32_pk_bf8_bf16 %0, %1, %2" : "=v"(cv) : "v"(v[c].x), "v"(sc));
+                            cv = __builtin_amdgcn_cvt_scalef32_pk_bf8_bf16(cv, __builtin_bit_cast(xm_b2, v[c].y), sc, true);
+                        } else {
+                            asm("v_cvt_scalef32_pk_fp8_bf16 %0, %1, %2" : "=v"(cv) : "v"(v[c].x), "v"(sc));
+                            cv = __builtin_amdgcn_cvt_scalef32_pk_fp8_bf16(cv, __builtin_bit_cast(xm_b2, v[c].y), sc, true);
+                        }
+                        av[4 * h + c] = __builtin_bit_cast(int, cv);
+                    }
+                };
+                // (a volatile u64 like the table reads: one ds_read_b64 that stays where the source puts it)
+                auto aread = [&](int b) {
+                    const uint64_t w = *(xm_lds_u64 *)&sm.aw[g][2 * (16 * (RB * wr + b) + r16)];
+                    return make_uint2((uint32_t)w, (uint32_t)(w >> 32));
+                };
+                // The stages are in source order and pinned (sched_barrier: the scheduler otherwise moves the
+                // asm conversions across the reads); the compiler's own s_waitcnt then count the reads in flight
+                uint2 va[4], vb[4];
+                uint2 awc = aread(0), awn = awc;
+                if (PIPE == 2) tread(awc.x, 0, va);
+#pragma unroll
+                for (int b = 0; b < RB; ++b) {
+                    if (b + 1 < RB) awn = aread(b + 1);
+                    if (PIPE == 2) {
+                        tread(awc.y, 1, vb);
+                        __builtin_amdgcn_sched_barrier(0);
+                        conv(va, awc.x, 0);
+                        __builtin_amdgcn_sched_barrier(0);
+                        if (b + 1 < RB) tread(awn.x, 0, va);
+                        __builtin_amdgcn_sched_barrier(0);
+                        conv(vb, awc.y, 1);
+                    } else {
+                        __builtin_amdgcn_sched_barrier(0);
+                        tread(awc.x, 0, va);
+                        conv(va, awc.x, 0);
+                        tread(awc.y, 1, va);
+                        conv(va, awc.y, 1);
+                    }
+                    dq[b] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(av, sel, dq[b], XF ? 1 : 0, 0, 0, 127, 0, 127);
+                    __builtin_amdgcn_sched_barrier(0);
+                    awc = awn;
+                }
+            }
+#pragma unroll
+            for (int b = 0; b < (PIPE ? 0 : RB); ++b) {  // (PIPE: the loop above)
                 const uint2 aw2 = *reinterpret_cast<const uint2 *>(&sm.aw[g][2 * (16 * (RB * wr + b) + r16)]);
                 uint32_t awh[2] = {aw2.x, aw2.y};
                 int sca = 127;  // this lane group's MX block scale (E8M0)

@@ -19,6 +19,22 @@ static void launch_shape(const GemmArgs &a, hipStream_t s) {
     // (the emitting instances only where this launch writes the next convolution's word image
     // from its own store: unsplit, or split with the in-launch sum -- fp8a_conv2d_chain)
     const bool emit = a.em.w != nullptr && (a.splits == 1 || a.skcnt != nullptr);
+    // option "xm_pipe": the word-staged plain forms run their software-pipelined instances (the fp32-staging
+    // and halved-block instances have none)
+    if constexpr (XF != 2) {
+        if (a.xm_pipe && !a.af32) {
+            if constexpr (XF == 0) {
+                if (a.skcnt != nullptr) {
+                    if (emit) gemm_f8mx_kernel<NCG, RB, false, XF, true, true, XmPipe<NCG, true, true>::value><<<g, Cf::NT, 0, s>>>(a);
+                    else gemm_f8mx_kernel<NCG, RB, false, XF, false, true, XmPipe<NCG, false, true>::value><<<g, Cf::NT, 0, s>>>(a);
+                    return;
+                }
+            }
+            if (emit) gemm_f8mx_kernel<NCG, RB, false, XF, true, false, XmPipe<NCG, true, false>::value><<<g, Cf::NT, 0, s>>>(a);
+            else gemm_f8mx_kernel<NCG, RB, false, XF, false, false, XmPipe<NCG, false, false>::value><<<g, Cf::NT, 0, s>>>(a);
+            return;
+        }
+    }
     if constexpr (XF == 0) {
         if (a.skcnt != nullptr) {  // split, summed inside the launch: the FIX instances
             if (a.af32) {

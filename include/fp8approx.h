@@ -142,6 +142,9 @@ int fp8a_kernel_time(double *out, int reset);
  * inside the launch (the tile's last-arriving block, one counter word per tile in the workspace after the
  * partials, zeroed by the launch's own pre-pass) instead of in a separate reduction kernel (0, the default:
  * the in-launch sum measured slower).
+ * "xm_pipe" (default 1; FP8A_XM_PIPE) -- gemm_f8mx_kernel's word-staged E4M3 / E5M2 launches run the
+ * instances whose K loop issues its LDS reads one stage ahead of the conversions that use them (0: the loop
+ * without the pipelining).
  * All of these change the schedule only: the outputs are bit-identical.  Returns the previous value, or FP8A_EINVAL
  * for an unknown name.  Not synchronised with launches in flight on other threads.
  */

@@ -8,6 +8,13 @@
 // Parts are switched off by template bits to attribute the time.  Clock: s_memtime around the loop
 // (shader cycles), so results are cycles, independent of DVFS.
 //
+// PIPE (third template argument, bits): the same instruction multiset per product, software-
+// pipelined inside the wave.  PA: block b + 1's A word pair is read before block
+// b's conversions (block 0's right after the barrier).  PB: the four table reads of K-step
+// (b, h) + 1 are issued, into the other of two buffers, before the eight conversions of step
+// (b, h); nothing is read across the tile's closing barrier.  PC: the build issues both units'
+// static-table reads before its first packed add.  PD: the MFMA's code operand in two buffers.
+//
 //   hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -o tools/bin/seg_bench tools/seg_bench.hip
 //   tools/bin/seg_bench [tiles]
 #include <hip/hip_runtime.h>
@@ -34,7 +41,9 @@ enum { P_LDS = 1, P_CVT = 2, P_MFMA = 4, P_BUILD = 8, P_BAR = 16, P_STAGE = 32, 
 // at compile time -- the bound.  P_POSRT: the same chosen by a wave-uniform word read once before
 // the loop (`negrows`, 0 here), i.e. the in-loop uniform branch a product kernel would carry.
 
-template <int P, int WAVES>
+enum { PA = 1, PB = 2, PC = 4, PD = 8 };
+
+template <int P, int WAVES, int PIPE = 0>
 __global__ __launch_bounds__(256, WAVES) void seg(const uint32_t *seed, float *out, unsigned long long *cyc, int tiles,
                                                   const uint32_t *gbuf, const uint32_t *negrows) {
     __shared__ __attribute__((aligned(16))) Stage sm;
@@ -65,6 +74,7 @@ __global__ __launch_bounds__(256, WAVES) void seg(const uint32_t *seed, float *o
     v4f dq[RB];
     for (int b = 0; b < RB; ++b) dq[b] = (v4f){0.0f, 0.0f, 0.0f, 0.0f};
     v8i av = {0, 0, 0, 0, 0, 0, 0, 0};
+    v8i av1 = {0, 0, 0, 0, 0, 0, 0, 0};  // (PD)
     const char *lut = reinterpret_cast<const char *>(sm.lut);
     const uint32_t wvo = (uint32_t)wv * 512u;
     typedef const volatile __attribute__((address_space(3))) uint64_t lds_u64;
@@ -93,7 +103,27 @@ __global__ __launch_bounds__(256, WAVES) void seg(const uint32_t *seed, float *o
             *reinterpret_cast<uint2 *>(&sm.aw[wv][2 * lane]) = make_uint2((110u << 23) | (stw & 0x78u), (111u << 23) | ((stw >> 8) & 0x78u));
             *reinterpret_cast<uint2 *>(&sm.aw[wv][2 * (lane + 64)]) = make_uint2((112u << 23) | ((stw >> 4) & 0x78u), (110u << 23) | ((stw >> 12) & 0x78u));
         }
-        if (P & P_BUILD) {
+        if ((P & P_BUILD) && (PIPE & PC)) {
+            // (c) both units' static-table reads first (unit u reads 32 B on, so the compiler keeps four
+            // reads: here the two units' offsets are one register), then the adds and the stores
+            auto pk = [](uint32_t v, u2 ad) { return __builtin_bit_cast(uint32_t, __builtin_bit_cast(u2, v) + ad); };
+            uint2 s0[2], s1[2];
+#pragma unroll
+            for (int u = 0; u < 2; ++u) {
+                s0[u] = *reinterpret_cast<const uint2 *>(lut + wb.y + 8 * q4 + 32 * u);
+                s1[u] = *reinterpret_cast<const uint2 *>(lut + wb.w + 8 * q4 + 32 * u);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int u = 0; u < 2; ++u) {
+                const uint4 b = wb;
+                const u2 a0 = __builtin_bit_cast(u2, b.x), a1 = __builtin_bit_cast(u2, b.z);
+                const u2 n0 = __builtin_bit_cast(u2, b.x ^ 0x80008000u), n1 = __builtin_bit_cast(u2, b.z ^ 0x80008000u);
+                uint32_t *d = &sm.tt[bkk[u]][btx * 32 + q4 * 4];
+                *reinterpret_cast<uint4 *>(d) = make_uint4(pk(s0[u].x, a0), pk(s1[u].x, a1), pk(s0[u].y, a0), pk(s1[u].y, a1));
+                if (both) *reinterpret_cast<uint4 *>(d + 16) = make_uint4(pk(s0[u].x, n0), pk(s1[u].x, n1), pk(s0[u].y, n0), pk(s1[u].y, n1));
+            }
+        } else if (P & P_BUILD) {
 #pragma unroll
             for (int u = 0; u < 2; ++u) {
                 const uint4 b = wb;
@@ -113,6 +143,64 @@ __global__ __launch_bounds__(256, WAVES) void seg(const uint32_t *seed, float *o
             const int r16 = lane & 15, g = lane >> 4;
             const uint32_t base = wvo + (uint32_t)(2 * g) * (uint32_t)(TTK * 4);
             const char *tt0 = reinterpret_cast<const char *>(&sm.tt[0][0]);
+            if constexpr ((PIPE & (PA | PB | PD)) != 0) {
+                static_assert(PIPE == 0 || ((P & P_LDS) && (P & P_CVT) && (P & P_MFMA)), "pipelined forms: the whole segment");
+                // the table reads of one K-step (one v_and_or_b32, four ds_read_b64) / its eight conversions
+                auto tread = [&](uint32_t aword, int h, uint2(&v)[4]) {
+                    uint32_t a;
+                    asm("v_and_or_b32 %0, %1, %2, %3" : "=v"(a) : "v"(aword), "s"(0x78u), "v"(base));
+                    __builtin_assume((a & 7u) == 0u);
+                    lds_u64 *ttk = (lds_u64 *)(tt0 + h * TTK * 4);
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) {
+                        const uint64_t w = ttk[(a >> 3) + 16 * c];
+                        v[c] = make_uint2((uint32_t)w, (uint32_t)(w >> 32));
+                    }
+                };
+                auto conv = [&](const uint2(&v)[4], uint32_t aword, int h, v8i &o) {
+                    const float sc = __uint_as_float(aword);
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) {
+                        s2 cv;
+                        asm("v_cvt_scalef32_pk_fp8_bf16 %0, %1, %2" : "=v"(cv) : "v"(v[c].x), "v"(sc));
+                        cv = __builtin_amdgcn_cvt_scalef32_pk_fp8_bf16(cv, __builtin_bit_cast(b2, v[c].y), sc, true);
+                        o[4 * h + c] = __builtin_bit_cast(int, cv);
+                    }
+                };
+                // (volatile u64, like the table reads: one ds_read_b64, kept where the source puts it)
+                auto aread = [&](int b) {
+                    const uint64_t w = *(lds_u64 *)&sm.aw[g][2 * (16 * b + r16)];
+                    return make_uint2((uint32_t)w, (uint32_t)(w >> 32));
+                };
+                uint2 va[4], vb[4];
+                uint2 awc = aread(0), awn = awc;
+                if (PIPE & PB) tread(awc.x, 0, va);
+#pragma unroll
+                for (int b = 0; b < RB; ++b) {
+                    v8i &o = ((PIPE & PD) && (b & 1)) ? av1 : av;
+                    if ((PIPE & PA) && b + 1 < RB) awn = aread(b + 1);
+                    if (PIPE & PB) {
+                        tread(awc.y, 1, vb);
+                        __builtin_amdgcn_sched_barrier(0);
+                        conv(va, awc.x, 0, o);
+                        __builtin_amdgcn_sched_barrier(0);
+                        if (!(PIPE & PA) && b + 1 < RB) awn = aread(b + 1);
+                        if (b + 1 < RB) tread(awn.x, 0, va);
+                        __builtin_amdgcn_sched_barrier(0);
+                        conv(vb, awc.y, 1, o);
+                    } else {
+                        __builtin_amdgcn_sched_barrier(0);
+                        tread(awc.x, 0, va);
+                        conv(va, awc.x, 0, o);
+                        tread(awc.y, 1, va);
+                        conv(va, awc.y, 1, o);
+                        if (!(PIPE & PA) && b + 1 < RB) awn = aread(b + 1);
+                    }
+                    dq[b] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(o, sel, dq[b], 0, 0, 0, 127, 0, 127);
+                    __builtin_amdgcn_sched_barrier(0);
+                    awc = awn;
+                }
+            } else {
 #pragma unroll
             for (int b = 0; b < RB; ++b) {
                 const uint2 aw2 = *reinterpret_cast<const uint2 *>(&sm.aw[g][2 * (16 * b + r16)]);
@@ -151,6 +239,7 @@ __global__ __launch_bounds__(256, WAVES) void seg(const uint32_t *seed, float *o
                 else
                     dq[b][0] += __int_as_float(av[0] ^ av[1] ^ av[2] ^ av[3] ^ av[4] ^ av[5] ^ av[6] ^ av[7]);
             }
+            }
         }
         if (P & P_BAR) __syncthreads();
     }
@@ -163,11 +252,11 @@ __global__ __launch_bounds__(256, WAVES) void seg(const uint32_t *seed, float *o
 
 typedef void (*kfn)(const uint32_t *, float *, unsigned long long *, int, const uint32_t *, const uint32_t *);
 
-template <int P, int W>
+template <int P, int W, int PIPE = 0>
 static void run(const char *name, int cus, const uint32_t *seed, float *out, unsigned long long *cyc, int tiles,
                 const uint32_t *gbuf) {
     const int blocks = cus * W;  // one workgroup = one wave per SIMD; W workgroups per CU
-    kfn f = seg<P, W>;
+    kfn f = seg<P, W, PIPE>;
     f<<<blocks, 256>>>(seed, out, cyc, 4, gbuf, gbuf);
     hipDeviceSynchronize();
     hipEvent_t a, b;
@@ -192,6 +281,27 @@ static void run(const char *name, int cus, const uint32_t *seed, float *out, uns
     // W waves share each SIMD for the whole loop (all resident at once)
     printf("%-34s waves/SIMD %d  %8.1f cyc/tile/wave  %6.2f products/SIMD-cycle  (%.3f ms, %.2f GHz by wall)\n", name,
            W, avg / tiles, prod_wave * W / avg, ms, mx / (ms * 1e6));
+}
+
+// the four lines that carry a decision, for one form of the loop, at 4 / 5 / 6 waves per SIMD
+template <int PIPE>
+static void run_form(const char *form, int cus, const uint32_t *seed, float *out, unsigned long long *cyc, int tiles,
+                     const uint32_t *gbuf) {
+    constexpr int ALL = P_LDS | P_CVT | P_MFMA | P_BUILD | P_BAR | P_STAGE;
+    constexpr int ALLG = ALL | P_GLOAD;
+    printf("-- %s\n", form);
+    run<ALL, 4, PIPE>("full", cus, seed, out, cyc, tiles, gbuf);
+    run<ALL, 5, PIPE>("full", cus, seed, out, cyc, tiles, gbuf);
+    run<ALL, 6, PIPE>("full", cus, seed, out, cyc, tiles, gbuf);
+    run<ALL | P_POS, 4, PIPE>("full, pos rows only", cus, seed, out, cyc, tiles, gbuf);
+    run<ALL | P_POS, 5, PIPE>("full, pos rows only", cus, seed, out, cyc, tiles, gbuf);
+    run<ALL | P_POS, 6, PIPE>("full, pos rows only", cus, seed, out, cyc, tiles, gbuf);
+    run<ALLG, 4, PIPE>("full + global loads", cus, seed, out, cyc, tiles, gbuf);
+    run<ALLG, 5, PIPE>("full + global loads", cus, seed, out, cyc, tiles, gbuf);
+    run<ALLG, 6, PIPE>("full + global loads", cus, seed, out, cyc, tiles, gbuf);
+    run<ALLG | P_POS, 4, PIPE>("full + global loads, pos rows", cus, seed, out, cyc, tiles, gbuf);
+    run<ALLG | P_POS, 5, PIPE>("full + global loads, pos rows", cus, seed, out, cyc, tiles, gbuf);
+    run<ALLG | P_POS, 6, PIPE>("full + global loads, pos rows", cus, seed, out, cyc, tiles, gbuf);
 }
 
 int main(int argc, char **argv) {
@@ -242,5 +352,16 @@ int main(int argc, char **argv) {
     run<ALL & ~P_CVT, 6>("full minus cvt", cus, seed, out, cyc, tiles, gbuf);
     run<ALL & ~P_LDS, 6>("full minus table reads", cus, seed, out, cyc, tiles, gbuf);
     run<ALL & ~P_MFMA, 6>("full minus mfma", cus, seed, out, cyc, tiles, gbuf);
+    // the loop as it is and its pipelined forms, the whole set twice (the spread of a line = pass 1 against pass 2)
+    for (int pass = 1; pass <= 2; ++pass) {
+        printf("==== pipelined forms, pass %d\n", pass);
+        run_form<0>("the loop as it is", cus, seed, out, cyc, tiles, gbuf);
+        run_form<PA>("(a) A words one block ahead", cus, seed, out, cyc, tiles, gbuf);
+        run_form<PA | PB>("(a)+(b) table reads one K-step ahead", cus, seed, out, cyc, tiles, gbuf);
+        run_form<PC>("(c) build: reads before adds", cus, seed, out, cyc, tiles, gbuf);
+        run_form<PA | PC>("(a)+(c)", cus, seed, out, cyc, tiles, gbuf);
+        run_form<PA | PB | PC>("(a)+(b)+(c)", cus, seed, out, cyc, tiles, gbuf);
+        run_form<PA | PB | PC | PD>("(a)+(b)+(c)+(d) two code buffers", cus, seed, out, cyc, tiles, gbuf);
+    }
     return 0;
 }
