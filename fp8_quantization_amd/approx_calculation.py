@@ -26,7 +26,7 @@ from .approx_ops import (_bias_dev, _res_quant_params, approx_conv2d, approx_con
                          approx_matmul_block, approx_matmul_check, bias_epilogue, dense_conv2d, dense_format,
                          dense_matmul, format_self_check, grouped_conv2d, make_flags, make_flags_v5, qamaa_conv2d,
                          qamaa_matmul)
-from .error_tables import get_comp_table_NN_v5, get_error_table_NN
+from .error_tables import get_comp_table_NN_v5, get_error_table_NN, load_error_table
 from .quantization.hijacker import QuantizationHijacker
 from .quantization.quantization_manager import QuantizationManager
 from .quantization.base_quantized_classes import QuantizedActivation, QuantizedModule
@@ -51,6 +51,19 @@ class ApproxOpMixin:
     def _approx_config(self):
         p = self.custom_approx_params
         E, M = p["expo_width"], p["mant_width"]
+        custom = p.get("error_table")
+        if custom is not None:
+            # opt-in extension: the user's own multiplier (error_tables.load_error_table) in place of the
+            # reference's selection -- withComp / dnsmp_factor / zero_table_ext are not consulted, and any
+            # format the kernels take runs (E5M2 included)
+            if p.get("approx_version", 9) == 5:
+                raise ValueError("custom_approx_params['error_table'] is a v9 error table (subtracted from the "
+                                 "significand product); the v5 model's table is a compensation table added to "
+                                 "the code sum -- drop approx_version 5 or the table")
+            if not 1 <= M <= 5:
+                raise ValueError("Invalid combination of expo_width and mant_width")
+            flags = make_flags(p["with_approx"], p["with_s2nn2s_opt"], p["quant_btw_mult_accu"], p["golden_clip_OF"])
+            return E, M, self._custom_table(custom, M), flags
         if p.get("approx_version", 9) == 5:
             # opt-in extension: the v5 integer-adder model with live sim_hw_add_OFUF /
             # with_OF_opt / with_UF_opt (approx_v5.py); without withComp, the zero table the v5
@@ -67,6 +80,16 @@ class ApproxOpMixin:
                                    zero_table_ext=p.get("zero_table_ext", False))
         flags = make_flags(p["with_approx"], p["with_s2nn2s_opt"], p["quant_btw_mult_accu"], p["golden_clip_OF"])
         return E, M, table, flags
+
+    def _custom_table(self, spec, M):
+        """custom_approx_params['error_table'] as the kernels' host table, normalised once per operator:
+        the result is kept with the spec object it came from, so a forward costs one identity test.  (A
+        spec mutated in place is not re-read: assign a new object to change the table.)"""
+        c = self.__dict__.get("_error_table_cache")
+        if c is None or c[0] is not spec or c[1] != M:
+            c = (spec, M, load_error_table(spec, M))
+            self.__dict__["_error_table_cache"] = c
+        return c[2]
 
     @staticmethod
     def _default_bias(b, E, device):

@@ -79,8 +79,9 @@ class ChainConsumerMixin:
         # as af32_maxct changes the answer), so the table is not rebuilt and re-listed every forward
         from . import _lib
         p = self.custom_approx_params
+        # (a custom error table by identity, as ApproxOpMixin._custom_table keeps it)
         key = (tuple(sorted((k, v) for k, v in p.items() if isinstance(v, (bool, int, float, str)))),
-               _lib.option_generation())
+               id(p.get("error_table")), _lib.option_generation())
         cached = getattr(self, "_chain_wants", None)
         if cached is None or cached[0] != key:
             from .approx_ops import conv2d_wants_image

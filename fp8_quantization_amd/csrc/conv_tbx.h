@@ -5,8 +5,11 @@
 // 800-809): with int32-tensor biases >= 2, param_prepare's integer powers make
 // min_norm 0, so every nonzero value decodes at its own binade and Q_R rounds at the value's own
 // binade (no subnormal floor).  Rounding is then scale-invariant, so for on-grid E4M3 operands
-// with s2n, per-product quantization, no golden clip and a {0,1} (or zero) error table the term
-// is a TABLE value times the operands' binades:
+// with s2n, per-product quantization, no golden clip and an error table without negative entries
+// whose V = sig_a sig_b - T / 8 stay positive (xm_table_form, fp8approx.hip: the zero table, the
+// built-in {0,1} table, a custom multiplier's; V may then lie up to 2M binades below 1, and L, the
+// expo-0 test and the F7 trigger all work on the term's own binade) the term is a TABLE value times
+// the operands' binades:
 //     r = L(m_a, m_b) * c_a * c_b,   L = Q3c(sig_a sig_b - T[m_a][m_b] / 8)
 // (Q3c: round to 3 mantissa bits at V's own binade with Q_R's saturating clamp, F6), followed by
 // the two quirks the general kernel (conv_tb_fast_kernel) applies per term:

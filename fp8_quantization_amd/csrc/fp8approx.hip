@@ -89,6 +89,30 @@ static int pack_table(const int32_t *table, int M, bool approx, TablePack &tp, i
     return FP8A_OK;
 }
 
+// The error tables the E4M3 / E5M2 matrix-core form (gemm_f8mx.h) and its satellites -- the VALU TM_F8
+// form, the depthwise table form (conv_tbx.h), the word-image hand-off -- can run: every
+// entry >= 0, so the approximate magnitude never exceeds the golden one and the F7 sign rule cannot fire
+// (what Q_R flushes in the golden product it flushes in the approximate one), and every
+// N = (2^M + m_a)(2^M + m_b) - 2^M t >= 1, so V' = N 2^-2M is positive, normal and -- N <= 225 -- exact in
+// bf16.  *vmin: the lowest binade of any V' (0 for the zero and the built-in tables, >= -2M).  A zeroed
+// pack (no table, approx off) passes with vmin 0.
+static bool xm_table_form(const TablePack &tp, int Mw, int *vmin) {
+    if (Mw < 1 || Mw > 5) return false;
+    const int n = 1 << Mw;
+    int lo = 1;
+    for (int ma = 0; ma < n; ++ma)
+        for (int mb = 0; mb < n; ++mb) {
+            const int t = tp.raw[ma * n + mb];
+            const int N = (n + ma) * (n + mb) - n * t;
+            if (t < 0 || N < 1) return false;
+            int b = 0;
+            while ((N >> (b + 1)) != 0) ++b;  // floor(log2 N)
+            lo = std::min(lo, b - 2 * Mw);
+        }
+    if (vmin) *vmin = lo;
+    return true;
+}
+
 // Fallback statistics since load (or the last reset): [0] launches whose gated exact kernel
 // ran, [1] 64 x 64 output units it recomputed, [2] launches rerun in gemm_tt_kernel's f32 form
 // (gemm_tt16_kernel's f16 window left), [3] tensor-bias launches recomputed by
@@ -792,14 +816,16 @@ static size_t gemm_workspace_bytes(int64_t M, int64_t N, int64_t K, int64_t conv
 
 // The table + hardware-fp8 form applies (TM_F8; run_gemm then takes the matrix-core kernel when
 // the workspace holds its pre-decoded operands): E4M3 (e4m3 conversion) or E5M2 (bf8 conversion,
-// round 4), a {0,1} or zero table, s2n + qbma, no golden clip, int-bias semantics, not v5.
-// (E5M2 has no VALU TM_F8 form: without the pre-decoded operands it keeps its table mode.)
+// round 4), a table of xm_table_form (no negative entry, every V' positive: the zero table, the built-in
+// {0,1} table, a custom multiplier's), s2n + qbma, no golden clip, int-bias semantics, not v5.
+// (E5M2 has no VALU TM_F8 form: without the pre-decoded operands it keeps its table mode.  E4M3's VALU
+// TM_F8 form builds its V' from the raw table as xm_lut_word does, in fp32, so it takes the same tables.)
 // FP8A_NO_F8=1 keeps the arithmetic forms; FP8A_NO_F8_E5M2=1 only for E5M2 (A/B runs).
-static bool f8_form(int E, int Mw, uint32_t flags, int table_mode) {
+static bool f8_form(int E, int Mw, uint32_t flags, const TablePack &tab) {
     static const bool no_f8 = getenv("FP8A_NO_F8") != nullptr;
     static const bool no_f8_e5 = getenv("FP8A_NO_F8_E5M2") != nullptr;
     const bool fmt = (E == 4 && Mw == 3) || (E == 5 && Mw == 2 && !no_f8_e5);
-    return !no_f8 && !(flags & F_V5) && fmt && (table_mode == TM_NONE || table_mode == TM_W1U) &&
+    return !no_f8 && !(flags & F_V5) && fmt && xm_table_form(tab, Mw, nullptr) &&
            (flags & F_S2N) && (flags & F_QBMA) && !(flags & F_GCLIP) && !(flags & F_TB);
 }
 
@@ -1050,9 +1076,9 @@ static int run_gemm(GemmArgs &a, const int32_t *table, void *ws, size_t ws_bytes
     if (rc) return rc;
     if (v5) mode = TM_V5;
     const int mode0 = mode;
-    // E4M3 / E5M2 with a {0,1} (or no) table, s2n and per-product quantization: the LUT + hardware
-    // fp8 / bf8 form (FP8A_NO_F8=1 keeps the arithmetic form, for comparison)
-    if (f8_form(a.E, a.Mw, a.flags, mode)) mode = TM_F8;
+    // E4M3 / E5M2 with a non-negative (or no) table (xm_table_form), s2n and per-product quantization:
+    // the LUT + hardware fp8 / bf8 form (FP8A_NO_F8=1 keeps the arithmetic form, for comparison)
+    if (f8_form(a.E, a.Mw, a.flags, a.tab)) mode = TM_F8;
     const int64_t total = a.M * a.N;
     const unsigned eblocks = (unsigned)std::min<int64_t>((total + 255) / 256, 4096);
     if (a.flags & F_TB) {
@@ -1107,7 +1133,8 @@ static int run_gemm(GemmArgs &a, const int32_t *table, void *ws, size_t ws_bytes
             a.bqw = (const uint2 *)(base + align256((size_t)a_words * 4));
             a.lutw = (const uint32_t *)(base + align256((size_t)a_words * 4) + xm_b_bytes(kpad, npad));
             a.ebr = (const uint16_t *)((const char *)a.lutw + 16384);
-            a.xm_vmin = mode == TM_NONE ? 0 : -1;
+            a.xm_vmin = 0;  // the table's lowest V' binade (the E5M2 halved-block form's `tok` threshold)
+            if (mode == TM_F8) (void)xm_table_form(a.tab, a.Mw, &a.xm_vmin);
             a.npad = npad;
             a.ttf7 = 0;
             for (int i = 0; tt && i < (1 << (2 * a.Mw)); ++i) a.ttf7 |= a.tab.raw[i] < 0;
@@ -2086,11 +2113,11 @@ static int conv2d_impl(const float *x, const float *w, float *y, int64_t Bn, int
         // fast form: needs s2n on and golden_clip_OF off (else every launch would fall back)
         const bool fast_ok = (flags & F_S2N) && !(flags & F_GCLIP) && workspace != nullptr &&
                              workspace_bytes >= FLAG_BYTES && Cout <= 65535 && Bn <= 65535;
-        // E4M3 table form (conv_tbx.h): {0,1} / zero table, qbma, 3-wide kernel rows, stride 1 or 2
+        // E4M3 / E5M2 table form (conv_tbx.h): a table of xm_table_form, qbma, 3-wide kernel rows, stride 1 or 2
         const int64_t nwg = (Wo + TBX_TW - 1) / TBX_TW, items = Bn * Cout * Ho * nwg;
         static const bool no_tbx = getenv("FP8A_NO_TBX") != nullptr;
         const bool tbx_ok = fast_ok && !no_tbx && ((E == 4 && Mw == 3) || (E == 5 && Mw == 2)) &&
-                            (mode == TM_NONE || mode == TM_W1U) &&
+                            xm_table_form(tp, Mw, nullptr) &&
                             (flags & F_QBMA) && kw == 3 && dw == 1 && sh == sw && (sw == 1 || sw == 2) &&
                             items < (1ll << 31) && Ho * Wo < (1ll << 31) &&
                             workspace_bytes >= FLAG_BYTES + (size_t)(Bn * Cin * H * W) * 4;
@@ -2204,7 +2231,7 @@ static int conv2d_impl(const float *x, const float *w, float *y, int64_t Bn, int
         const int64_t kpad = (Kg + BK - 1) / BK * BK, npad = (cog + BN - 1) / BN * BN;
         // (run_gemm's matrix-core forms: every one applies fq in its A pre-decode, xm_decode_a)
         const uint32_t gf = flags & ~F_TB;
-        const bool form = f8_form(E, Mw, gf, mode) || tt_form(Mw, gf, tp) || v5mx_form(Mw, gf, mode);
+        const bool form = f8_form(E, Mw, gf, tp) || tt_form(Mw, gf, tp) || v5mx_form(Mw, gf, mode);
         const bool fused = form && !no_mx() && a_words < (1ll << 30) &&
                            kpad * npad * 4 < (1ll << 32) &&
                            workspace_bytes >= gemm_workspace_bytes(Mrows, cog, Kg, a_words);
@@ -2447,7 +2474,9 @@ int fp8a_word_image_init(void *image, int64_t Bn, int64_t C, int64_t H, int64_t 
     if (image == nullptr || fp8a_word_image_bytes(Bn, C, H, W, ph, pw) == 0) return fail(FP8A_EINVAL, "word image");
     if (((uintptr_t)image & 255) != 0) return fail(FP8A_EINVAL, "word image must be 256-byte aligned");
     const WordImage wi = word_image(H, W, ph, pw);
-    const int64_t words = Bn * C * wi.H * wi.W;
+    // (every word of fp8a_word_image_bytes, the 256-byte rounding's tail included: no kernel reads it, but
+    // a caller that compares or copies whole images then sees defined bytes)
+    const int64_t words = (int64_t)(align256((size_t)(Bn * C * wi.H * wi.W) * 4) / 4);
     word_image_fill_kernel<<<(unsigned)std::min<int64_t>((words + 255) / 256, 8192), 256, 0, (hipStream_t)stream>>>(
         (uint32_t *)image, words);
     return hip_check("fp8a word image init");
@@ -2468,7 +2497,7 @@ int fp8a_conv2d_wants_image(int64_t Cout, int kh, int kw, int ph, int pw, int gr
         static const bool no_tbx = getenv("FP8A_NO_TBX") != nullptr;
         static const bool chain_tbx = getenv("FP8A_CHAIN_TBX") != nullptr && atoi(getenv("FP8A_CHAIN_TBX")) != 0;
         const bool tbx = chain_tbx && !no_tbx && ((E == 4 && Mw == 3) || (E == 5 && Mw == 2)) &&
-                         (mode == TM_NONE || mode == TM_W1U) && (flags & F_S2N) && (flags & F_QBMA) &&
+                         xm_table_form(tp, Mw, nullptr) && (flags & F_S2N) && (flags & F_QBMA) &&
                          !(flags & (F_GCLIP | F_V5)) && kw == 3 && dw == 1 && sh == sw && (sw == 1 || sw == 2);
         (void)kh; (void)dh;
         return tbx ? 2 : 0;
@@ -2478,7 +2507,7 @@ int fp8a_conv2d_wants_image(int64_t Cout, int kh, int kw, int ph, int pw, int gr
     // border holds the E4M3 / E5M2 form's zero word, fp8a_word_image_init); emitted by the staged
     // v5 depthwise kernel only (conv_v5ds_kernel) -- every other producer flags the image invalid
     if (flags & F_V5) return (v5mx_form(Mw, flags, TM_V5) && ph == 0 && pw == 0) ? 3 : 0;
-    if (!f8_form(E, Mw, flags & ~F_TB, mode)) return 0;
+    if (!f8_form(E, Mw, flags & ~F_TB, tp)) return 0;
     if (kh == 1 && kw == 1 && ph == 0 && pw == 0) {  // xm_af32: fp32 staging up to af32_maxct column tiles
         const int64_t bnt = 16 * xm_ncg(Cout), ct = (Cout + bnt - 1) / bnt;
         if (ct <= af32_maxct(sh, sw)) return 0;
@@ -2625,7 +2654,7 @@ int fp8a_matmul_block(const float *A, int64_t lda, const float *B, int64_t sbk, 
         rc = pack_table(table, Mw, (flags & F_APPROX) != 0, tp, mode);
         if (rc) return rc;
         const int64_t kpad = (K + BK - 1) / BK * BK, npad = (N + BN - 1) / BN * BN, a_words = M * kpad;
-        const bool fused = f8_form(E, Mw, flags, mode) && !no_mx() && a_words < (1ll << 30) &&
+        const bool fused = f8_form(E, Mw, flags, tp) && !no_mx() && a_words < (1ll << 30) &&
                            kpad * npad * 4 < (1ll << 32) && rest >= gemm_workspace_bytes(M, N, K, 0);
         if (fused) {
             a.fqin = fin;

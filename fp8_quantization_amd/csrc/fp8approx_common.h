@@ -207,7 +207,7 @@ struct GemmArgs {
     // E5M2 (gemm_f8mx_kernel XF = 1): per (K-step, 16-column group) the nonzero B elements' exponent
     // range, (max e_b + 128) | (min e_b + 128) << 8 ([kpad][npad / 16]; 0xFF00 when all are zero)
     const uint16_t *ebr;
-    int xm_vmin;  // the smallest binade of the table value V' (0: V' >= 1, -1 with a {0,1} table)
+    int xm_vmin;  // the smallest binade of the table value V' (0: V' >= 1; down to -2M with a custom table, xm_table_form)
     int xm_pipe;  // host side only (launch_shape, k_f8mx.hip): the word-staged E4M3 / E5M2 launches run the instances
                   // whose K loop reads LDS one stage ahead (option "xm_pipe", gemm_f8mx.h PIPE; 0: the loop without it)
     int64_t npad;

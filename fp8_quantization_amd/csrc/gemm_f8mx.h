@@ -165,6 +165,10 @@ __device__ __forceinline__ bool xm_bias_ok(int b) { return b >= -100 && b <= 120
 
 // Table word e of layout [pair][m_a]: the bf16 pair V'(m_a, code0), V'(m_a, code1), s_a = +, for
 // M mantissa bits (3: E4M3, 2: E5M2; rows / codes >= 2^M are never addressed).
+// Any table of xm_table_form (fp8approx.hip): V' = N 2^-2M with 1 <= N <= 225 is a positive normal with at
+// most 8 significant bits in binades -2M .. 1, exact in bf16; the pre-clamp takes V's own binade, and the
+// packed exponent add of c_b (|e_b| <= 62 inside the exactness window) keeps the bf16 exponent field in
+// [127 - 6 - 62, 128 + 50].
 __device__ __forceinline__ uint32_t xm_lut_word(const TablePack &tab, int e, int M) {
     const int pr = e >> 3, ma = e & 7, n = 1 << M;
     const float ulp = M == 3 ? 0.125f : 0.25f;

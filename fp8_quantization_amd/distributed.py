@@ -2,7 +2,8 @@
 
 Inference images are independent, so the validation set is sharded contiguously over ranks
 (one process per GPU) with no collective in the data path.  The collectives:
-  * once, before the data path: rank 0's float model state (parameters and buffers: the BN
+  * once, before the data path: a custom error table (broadcast_error_tables: rank 0's is what every
+    rank runs, a rank whose own differs raises), rank 0's float model state (parameters and buffers: the BN
     statistics of a synthetic-weights model are estimated per process) and, after rank 0 alone
     has calibrated, its FP8 ranges (every FPQuantizer.maxval / sign_bits, a few KB) are
     broadcast, so all ranks use identical weights and bA / bB / bR (calibrate_on_rank0);
@@ -135,6 +136,64 @@ def broadcast_quant_state(model, src=0):
             off += cn
 
 
+def approx_operators(model):
+    """The modules that carry an approx configuration dict (the operators' custom_approx_params)."""
+    return [m for m in model.modules() if isinstance(getattr(m, "custom_approx_params", None), dict)]
+
+
+def broadcast_error_tables(model, src=0):
+    """Custom error tables (custom_approx_params["error_table"]): rank `src`'s table is what every rank
+    runs.  Two broadcasts in all, next to the quantizer state: an int64 header (per operator: the
+    table's side, 0 without one) and one int32 buffer of every table.  A rank that holds no table takes
+    rank `src`'s; a rank whose own table differs from rank `src`'s -- another file behind the same flag,
+    or a table where rank `src` has none -- raises ValueError naming both digests (sha256 of the int8
+    bytes, error_tables.table_digest), and every other rank raises with it instead of waiting in the next
+    collective."""
+    ws, rank = world()
+    if ws == 1:
+        return
+    from .error_tables import load_error_table, table_digest
+    ops = approx_operators(model)
+    if not ops:
+        return
+    mine, cache = [], {}
+    for m in ops:  # (operators share one spec object: normalise each object once)
+        p = m.custom_approx_params
+        spec = p.get("error_table")
+        if spec is not None and id(spec) not in cache:
+            cache[id(spec)] = load_error_table(spec, p["mant_width"])
+        mine.append(None if spec is None else cache[id(spec)])
+    dev = comm_device()
+    hdr = torch.tensor([0 if t is None else t.shape[0] for t in mine], dtype=torch.int64)
+    hdr = hdr.to(dev)
+    dist.broadcast(hdr, src)
+    sides = hdr.cpu().tolist()
+    total = sum(n * n for n in sides)
+    if rank == src:
+        flat = torch.cat([t.reshape(-1) for t in mine if t is not None] + [torch.zeros(0, dtype=torch.int32)]).to(dev)
+    else:
+        flat = torch.empty(total, dtype=torch.int32, device=dev)
+    if total:
+        dist.broadcast(flat, src)
+    flat = flat.cpu()
+    off, bad, shared = 0, None, {}
+    for m, own, n in zip(ops, mine, sides):
+        theirs = flat[off:off + n * n].view(n, n).contiguous() if n else None
+        off += n * n
+        if own is None and theirs is not None:
+            key = table_digest(theirs)  # (one tensor object per distinct table, as the operators had one spec)
+            m.custom_approx_params["error_table"] = shared.setdefault(key, theirs)
+        elif own is not None and (theirs is None or own.shape != theirs.shape or not torch.equal(own, theirs)):
+            bad = bad or (table_digest(own), table_digest(theirs) if theirs is not None else "none")
+    flag = torch.tensor([1 if bad else 0], dtype=torch.int32, device=dev)
+    dist.all_reduce(flag, op=dist.ReduceOp.MAX)
+    if bad:
+        raise ValueError(f"rank {rank}'s error table (sha256 {bad[0]}) differs from rank {src}'s (sha256 {bad[1]}): "
+                         f"rank {src}'s table is what every rank runs")
+    if int(flag.item()):
+        raise ValueError(f"another rank's error table differs from rank {src}'s")
+
+
 def allreduce_bn_sums(sums, batch_count, group=None):
     """The BN re-estimation's collective (bn_reestimate.reestimate_bn_stats): every layer's summed
     per-batch statistics -- `sums`, a list of float32 tensors, the same shapes on every rank -- and
@@ -181,6 +240,7 @@ def calibrate_on_rank0(model, batches, src=0, quantized=False):
         model.set_quant_state(True, True)
     model.fix_ranges()
     broadcast_quant_state(model, src)
+    broadcast_error_tables(model, src)
 
 
 def gather_logits(logits):

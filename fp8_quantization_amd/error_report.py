@@ -9,6 +9,7 @@ approx sum against the golden one, the shares of normal values in A, B and the p
 the production kernel's distance from the literal check kernel in units of the project's 1e-5 S bar.
 
     python -m fp8_quantization_amd.error_report --arch resnet18 --batch 16 [--size 224] [--json]
+                                                [--error-table FILE]
 
 builds the synthetic calibrated workload of the benchmark's workload modules (random weights, BN
 statistics estimated on synthetic batches, one calibration batch, fixed ranges) and prints the table.
@@ -138,13 +139,22 @@ def main(argv=None):
     ap.add_argument("--no-s2n", action="store_true", help="with_s2nn2s_opt off (adds the R_3d share)")
     ap.add_argument("--cal-batch", type=int, default=64)
     ap.add_argument("--bn-stats-batches", type=int, default=4)
+    ap.add_argument("--error-table", default=None, metavar="FILE",
+                    help="a custom error table (.npy or text rows) in place of the built-in one")
     args = ap.parse_args(argv)
     cfg = dict(expo_width=args.expo_width, mant_width=args.mant_width, dnsmp_factor=3, withComp=args.with_comp,
                with_approx=True, with_s2nn2s_opt=not args.no_s2n, quant_btw_mult_accu=True)
+    digest = None
+    if args.error_table:
+        from .error_tables import load_error_table, table_digest
+        cfg["error_table"] = load_error_table(args.error_table, args.mant_width)
+        digest = table_digest(cfg["error_table"])
     model = build_workload(args.arch, args.size, cfg, args.bn_stats_batches, args.cal_batch)
     g = torch.Generator(device="cpu").manual_seed(10)
     x = torch.randn((args.batch, 3, args.size, args.size), generator=g).to("cuda")
     rows = layer_error_report(model, x)
+    if digest is not None and not args.json:  # (--json stays the bare list of rows)
+        print(f"error table {args.error_table} sha256 {digest}")
     print(json.dumps(rows) if args.json else format_report(rows))
     return rows
 

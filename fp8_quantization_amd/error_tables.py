@@ -8,6 +8,10 @@ quirks: E4M3 ignores dnsmp_factor; withComp=True on E4M3 is the all-
 unsupported (E, M) raise ValueError; an unlisted dnsmp_factor for E3M4/E2M5 with withComp
 raises UnboundLocalError exactly as the reference does.
 """
+import hashlib
+import os
+
+import numpy as np
 import torch
 
 _DEC = {".": 0, "-": -1, "1": 1, "2": 2, "3": 3, "4": 4, "5": 5}
@@ -398,3 +402,120 @@ def get_comp_table_NN_v5(expo_width, mant_width, withComp, dnsmp_factor, zero_ta
     if zero_table_ext and withComp and 1 <= mant_width <= 5 and (expo_width, mant_width) not in ((4, 3), (3, 4), (2, 5)):
         return torch.zeros((2 ** mant_width, 2 ** mant_width), dtype=torch.int32)  # (as get_error_table_NN)
     raise ValueError("Invalid combination of expo_width and mant_width")
+
+
+# ---------------------------------------------------------------------------------------------
+# Custom error tables: a user's own multiplier through the same kernels.
+# custom_approx_params["error_table"] takes anything load_error_table accepts.
+_ROW_CHARS = {".": 0, "-": -1, **{str(d): d for d in range(10)}}
+_ROW_OF = {v: k for k, v in _ROW_CHARS.items()}
+_ROW_OF[0] = "."
+
+
+def _parse_rows(text, what):
+    """Text in this module's row notation: one row per line, '.' = 0, '-' = -1, digits as themselves;
+    blank lines and '#' comments are skipped."""
+    rows = []
+    for ln, line in enumerate(text.splitlines(), 1):
+        line = line.split("#", 1)[0].strip()
+        if not line:
+            continue
+        for col, ch in enumerate(line):
+            if ch not in _ROW_CHARS:
+                raise ValueError(f"{what}: line {ln}, column {col + 1}: {ch!r} is not a table entry "
+                                 "('.' = 0, '-' = -1, digits 0-9)")
+        rows.append([_ROW_CHARS[ch] for ch in line])
+    return rows
+
+
+def load_error_table(spec, mant_width):
+    """Normalise a user's error table to a contiguous CPU int32 tensor [2^M, 2^M].
+
+    spec: an integer tensor, an ndarray, a nested list, the path of a .npy file, or the path of a
+    text file in this module's row notation.  Entry [m_a][m_b] is subtracted, times 2^-M, from the exact
+    significand product (v9:178-184), exactly as the built-in tables are.  ValueError (naming the
+    offending entry) for a wrong shape, non-integer values, or entries outside the int8 range the
+    kernels' table pack holds."""
+    n = 2 ** int(mant_width)
+    what = "error table"
+    if isinstance(spec, (str, os.PathLike)):
+        path = os.fspath(spec)
+        what = f"error table {path}"
+        if path.endswith(".npy"):
+            arr = np.load(path, allow_pickle=False)
+        else:
+            with open(path) as f:
+                rows = _parse_rows(f.read(), what)
+            if len({len(r) for r in rows}) > 1:
+                bad = next(i for i, r in enumerate(rows) if len(r) != len(rows[0]))
+                raise ValueError(f"{what}: row {bad} has {len(rows[bad])} entries, row 0 has {len(rows[0])}")
+            arr = np.asarray(rows, dtype=np.int64).reshape(len(rows), -1)
+    elif isinstance(spec, torch.Tensor):
+        arr = spec.detach().cpu().numpy()
+    else:
+        try:
+            arr = np.asarray(spec)
+        except ValueError as e:  # ragged nested list
+            raise ValueError(f"{what}: not a rectangular array ({e})") from None
+    if arr.dtype == object or arr.dtype.kind not in "iufb":
+        raise ValueError(f"{what}: entries must be integers, got dtype {arr.dtype}")
+    if arr.shape != (n, n):
+        raise ValueError(f"{what}: shape {tuple(arr.shape)}, expected ({n}, {n}) for mant_width {mant_width}")
+    if arr.dtype.kind == "f":
+        bad = np.argwhere(~(np.isfinite(arr) & (arr == np.round(arr))))
+        if len(bad):
+            i, j = (int(v) for v in bad[0])
+            raise ValueError(f"{what}: entry [{i}][{j}] = {arr[i, j].item()!r} is not an integer")
+    arr = arr.astype(np.int64)
+    bad = np.argwhere((arr < -128) | (arr > 127))
+    if len(bad):
+        i, j = (int(v) for v in bad[0])
+        raise ValueError(f"{what}: entry [{i}][{j}] = {int(arr[i, j])} is outside the int8 range [-128, 127]")
+    return torch.from_numpy(np.ascontiguousarray(arr.astype(np.int32)))
+
+
+def format_error_table(t):
+    """The inverse of the text form load_error_table reads: one string per row ('.' = 0, '-' = -1,
+    digits).  ValueError for an entry the notation has no character for (outside -1 .. 9)."""
+    arr = np.asarray(t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else t)
+    if arr.ndim != 2:
+        raise ValueError(f"error table: shape {tuple(arr.shape)} is not two-dimensional")
+    rows = []
+    for i, r in enumerate(arr.tolist()):
+        for j, v in enumerate(r):
+            if v != int(v) or int(v) not in _ROW_OF:
+                raise ValueError(f"error table: entry [{i}][{j}] = {v!r} has no character in the row notation "
+                                 "(-1 .. 9); save it as .npy instead")
+        rows.append("".join(_ROW_OF[int(v)] for v in r))
+    return rows
+
+
+def table_from_multiplier(fn, mant_width):
+    """The error table of an approximate significand multiplier.  fn(ma, mb) is the approximate product
+    of the significands (2^M + ma) and (2^M + mb) as an integer in units of 2^-2M; the entry is
+    ((2^M + ma)(2^M + mb) - fn(ma, mb)) / 2^M.  ValueError when that is not an integer: the model
+    subtracts whole units of 2^-M only (v9:182)."""
+    M = int(mant_width)
+    n = 2 ** M
+    rows = []
+    for ma in range(n):
+        row = []
+        for mb in range(n):
+            approx = fn(ma, mb)
+            if approx != int(approx):
+                raise ValueError(f"multiplier({ma}, {mb}) = {approx!r} is not an integer (units of 2^-{2 * M})")
+            diff = (n + ma) * (n + mb) - int(approx)
+            if diff % n:
+                raise ValueError(f"multiplier({ma}, {mb}) = {int(approx)}: the error {diff} x 2^-{2 * M} is not a "
+                                 f"whole number of 2^-{M} units, which is all the model subtracts")
+            row.append(diff // n)
+        rows.append(row)
+    return load_error_table(rows, M)
+
+
+def table_digest(t):
+    """sha256 (hex) of the table's int8 bytes, row-major: what result files and ranks compare."""
+    arr = np.asarray(t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else t)
+    if np.any(arr != np.round(arr)) or np.any((arr < -128) | (arr > 127)):
+        raise ValueError("error table: entries outside the int8 range have no digest")
+    return hashlib.sha256(np.ascontiguousarray(arr.astype(np.int8)).tobytes()).hexdigest()

@@ -177,6 +177,9 @@ def parse(argv=None):
     ap.add_argument("--bn-batches", type=int, default=None,
                     help="train batches of the BN re-estimation (default: int(0.002 * number of train batches), "
                          "the reference's)")
+    ap.add_argument("--error-table", default=None, metavar="FILE",
+                    help="a custom error table (.npy, or text rows: '.' = 0, '-' = -1, digits) in place of the "
+                         "built-in one: error_tables.load_error_table")
     ap.add_argument("--output", default=None, help="also write the result JSON here")
     return ap.parse_args(argv)
 
@@ -198,7 +201,7 @@ def validate(model, val, train, args, dev, rank=0, ws=1, source=""):
             yield x.to(dev, non_blocking=True)
             if i >= args.num_est_batches - 1:
                 break
-    calibrate_on_rank0(model, cal_batches())
+    calibrate_on_rank0(model, cal_batches())  # (a custom error table travels with the quantizer state)
     bn_batches = None
     if args.reestimate_bn_stats:
         from .bn_reestimate import reestimate_bn_stats
@@ -283,6 +286,9 @@ def approx_cfg(args):
         # the res quantizer through the original_quantize_res branch
         cfg["run_method"] = dict(approx_flag=False, quantize_after_mult_and_add=False, res_quantizer_flag=True,
                                  original_quantize_res=True)
+    if getattr(args, "error_table", None):
+        from .error_tables import load_error_table
+        cfg["error_table"] = load_error_table(args.error_table, args.mant_width)  # read once, here
     return cfg
 
 
@@ -302,7 +308,10 @@ def main(argv=None):
     model = build_model(args.arch, args.weights, cfg, args.image_size).to(dev).eval()
     res = validate(model, val, train, args, dev, rank, ws, source)
     if rank == 0:
-        res["approx_params"] = cfg
+        from .error_tables import table_digest
+        tab = cfg.get("error_table")
+        res["approx_params"] = {k: v for k, v in cfg.items() if k != "error_table"}
+        res["error_table_digest"] = table_digest(tab) if tab is not None else None
         print(json.dumps(res), flush=True)
         if args.output:
             with open(args.output, "w") as f:

@@ -471,7 +471,8 @@ int fp8a_word_image_init(void *image, int64_t Bn, int64_t C, int64_t H, int64_t 
  * Results are bit-identical to the unchained calls.  workspace: fp8a_conv2d_block_workspace_size().
  */
 /* The word image a convolution of this shape / format would read as in_image: 1 = the matrix-core
- * path's (ungrouped, Cout > 1, E4M3 / E5M2 with s2n + qbma and a {0,1} or zero table, not a 1x1
+ * path's (ungrouped, Cout > 1, E4M3 / E5M2 with s2n + qbma and a table without negative entries whose
+ * significand products stay positive -- the zero table, the built-in {0,1} table, a custom one --, not a 1x1
  * unpadded convolution staged from fp32; images of its padding), 2 = the tensor-bias table form's
  * (single-output-channel groups, 3-wide undilated rows, stride 1 / 2; images with ph = pw = 0),
  * 3 = the v5 matrix-core form's (unpadded convolutions), 0 = none: emitting an image for it would
