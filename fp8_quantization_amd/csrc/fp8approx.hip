@@ -365,7 +365,8 @@ __global__ __launch_bounds__(256) void conv_tb_direct_kernel(const float *x, con
 // with_s2nn2s_opt on, golden_clip_OF off, the term is then
 //   v0 = a*b - T[mA][mB] * cA * cB * 2^-M                         (exact, as in the GEMM)
 //   sign quirk F7: Q_R(g) is 0 only in the binade 2^-bR (expo 0, mantissa rounding to 0), where
-//                  a negative g gives the term |v0|
+//                  a negative g gives the term |v0| (with quant_btw_mult_accu only: without it g
+//                  is not quantized and the term keeps g's sign)
 //   Q_R, tb form: round at the value's own binade with the F6 clamp, except in the binade
 //                  [2^-bR, 2^(1-bR)) (expo field 0), whose decode is 2^(1-bR) * m / 2^M, i.e.
 //                  2 * (Q(x) - sign * 2^-bR)
@@ -424,9 +425,10 @@ __global__ __launch_bounds__(256) void conv_tb_fast_kernel(const float *x, const
                 const float b = sw_v[k];
                 const float gq = a * b;  // exact
                 float v = __fmaf_rn(-sT[mA * n + sw_m[k]], cA * sw_c[k], gq);
-                // F7: Q_R(g) == 0 (so the sign is +) only for |g| in [2^-bR, 2^-bR (1 + 2^-(M+1))]
+                // F7: Q_R(g) == 0 (so the sign is +) only for |g| in [2^-bR, 2^-bR (1 + 2^-(M+1))]; without
+                // quant_btw_mult_accu the sign is that of the unquantized g (v9:35-36, 68)
                 const float ag = fabsf(gq);
-                if (gq < 0.0f && ag >= zlo && ag <= zhi) v = fabsf(v);
+                if (qbma && gq < 0.0f && ag >= zlo && ag <= zhi) v = fabsf(v);
                 if (qbma) {
                     const uint32_t pb = __float_as_uint(v) & 0x7F800000u;
                     const float pe = __uint_as_float(pb);

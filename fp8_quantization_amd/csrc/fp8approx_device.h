@@ -20,8 +20,15 @@ enum : uint32_t { F_APPROX = 1u, F_S2N = 2u, F_QBMA = 4u, F_GCLIP = 8u, F_TB = 1
 
 __device__ __forceinline__ float p2(int k) { return ldexpf(1.0f, k); }
 
-// param_prepare (v9:189-229).  Int bias: Python float powers.  Tensor bias (tb): 2**(negative)
-// is an integer power and evaluates to 0 (quirk F5).
+// torch's 2**k for an int32 tensor k: an integer power in int32 arithmetic -- 0 for a negative
+// exponent (quirk F5), -2^31 at k = 31, 0 above.
+__device__ __forceinline__ float ipow2_i32(int k) {
+    return (k < 0 || k >= 32) ? 0.0f : (k == 31) ? -2147483648.0f : (float)(1u << k);
+}
+
+// param_prepare (v9:189-229).  Int bias: Python float powers.  Tensor bias (tb): int32 powers
+// (ipow2_i32), so min_norm is 0 once b >= 2 and max_norm is 0 once maxe - b >= 32 (negative at 31:
+// under golden_clip_OF every value then counts as overflow).
 struct DFmt {
     float mn;   // min_norm
     float mx;   // max_norm
@@ -39,8 +46,8 @@ __device__ __forceinline__ DFmt dfmt(int E, int M, int b, bool tb) {
         f.mn = p2(1 - b);
         f.mx = ldexpf(frac, f.maxe - b);
     } else {
-        f.mn = (1 - b >= 0) ? p2(1 - b) : 0.0f;
-        f.mx = (f.maxe - b >= 0) ? p2(f.maxe - b) * frac : 0.0f;
+        f.mn = ipow2_i32(1 - b);
+        f.mx = ipow2_i32(f.maxe - b) * frac;
     }
     return f;
 }

@@ -30,9 +30,17 @@
  * torch.ldexp(x, k) (= x * pow(2.0, k)). */
 static float pow2f(int k) { return ldexpf(1.0f, k); }
 
+/* torch's 2**k for an int32 tensor k: an INTEGER power in int32 arithmetic.  A negative exponent gives
+ * 0 (quirk F5); 2^31 wraps to -2^31 and every higher power to 0. */
+static float ipow2_i32(int k) {
+    if (k < 0 || k >= 32) return 0.0f;
+    return (k == 31) ? -2147483648.0f : (float)(1u << k);
+}
+
 /* param_prepare, approx_matmul_whole_v9.py:189-229.  With an int bias the powers are
- * Python floats; with an int32 tensor bias (tb) 2**(negative) is an INTEGER power and
- * evaluates to 0 (quirk F5), so min_norm = 0 once b >= 2. */
+ * Python floats; with an int32 tensor bias (tb) they are int32 powers (ipow2_i32), so
+ * min_norm = 0 once b >= 2, and max_norm = 0 once max_expo - b >= 32 (negative at 31): with
+ * golden_clip_OF every nonzero value (at 31: every value) then counts as overflow. */
 typedef struct {
     int E, M, b, tb;
     float min_norm, max_norm;
@@ -49,8 +57,8 @@ static orc_fmt orc_param(int E, int M, int b, int tb) {
         p.min_norm = (float)ldexp(1.0, 1 - b);
         p.max_norm = (float)(ldexp(1.0, p.max_expo - b) * frac);
     } else {
-        p.min_norm = (1 - b >= 0) ? (float)ldexp(1.0, 1 - b) : 0.0f;
-        p.max_norm = (p.max_expo - b >= 0) ? (float)ldexp(1.0, p.max_expo - b) * (float)frac : 0.0f;
+        p.min_norm = ipow2_i32(1 - b);
+        p.max_norm = ipow2_i32(p.max_expo - b) * (float)frac;
     }
     return p;
 }
