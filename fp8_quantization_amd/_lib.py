@@ -28,7 +28,7 @@ SYMBOLS = ("fp8a_version", "fp8a_last_error", "fp8a_fallback_stats", "fp8a_path_
            "fp8a_flag_arena_slot_bytes",
            "fp8a_check_workspace_size", "fp8a_matmul_check", "fp8a_conv2d_check_workspace_size", "fp8a_conv2d_check",
            "fp8a_fp8_mse_workspace_size", "fp8a_fp8_mse_search", "fp8a_fq_selfcheck",
-           "fp8a_bn_train_workspace_size", "fp8a_bn_train")
+           "fp8a_bn_train_workspace_size", "fp8a_bn_train", "fp8a_bmm", "fp8a_bmm_stats")
 
 _lib = None
 
@@ -113,6 +113,9 @@ def load():
         "fp8a_fq_selfcheck": ([F, I, I, I, I, I, ctypes.c_uint64, ctypes.c_uint64, P, P], I),
         "fp8a_bn_train_workspace_size": ([I64, I64, I64], SZ),
         "fp8a_bn_train": ([P, P, I64, I64, I64, P, P, F, F, P, P, P, P, P, I, F, F, P, I, I, I, P, P, P, SZ, P], I),
+        "fp8a_bmm": ([P, P, P, I64, I64, I64, I64, I64, I64, I64, I64, I64, I64, I64, I64, I64, I64, I64, I, I, P, P, I64,
+                      P, P, U, P], I),
+        "fp8a_bmm_stats": ([P, I], I),
     }
     for name, (args, res) in sig.items():
         f = getattr(L, name)
@@ -252,6 +255,15 @@ def splitk_stats(reset=False):
     out = (ctypes.c_uint64 * 1)()
     check(L.fp8a_splitk_stats(ctypes.cast(out, ctypes.c_void_p), 1 if reset else 0), "fp8a_splitk_stats")
     return int(out[0])
+
+
+def bmm_stats(reset=False):
+    """fp8a_bmm_stats: dict(launches, tiles, recomputed) -- fp8a_bmm launches and their 64 x 64 output tiles
+    (host-side counters) and the tiles recomputed with the exact term (synchronises the device)."""
+    L = load()
+    out = (ctypes.c_uint64 * 3)()
+    check(L.fp8a_bmm_stats(ctypes.cast(out, ctypes.c_void_p), 1 if reset else 0), "fp8a_bmm_stats")
+    return dict(launches=int(out[0]), tiles=int(out[1]), recomputed=int(out[2]))
 
 
 def clock_stats(reset=False):

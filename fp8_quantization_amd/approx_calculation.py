@@ -12,6 +12,9 @@ per-group, per-output-column Python loop (approx_calculation.py:774-799):
 
 The behaviour lives in mixins so the same run_forward can sit on the reference's own
 QuantizationHijacker / BNFusedHijacker (see ``bind_operator_classes`` and INTEGRATION.md).
+
+QCustomMatMul has no reference counterpart: an activation x activation product batched over
+(image, head) -- attention's QK^T and PV -- through the same multiplier (fp8a_bmm; DESIGN.md §3z').
 """
 import os
 
@@ -22,7 +25,7 @@ import torch.nn.functional as F
 from torch import nn
 
 from . import _lib
-from .approx_ops import (_bias_dev, _res_quant_params, approx_conv2d, approx_conv2d_check, approx_matmul,
+from .approx_ops import (_bias_dev, _res_quant_params, approx_bmm, approx_conv2d, approx_conv2d_check, approx_matmul,
                          approx_matmul_block, approx_matmul_check, bias_epilogue, dense_conv2d, dense_format,
                          dense_matmul, format_self_check, grouped_conv2d, make_flags, make_flags_v5, qamaa_conv2d,
                          qamaa_matmul)
@@ -39,8 +42,9 @@ DENSE_EXACT = os.environ.get("FP8A_DENSE", "1") != "0"
 
 # (the hijacker bases too: the reference's replace_operations_with_approx_ops takes them from its
 # `from approx.approx_calculation import *`, INTEGRATION.md §3 Option A)
-__all__ = ["QCustomBNConv2dTorch", "QCustomLinearTorch", "QCustomConv2dTorch", "ApproxOpMixin",
-           "ApproxConv2dMixin", "ApproxLinearMixin", "ExactConv2dMixin", "bind_operator_classes",
+__all__ = ["QCustomBNConv2dTorch", "QCustomLinearTorch", "QCustomConv2dTorch", "QCustomMatMul", "ApproxOpMixin",
+           "ApproxConv2dMixin", "ApproxLinearMixin", "ApproxMatMulMixin", "ExactConv2dMixin", "bind_operator_classes",
+           "bind_matmul_class",
            "QuantizationHijacker", "BNFusedHijacker", "QuantizationManager",
            "QuantizedActivation", "QuantizedModule", "activations_set"]
 
@@ -362,6 +366,69 @@ class ApproxLinearMixin(ApproxOpMixin):
         return out
 
 
+class ApproxMatMulMixin(ApproxOpMixin):
+    """forward(a, b) of QCustomMatMul: an activation x activation product batched over one or two leading
+    dims (attention's QK^T and PV) through the approx multiplier -- one fp8a_bmm launch.  The reference has
+    no quantized matmul module; the arithmetic per term is v9's, and the quantizers sit where
+    QuantizationHijacker._core puts a layer's: both operands through per-tensor activation quantizers
+    (``a_quantizer``, ``b_quantizer``: bA, bB), the calibration / original_quantize_res product through
+    ``res_quantizer`` (which gives the product its bR), the approx result returned unquantized.
+
+    Not supported here: quantize_after_mult_and_add and approx_version 5 (NotImplementedError);
+    self_check_mode is ignored (no error_report rows for these products)."""
+
+    def _init_matmul_quantizers(self):
+        mk = dict(qmethod=self.act_method, init=self.act_range_method, qparams=self.act_qparams,
+                  range_estim_params=self.act_range_options)
+        self.a_quantizer = QuantizationManager(**mk)
+        self.b_quantizer = QuantizationManager(**mk)
+        self.res_quantizer = QuantizationManager(**mk)
+        self._check_supported()
+
+    _check_res_flag = QuantizationHijacker._check_res_flag
+
+    def _check_supported(self):
+        name = type(self).__name__
+        if self.quantize_after_mult_and_add:
+            raise NotImplementedError(f"{name}: quantize_after_mult_and_add has no batched product")
+        if (self.custom_approx_params or {}).get("approx_version", 9) == 5:
+            raise NotImplementedError(f"{name}: approx_version 5 has no batched product")
+
+    def forward(self, a, b, out=None):
+        """a [..., M, K] @ b [..., K, N] (any views: heads cut from [B, S, H*d], a transposed b); out: None, or
+        the view (unit n stride) that receives the product."""
+        self._check_supported()
+        if self._qa():
+            a = self.a_quantizer(a)
+            b = self.b_quantizer(b)
+        res = None
+        if not self.fix_ranges_flag or self.original_quantize_res:
+            res = torch.matmul(a, b)
+            if self._qa() and self.res_quantizer_flag:
+                res = self.res_quantizer(res)
+        if self.res_quantizer_flag and self.approx_flag:
+            E, M, table, flags = self._approx_config()
+            dev = a.device
+            res = approx_bmm(a.detach(), b.detach(), E, M, self._default_bias(self.a_quantizer.get_fp_bias(), E, dev),
+                             self._default_bias(self.b_quantizer.get_fp_bias(), E, dev),
+                             self._default_bias(self.res_quantizer.get_fp_bias(), E, dev), table, flags=flags, out=out)
+        self._check_res_flag()
+        if res is None:  # (as the hijacker: fixed ranges with no product selected)
+            raise UnboundLocalError("local variable 'res' referenced before assignment")
+        if out is not None and res is not out:
+            out.copy_(res)
+            res = out
+        return res
+
+
+def bind_matmul_class(module_cls=QuantizedModule):
+    """QCustomMatMul on top of any QuantizedModule implementation exposing the reference surface."""
+    def __init__(self, *args, **kwargs):
+        module_cls.__init__(self, *args, **kwargs)
+        self._init_matmul_quantizers()
+    return type("QCustomMatMul", (ApproxMatMulMixin, module_cls), {"__init__": __init__})
+
+
 def bind_operator_classes(hijacker_cls=QuantizationHijacker, bnfused_cls=BNFusedHijacker):
     """Build the three operator classes on top of any hijacker implementation exposing the
     reference surface (get_*_fp_bias, approx_flag, custom_approx_params, ...)."""
@@ -381,3 +448,9 @@ class QCustomLinearTorch(ApproxLinearMixin, QuantizationHijacker, nn.Linear):
 
 class QCustomConv2dTorch(ExactConv2dMixin, QuantizationHijacker, nn.Conv2d):
     pass
+
+
+class QCustomMatMul(ApproxMatMulMixin, QuantizedModule):
+    def __init__(self, *args, **kwargs):
+        super().__init__(*args, **kwargs)
+        self._init_matmul_quantizers()

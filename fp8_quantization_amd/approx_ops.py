@@ -21,7 +21,7 @@ from torch import nn
 from . import _lib
 from .error_tables import get_error_table_NN  # noqa: F401  (re-exported, v9:555)
 
-__all__ = ["custom_matmul_vectorize", "approx_matmul", "approx_matmul_block", "approx_terms", "approx_conv2d", "qamaa_matmul", "qamaa_conv2d",
+__all__ = ["custom_matmul_vectorize", "approx_matmul", "approx_bmm", "approx_matmul_block", "approx_terms", "approx_conv2d", "qamaa_matmul", "qamaa_conv2d",
            "quant_to_fp_any_vectorize_torch", "float_to_fpany_absint_torch", "get_error_table_NN",
            "make_flags", "make_flags_v5", "fp8_fake_quantize", "bn_act_epilogue", "dense_format", "dense_matmul",
            "dense_conv2d", "grouped_conv2d", "dense_conv2d_fused", "approx_matmul_check", "approx_conv2d_check",
@@ -159,6 +159,71 @@ def approx_matmul(A, B, E, M, bA, bB, bR, table=None, flags=None, **flag_kwargs)
     C = _matmul_op(A, B, _bias_dev(bA, dev), bB_, _bias_dev(bR, dev), tab, int(E), int(M), int(flags))
     _prof_end(ev, A.shape[0] * A.shape[1] * B.shape[1])
     return C
+
+
+# ----------------------------------------------------------------------------------- batched matmul
+def _bmm_view(t, what):
+    """(nb0, nb1, s0, s1) of a [b, r, c] / [b0, b1, r, c] view: the two-stride batch form."""
+    if t.dim() == 3:
+        return 1, t.shape[0], 0, t.stride(0)
+    if t.dim() == 4:
+        return t.shape[0], t.shape[1], t.stride(0), t.stride(1)
+    raise AssertionError(f"approx_bmm: {what} needs one or two leading batch dims, got {tuple(t.shape)}")
+
+
+@torch.library.custom_op("fp8approx::bmm", mutates_args=("out",))
+def _bmm_op(A: torch.Tensor, B: torch.Tensor, out: torch.Tensor, bA: torch.Tensor, bB: torch.Tensor,
+            bR: torch.Tensor, table: torch.Tensor, E: int, M: int, flags: int) -> None:
+    L = _lib.load()
+    nb0, nb1, sa0, sa1 = _bmm_view(A, "A")
+    _, _, sb0, sb1 = _bmm_view(B, "B")
+    _, _, sc0, sc1 = _bmm_view(out, "out")
+    Mr, K = A.shape[-2:]
+    N = B.shape[-1]
+    bBs = 0 if bB.numel() == 1 else 1
+    rc = L.fp8a_bmm(_lib.dev_ptr(A), _lib.dev_ptr(B), _lib.dev_ptr(out), nb0, nb1, Mr, N, K,
+                    A.stride(-2), sa0, sa1, B.stride(-2), B.stride(-1), sb0, sb1, out.stride(-2), sc0, sc1,
+                    E, M, _lib.dev_ptr(bA), _lib.dev_ptr(bB), bBs, _lib.dev_ptr(bR), _lib.host_ptr(table), flags,
+                    _lib.stream_ptr(A.device))
+    _lib.check(rc, "fp8a_bmm")
+
+
+@_bmm_op.register_fake
+def _(A, B, out, bA, bB, bR, table, E, M, flags):
+    return None
+
+
+def approx_bmm(A, B, E, M, bA, bB, bR, table=None, flags=None, out=None, **flag_kwargs):
+    """C[..., m, n] = sum_k approx_v9 term(A[..., m, k], B[..., k, n]) on the GPU, one launch for all batch items.
+
+    A [..., M, K] and B [..., K, N] float32 device tensors with one or two equal leading batch dims.  Views are
+    consumed in place -- head views cut from [B, S, H*d] buffers, a transposed B -- as long as A's k stride
+    is 1 (else a contiguous copy is taken).  bA, bR: int or 1-element tensor; bB: int, 1-element or per-column
+    [N] tensor.  out: None, or a float32 view of C's shape with unit n stride that does not overlap A or B
+    (attention writes its context straight into [B, S, H, d]).  Returns C (out when given).
+    """
+    if A.dim() not in (3, 4) or A.dim() != B.dim() or A.shape[:-2] != B.shape[:-2] or A.shape[-1] != B.shape[-2]:
+        raise AssertionError(f"approx_bmm: shape mismatch {tuple(A.shape)} @ {tuple(B.shape)}")  # v9:20
+    if flags is None:
+        flags = make_flags(**flag_kwargs)
+    A, B = _as_f32(A), _as_f32(B)
+    if A.stride(-1) != 1 and A.shape[-1] > 1:
+        A = A.contiguous()
+    shape = tuple(A.shape[:-1]) + (B.shape[-1],)
+    dev = A.device
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=dev)
+    elif tuple(out.shape) != shape or out.dtype != torch.float32 or out.device != dev or \
+            (out.stride(-1) != 1 and shape[-1] > 1):
+        raise AssertionError(f"approx_bmm: out must be a float32 {shape} view with unit n stride on {dev}")
+    tab = _table_host(table, M, _uses_table(flags))
+    bB_ = _bias_dev(bB, dev)
+    if bB_.numel() not in (1, B.shape[-1]):
+        raise AssertionError(f"approx_bmm: {bB_.numel()} column biases for {B.shape[-1]} columns")
+    ev = _prof_start()
+    _bmm_op(A, B, out, _bias_dev(bA, dev), bB_, _bias_dev(bR, dev), tab, int(E), int(M), int(flags))
+    _prof_end(ev, A.numel() * B.shape[-1])
+    return out
 
 
 @torch.library.custom_op("fp8approx::matmul_block", mutates_args=())

@@ -31,6 +31,7 @@
 #include "gemm_check.h"
 #include "fq_mse.h"
 #include "bn_train.h"
+#include "gemm_bmm.h"
 
 // (defined with C linkage below; run_gemm launches it too)
 extern "C" __global__ void fq_bias_kernel(fp8a::FqIn fq, float *bias_out, int32_t *ibias_out);
@@ -1899,6 +1900,85 @@ int fp8a_matmul(const float *A, int64_t lda, const float *B, int64_t sbk, int64_
     if (lda < K || ldc < N) return fail(FP8A_EINVAL, "leading dimension smaller than extent");
     GemmArgs a = make_args(A, lda, B, sbk, sbn, C, ldc, M, N, K, E, Mw, bA, bB, bB_stride, bR, flags);
     return run_gemm(a, table, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+// ------------------------------------------------------------------------- batched product
+// fp8a_bmm (gemm_bmm.h): one launch of gemm_bmm_kernel over (64 x 64 tiles, batch items); nothing else on
+// the stream -- no workspace, no pre-pass, no gated kernel -- so it is capture-safe by construction.
+static std::atomic<uint64_t> g_bmm_launches, g_bmm_tiles;  // host-side (a replayed graph adds nothing)
+
+// elements spanned by a (batch, batch, rows, cols) view of non-negative strides
+static int64_t bmm_span(int64_t n0, int64_t s0, int64_t n1, int64_t s1, int64_t r, int64_t sr, int64_t c, int64_t sc) {
+    return (n0 - 1) * s0 + (n1 - 1) * s1 + (r - 1) * sr + (c - 1) * sc + 1;
+}
+
+int fp8a_bmm(const float *A, const float *B, float *C, int64_t nb0, int64_t nb1, int64_t M, int64_t N, int64_t K,
+             int64_t lda, int64_t sa0, int64_t sa1, int64_t sbk, int64_t sbn, int64_t sb0, int64_t sb1, int64_t ldc,
+             int64_t sc0, int64_t sc1, int E, int Mw, const int32_t *bA, const int32_t *bB, int64_t bB_stride,
+             const int32_t *bR, const int32_t *table, uint32_t flags, fp8a_stream_t stream) {
+    int rc = check_format(E, Mw);
+    if (rc) return rc;
+    if (nb0 < 0 || nb1 < 0 || M < 0 || N < 0 || K < 0) return fail(FP8A_EINVAL, "fp8a_bmm: negative extent");
+    if (flags & F_TB)
+        return fail(FP8A_EINVAL, "fp8a_bmm: no tensor-bias semantics (FP8A_TB) for a batched product");
+    if (flags & (F_V5 | F_OFUF | F_OF | F_UF))
+        return fail(FP8A_EINVAL, "fp8a_bmm: the v5 model is not implemented for a batched product");
+    if (flags & ~(F_APPROX | F_S2N | F_QBMA | F_GCLIP)) return fail(FP8A_EINVAL, "fp8a_bmm: unknown flag bits");
+    if (bB_stride != 0 && bB_stride != 1) return fail(FP8A_EINVAL, "fp8a_bmm: bB_stride must be 0 or 1");
+    if (lda < 0 || sa0 < 0 || sa1 < 0 || sbk < 0 || sbn < 0 || sb0 < 0 || sb1 < 0 || ldc < 0 || sc0 < 0 || sc1 < 0)
+        return fail(FP8A_EINVAL, "fp8a_bmm: negative stride");
+    if ((M > 1 && lda < K) || (M > 1 && ldc < N)) return fail(FP8A_EINVAL, "leading dimension smaller than extent");
+    TablePack tp;
+    int mode;
+    rc = pack_table(table, Mw, (flags & F_APPROX) != 0, tp, mode);
+    if (rc) return rc;
+    const int64_t nb = nb0 * nb1;
+    if (nb == 0 || M == 0 || N == 0) return FP8A_OK;
+    if (!C || (K > 0 && (!A || !B || !bA || !bB || !bR))) return fail(FP8A_EINVAL, "fp8a_bmm: null pointer");
+    if (K > 0) {  // C over an operand, where that is cheap to see: the same base, or two dense spans that meet
+        const int64_t ea = bmm_span(nb0, sa0, nb1, sa1, M, lda, K, 1), eb = bmm_span(nb0, sb0, nb1, sb1, K, sbk, N, sbn),
+                      ec = bmm_span(nb0, sc0, nb1, sc1, M, ldc, N, 1);
+        const bool dc = ec == nb * M * N;
+        const bool oa = C == A || (dc && ea == nb * M * K && C < A + ea && A < C + ec);
+        const bool ob = C == B || (dc && eb == nb * K * N && C < B + eb && B < C + ec);
+        if (oa || ob) return fail(FP8A_EINVAL, "fp8a_bmm: C overlaps an operand");
+    }
+    BmmArgs a;
+    memset(&a, 0, sizeof(a));
+    a.A = A; a.B = B; a.C = C; a.nb1 = nb1; a.M = M; a.N = N; a.K = K;
+    a.lda = lda; a.sa0 = sa0; a.sa1 = sa1; a.sbk = sbk; a.sbn = sbn; a.sb0 = sb0; a.sb1 = sb1;
+    a.ldc = ldc; a.sc0 = sc0; a.sc1 = sc1;
+    a.num_mt = (M + BM - 1) / BM;
+    a.tiles = a.num_mt * ((N + BN - 1) / BN);
+    a.E = E; a.Mw = Mw; a.kexp = 0x7F800000u; a.kdc = (uint32_t)(23 - Mw) << 23;
+    a.bA = bA; a.bB = bB; a.bBs = bB_stride; a.bR = bR; a.flags = flags;
+    a.tab = tp;
+    a.recount = bmm_recount_ptr();
+    if (a.recount == nullptr) return fail(FP8A_EHIP, "fp8a_bmm: the recomputed-tile counter's address");
+    if (a.tiles > 0x7FFFFFFFll / nb) return fail(FP8A_EINVAL, "fp8a_bmm: more than 2^31 - 1 tiles");
+    if (f8_form(E, Mw, flags, tp)) mode = TM_F8;
+    const dim3 grid((unsigned)(a.tiles * nb));
+    const bool s2n = flags & F_S2N, q = flags & F_QBMA, gc = flags & F_GCLIP;
+    hipStream_t s = (hipStream_t)stream;
+    if (s2n) q ? launch_bmm_p3(mode, gc, a, grid, s) : launch_bmm_p2(mode, gc, a, grid, s);
+    else q ? launch_bmm_p1(mode, gc, a, grid, s) : launch_bmm_p0(mode, gc, a, grid, s);
+    ++g_bmm_launches;
+    g_bmm_tiles += (uint64_t)(a.tiles * nb);
+    return hip_check("fp8a_bmm launch");
+}
+
+int fp8a_bmm_stats(uint64_t out[3], int reset) {
+    if (out == nullptr) return fail(FP8A_EINVAL, "null pointer");
+    unsigned long long r = 0;
+    if (hipDeviceSynchronize() != hipSuccess || bmm_recount_read(&r, reset != 0) != 0) return hip_check("fp8a_bmm_stats");
+    out[0] = g_bmm_launches.load();
+    out[1] = g_bmm_tiles.load();
+    out[2] = r;
+    if (reset) {
+        g_bmm_launches = 0;
+        g_bmm_tiles = 0;
+    }
+    return FP8A_OK;
 }
 
 int fp8a_terms(const float *A, int64_t lda, const float *B, int64_t sbk, int64_t sbn, float *T, int64_t M,

@@ -130,6 +130,8 @@ def mini_test_batches(n_batches_total, num_batches=10, start_index=5, step=300):
 
 def build_model(arch, weights, cfg, image_size=224):
     from . import resnet_workload as rw
+    if cfg.get("approx_attention") and arch != "vit_b16":
+        raise ValueError(f"--approx-attention: {arch} has no attention (ViT architectures only)")
     if arch == "resnet18":
         return rw.resnet18_approx(weights=weights, **cfg)
     if arch == "resnet50":
@@ -180,6 +182,8 @@ def parse(argv=None):
     ap.add_argument("--error-table", default=None, metavar="FILE",
                     help="a custom error table (.npy, or text rows: '.' = 0, '-' = -1, digits) in place of the "
                          "built-in one: error_tables.load_error_table")
+    ap.add_argument("--approx-attention", action="store_true",
+                    help="ViT only: QK^T and PV of every attention through the approx multiplier (batched products)")
     ap.add_argument("--output", default=None, help="also write the result JSON here")
     return ap.parse_args(argv)
 
@@ -251,7 +255,8 @@ def validate(model, val, train, args, dev, rank=0, ws=1, source=""):
     return dict(arch=args.arch, data=source, images=seen, top_1_accuracy=correct1 / max(1, seen),
                 top_5_accuracy=correct5 / max(1, seen), loss=loss_sum / max(1, seen), images_per_s=seen / elapsed,
                 n_gpus=ws, evaluate_param="mini_test" if args.mini_test else "full_test",
-                reestimate_bn_stats=bool(args.reestimate_bn_stats), bn_batches=bn_batches)
+                reestimate_bn_stats=bool(args.reestimate_bn_stats), bn_batches=bn_batches,
+                approx_attention=bool(getattr(args, "approx_attention", False)))
 
 
 def _n_batches(ds, batch):
@@ -286,6 +291,8 @@ def approx_cfg(args):
         # the res quantizer through the original_quantize_res branch
         cfg["run_method"] = dict(approx_flag=False, quantize_after_mult_and_add=False, res_quantizer_flag=True,
                                  original_quantize_res=True)
+    if getattr(args, "approx_attention", False):
+        cfg["approx_attention"] = True
     if getattr(args, "error_table", None):
         from .error_tables import load_error_table
         cfg["error_table"] = load_error_table(args.error_table, args.mant_width)  # read once, here

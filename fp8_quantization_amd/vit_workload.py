@@ -18,13 +18,16 @@ Extension over the reference: its encoder linears receive [B, 197, 768] inputs a
 2-D assertion of custom_matmul_vectorize under approx_flag; here every approx linear
 of the model folds the leading dims into rows (``flatten_leading_dims``), so each token row gets
 exactly the approx product the reference computes for a 2-D input.  Attention (softmax(QK^T)V)
-is the reference's plain fp32 SDPA (vit_quantized_approx.py:188-196), not an approx product.
+is the reference's plain fp32 SDPA (vit_quantized_approx.py:188-196), not an approx product --
+unless ``approx_attention=True`` (second extension, opt-in): then QK^T and PV of every layer run
+through the approx multiplier as batched products (QCustomMatMul, one fp8a_bmm launch each) with
+the softmax between them in fp32 torch.
 """
 import torch
 import torch.nn.functional as F
 from torch import nn
 
-from .approx_calculation import QCustomLinearTorch
+from .approx_calculation import QCustomLinearTorch, QCustomMatMul
 from .model_wrap import QuantizedModel, fused_linear_tail, quantize_model
 from .quantization.base_quantized_classes import QuantizedActivation
 
@@ -274,7 +277,32 @@ class QuantizedViTSelfAttention(QuantizedActivation):
         self.training = orig.training
         self.attention_probs_dropout_prob = orig.attention_probs_dropout_prob
 
+    def enable_approx_attention(self, **quant_params):
+        """QK^T and PV as approx products: the two QCustomMatMul operators (``approx_attention``)."""
+        self.qk_matmul = QCustomMatMul(**quant_params)
+        self.pv_matmul = QCustomMatMul(**quant_params)
+
+    def _approx_attention(self, x):
+        """scores = qk_matmul(q, k^T), probs = softmax(scores / sqrt(d)) in fp32, ctx = pv_matmul(probs, v): the
+        per-head operands are views of the linears' [B, S, H*d] outputs and the context is written in that
+        layout -- no permute copies."""
+        H, d = self.num_attention_heads, self.attention_head_size
+
+        def heads(t):
+            return t.view(t.shape[:-1] + (H, d)).permute(0, 2, 1, 3)
+        q, k, v = heads(self.query(x)), heads(self.key(x)), heads(self.value(x))
+        scores = self.qk_matmul(q, k.transpose(-1, -2))
+        probs = torch.softmax(scores * d ** -0.5, dim=-1)
+        p = self.attention_probs_dropout_prob
+        if self.training and p > 0:
+            probs = F.dropout(probs, p, True)
+        ctx = torch.empty(x.shape[:-1] + (H, d), dtype=torch.float32, device=x.device)
+        self.pv_matmul(probs, v, out=ctx.permute(0, 2, 1, 3))
+        return ctx.view(x.shape[:-1] + (self.all_head_size,))
+
     def forward(self, x):
+        if hasattr(self, "qk_matmul"):
+            return self.quantize_activations(self._approx_attention(x))
         return self.quantize_activations(_attention(self, x))
 
 
@@ -357,23 +385,33 @@ class QuantizedViTModel(QuantizedActivation):
 
 class QuantizedVisionTransformerForImageClassification(QuantizedModel):
     """vit_quantized_approx.py:367-391.  ``flatten_token_rows`` (default on) is the F4
-    extension above; off, the encoder linears raise AssertionError like the reference's."""
+    extension above; off, the encoder linears raise AssertionError like the reference's.
+    ``approx_attention`` (default off: the module tree, state-dict keys and logits of the model
+    without it) gives every self-attention its ``qk_matmul`` / ``pv_matmul`` approx operators."""
 
     def __init__(self, model_fp, input_size=(1, 3, 224, 224), quant_setup=None, flatten_token_rows=True,
-                 **quant_params):
+                 approx_attention=False, **quant_params):
         super().__init__(input_size)
+        self.approx_attention = bool(approx_attention)
+        if approx_attention and not (quant_params.get("run_method") or {}).get("approx_flag", False):
+            raise ValueError("approx_attention needs run_method['approx_flag']: it routes QK^T and PV through the "
+                             "approx multiplier")
         self.vit = quantize_model(model_fp.vit, specials={ViTModel: QuantizedViTModel}, **quant_params)
         self.classifier = quantize_model(model_fp.classifier, **quant_params)
         for m in self.modules():
             if isinstance(m, QCustomLinearTorch):
                 m.flatten_leading_dims = flatten_token_rows
+        if approx_attention:
+            for m in list(self.modules()):
+                if isinstance(m, QuantizedViTSelfAttention):
+                    m.enable_approx_attention(**quant_params)
 
     def forward(self, x):
         return self.classifier(self.vit(x)[:, 0, :])
 
 
 def vit_b16_approx(weights=None, image_size=224, patch_size=16, hidden=768, layers=12, heads=12, mlp=3072,
-                   num_labels=1000, flatten_token_rows=True, seed=None, **cfg):
+                   num_labels=1000, flatten_token_rows=True, approx_attention=False, seed=None, **cfg):
     """The reference's vit_quantized_approx (vit_quantized_approx.py:394-398) with random-init
     (or locally loaded) weights instead of ``from_pretrained``."""
     from .resnet_workload import approx_qparams, load_float_weights
@@ -385,14 +423,18 @@ def vit_b16_approx(weights=None, image_size=224, patch_size=16, hidden=768, laye
     assert hidden % heads == 0 and image_size % patch_size == 0
     return QuantizedVisionTransformerForImageClassification(fp, input_size=(1, 3, image_size, image_size),
                                                             flatten_token_rows=flatten_token_rows,
+                                                            approx_attention=approx_attention,
                                                             **approx_qparams(**cfg))
 
 
-def vit_approx_macs_per_image(image_size=224, patch_size=16, hidden=768, layers=12, mlp=3072, num_labels=1000):
+def vit_approx_macs_per_image(image_size=224, patch_size=16, hidden=768, layers=12, mlp=3072, num_labels=1000,
+                              approx_attention=False):
     """Approx-MACs of one image: per layer Q, K, V, attention output (T x D x D each) and the
-    MLP (2 x T x D x mlp), plus the classifier on the class token; T = patches + 1."""
+    MLP (2 x T x D x mlp), plus the classifier on the class token; T = patches + 1.  With
+    approx_attention also QK^T and PV of every head (2 x T x T x D per layer)."""
     T = (image_size // patch_size) ** 2 + 1
-    return layers * (4 * T * hidden * hidden + 2 * T * hidden * mlp) + hidden * num_labels
+    attn = layers * 2 * T * T * hidden if approx_attention else 0
+    return layers * (4 * T * hidden * hidden + 2 * T * hidden * mlp) + hidden * num_labels + attn
 
 
 __all__ = ["ViTForImageClassification", "QuantizedVisionTransformerForImageClassification", "vit_b16_approx",

@@ -273,6 +273,36 @@ int fp8a_matmul(const float *A, int64_t lda, const float *B, int64_t sbk, int64_
                 fp8a_stream_t stream);
 
 /*
+ * The batched approx product (activation x activation: attention's QK^T and PV), one launch over
+ * nb0 x nb1 batch items with two batch strides per operand, so per-head operands are read straight
+ * out of [B, S, H*d] buffers and the context is written straight into one:
+ *   C(i0,i1,m,n) = sum_k term(A(i0,i1,m,k), B(i0,i1,k,n))
+ *   A(i0,i1,m,k) = A[i0*sa0 + i1*sa1 + m*lda + k]
+ *   B(i0,i1,k,n) = B[i0*sb0 + i1*sb1 + k*sbk + n*sbn]
+ *   C(i0,i1,m,n) = C[i0*sc0 + i1*sc1 + m*ldc + n]
+ * term is the v9 term with int biases: bA, bR device int32 [1], bB device
+ * int32 with bB_stride 0 (shared) or 1 (per column n); every format, table (custom ones included)
+ * and APPROX / S2N / QBMA / GCLIP combination of the single product.  FP8A_TB and the v5 flags
+ * return FP8A_EINVAL.  Strides are non-negative; C must not overlap A or B.  Asynchronous, no
+ * workspace, no allocation, no host synchronisation, safe under stream capture, deterministic
+ * (fixed k order per output, no float atomics).  A 64 x 64 output tile whose operands are not all
+ * exactly representable in their FP8 codes (or lie outside the fast forms' exactness window) is
+ * recomputed with the exact term inside the same launch.  Empty extents: nb0*nb1 == 0, M == 0 or
+ * N == 0 write nothing; K == 0 writes zeros.
+ * Diagnostics: launches and output tiles since load or the last reset (host-side counters: a
+ * replayed graph adds nothing) and tiles recomputed exactly (device counter; synchronises).
+ */
+int fp8a_bmm(const float *A, const float *B, float *C,
+             int64_t nb0, int64_t nb1, int64_t M, int64_t N, int64_t K,
+             int64_t lda, int64_t sa0, int64_t sa1,
+             int64_t sbk, int64_t sbn, int64_t sb0, int64_t sb1,
+             int64_t ldc, int64_t sc0, int64_t sc1,
+             int E, int Mw,
+             const int32_t *bA, const int32_t *bB, int64_t bB_stride, const int32_t *bR,
+             const int32_t *table, uint32_t flags, fp8a_stream_t stream);
+int fp8a_bmm_stats(uint64_t out[3], int reset);
+
+/*
  * Per-product terms (debug / parity): T[m, k, n] = the value the reference sums at v9:113.
  * Same arguments as fp8a_matmul; T is dense [M][K][N].
  */
