@@ -602,6 +602,11 @@ static int g_opt_xm_sign_rows = getenv("FP8A_XM_SIGN_ROWS") ? atoi(getenv("FP8A_
 // its LDS reads one stage ahead of the conversions that use them (1, the default; gemm_f8mx.h PIPE,
 // DESIGN.md 3x); 0: the loop without it (the same conversions and MFMAs in the same order: the same bits)
 static int g_opt_xm_pipe = getenv("FP8A_XM_PIPE") ? atoi(getenv("FP8A_XM_PIPE")) != 0 : 1;
+// "xm_wave_rows": with "xm_pipe", the 128 x 64 instances (unsplit, or split through the reduce pass) run with
+// the math loop's waves mapped by rows -- wave w the tile's rows 32 w .. 32 w + 31 and all 64 columns, one table
+// address per (row block, K-step) for the four column groups (1, the default; gemm_f8mx.h WROWS, DESIGN.md
+// 3aa); 0: waves by columns (every accumulator the same MFMAs over the same codes in the same order: the same bits)
+static int g_opt_xm_wave_rows = getenv("FP8A_XM_WAVE_ROWS") ? atoi(getenv("FP8A_XM_WAVE_ROWS")) != 0 : 1;
 // "fq_fast": the matrix-core path's fake quantizers (the post quantizer, the emitted words' quantizer,
 // the fused input quantizer of the A pre-pass, the split-K reduction; not the fp32 staging) run
 // fq_apply_fast and the emitted word is formed from the quantized value's bits (fq_word), wherever the
@@ -1146,6 +1151,7 @@ static int run_gemm(GemmArgs &a, const int32_t *table, void *ws, size_t ws_bytes
             a.xncg = tt ? 4 : xm_ncg(a.N);
             a.xm_signs = g_opt_xm_sign_rows;
             a.xm_pipe = g_opt_xm_pipe;
+            a.xm_wave_rows = g_opt_xm_wave_rows;
             // the in-launch split-K sum: the E4M3 matrix-core kernel (the E5M2 form's halved-block rerun
             // writes a tile's partials a second time, after its counter has run out: it keeps the reduce pass)
             a.skcnt = nullptr;
@@ -1551,6 +1557,11 @@ int fp8a_set_option(const char *name, int value) {
     if (strcmp(name, "xm_pipe") == 0) {
         const int old = g_opt_xm_pipe;
         g_opt_xm_pipe = value != 0;
+        return old;
+    }
+    if (strcmp(name, "xm_wave_rows") == 0) {
+        const int old = g_opt_xm_wave_rows;
+        g_opt_xm_wave_rows = value != 0;
         return old;
     }
     if (strcmp(name, "splitk_fixup") == 0) {

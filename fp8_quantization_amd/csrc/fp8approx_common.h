@@ -168,6 +168,8 @@ struct GemmArgs {
     // the same order, inside the launch: skcnt[tile] counts the arrivals (sk_words words after the
     // partials in the workspace, zeroed by xm_decode_b ahead of every launch)
     int splits;
+    int xm_wave_rows;  // host side only (launch_shape, k_f8mx.hip; in what was padding): the 128 x 64 "xm_pipe" instances
+                       // run with the math loop's waves by rows (option "xm_wave_rows", gemm_f8mx.h WROWS; 0: by columns)
     int64_t kchunk;
     float *part;
     uint32_t *skcnt;

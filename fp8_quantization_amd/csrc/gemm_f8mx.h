@@ -636,9 +636,18 @@ template <int NCG, bool EMIT, bool FIX> struct XmPipe { static constexpr int val
 template <> struct XmPipe<4, false, false> { static constexpr int value = XM_PIPE_PLAIN64; };
 template <> struct XmPipe<4, true, false> { static constexpr int value = XM_PIPE_EMIT64; };
 template <bool EMIT> struct XmPipe<1, EMIT, true> { static constexpr int value = 0; };
-template <int NCG, int RB, bool AF32, int XF, bool EMIT, bool FIX = false, int PIPE = 0>
+// WROWS (option "xm_wave_rows"; the word-staged 128 x 64 PIPE instances without the split sum):
+// waves by rows.  The tile, its LDS layout, the staging and the build stay; in the math loop wave w owns tile
+// rows 32 w .. 32 w + 31 (two 16-row blocks) and all four 16-column groups instead of 16 columns of all eight
+// blocks.  The table address (row bits | K-step offset) then has no wave term, and one v_and_or_b32 per (row
+// block, K-step) serves the sixteen table reads of the four column groups (the group in the reads' immediates):
+// per staged tile and lane 2 A pair reads and 4 address ops instead of 8 and 16.  Accumulator dq[4 rb + cg]
+// is (row block 2 w + rb, column group cg); it still takes one MFMA per staged tile, in K order, over the same
+// 128 codes converted from the same table and scale words: the same bits as the mapping by columns.
+template <int NCG, int RB, bool AF32, int XF, bool EMIT, bool FIX = false, int PIPE = 0, bool WROWS = false>
 __global__ __launch_bounds__(256, (XmWaves<AF32, EMIT>::value)) void gemm_f8mx_kernel(const GemmArgs p) {
     static_assert(PIPE == 0 || (!AF32 && XF != 2), "PIPE: the word-staged plain forms only");
+    static_assert(!WROWS || (NCG == 4 && RB == 8 && PIPE != 0 && !FIX), "WROWS: the 128 x 64 PIPE instances");
     using Cf = XmCfg<NCG, RB>;
     constexpr int XM = XmFmt<XF>::M, XB = XmFmt<XF>::XB;
     constexpr int NT = Cf::NT, BMT = Cf::BMT, BNT = Cf::BNT, TTK = Cf::TTK, APR = Cf::APR;
@@ -922,7 +931,91 @@ __global__ __launch_bounds__(256, (XmWaves<AF32, EMIT>::value)) void gemm_f8mx_k
                 const uint32_t tok1 = (uint32_t)min(max(140 + (int)(r1 >> 8) - 128 + p.xm_vmin, 0), 252);
                 thr = thi0 | (thi1 << 8) | (tok0 << 16) | (tok1 << 24);
             }
-            if constexpr (PIPE != 0) {
+            if constexpr (WROWS) {
+                const uint32_t rbase = (uint32_t)(2 * g) * (uint32_t)(TTK * 4);  // (no wave term)
+                auto addr = [&](uint32_t aword) {
+                    uint32_t a;
+                    asm("v_and_or_b32 %0, %1, %2, %3" : "=v"(a) : "v"(aword), "s"(XM_ROW_MASK), "v"(rbase));
+                    return a;
+                };
+                // the four table reads of (column group cg, K-step h): immediates (4 cg + c) * 128 + h * TTK * 4
+                auto tread = [&](uint32_t a, int cg, int h, uint2(&v)[4]) {
+                    __builtin_assume((a & 7u) == 0u);
+                    xm_lds_u64 *ttk = (xm_lds_u64 *)(tt0 + h * TTK * 4 + cg * 512);
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) {
+                        const uint64_t w = ttk[(a >> 3) + 16 * c];
+                        v[c] = make_uint2((uint32_t)w, (uint32_t)(w >> 32));
+                    }
+                };
+                auto conv = [&](const uint2(&v)[4], uint32_t aword, int h) {
+                    const float sc = __uint_as_float(aword);
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) {
+                        xm_s2 cv;
+                        if (XF) {
+                            asm("v_cvt_scalef32_pk_bf8_bf16 %0, %1, %2" : "=v"(cv) : "v"(v[c].x), "v"(sc));
+                            cv = __builtin_amdgcn_cvt_scalef32_pk_bf8_bf16(cv, __builtin_bit_cast(xm_b2, v[c].y), sc, true);
+                        } else {
+                            asm("v_cvt_scalef32_pk_fp8_bf16 %0, %1, %2" : "=v"(cv) : "v"(v[c].x), "v"(sc));
+                            cv = __builtin_amdgcn_cvt_scalef32_pk_fp8_bf16(cv, __builtin_bit_cast(xm_b2, v[c].y), sc, true);
+                        }
+                        av[4 * h + c] = __builtin_bit_cast(int, cv);
+                    }
+                };
+                auto aread = [&](int rb) {
+                    const uint64_t w = *(xm_lds_u64 *)&sm.aw[g][2 * (16 * (2 * wvu + rb) + r16)];
+                    return make_uint2((uint32_t)w, (uint32_t)(w >> 32));
+                };
+                // The pipeline of PIPE over the steps (row block, column group, K-step h); a row block's two
+                // addresses stay live across its four column groups.  The second block's A pair is read right
+                // after the first block's last table reads are issued, when that block's addresses are dead (read
+                // a whole block ahead, as in the mapping by columns, it is two registers too many: the plain
+                // instance spilled one VGPR and the emitting one three more across the loop)
+                uint2 va[4], vb[4];
+                uint2 awc = aread(0), awn = awc;
+                uint32_t a0 = addr(awc.x), a1 = addr(awc.y);
+                if (PIPE == 2) tread(a0, 0, 0, va);
+#pragma unroll
+                for (int rb = 0; rb < 2; ++rb) {
+                    uint32_t a0n = a0, a1n = a1;
+#pragma unroll
+                    for (int cg = 0; cg < 4; ++cg) {
+                        if (PIPE == 2) {
+                            tread(a1, cg, 1, vb);
+                            if (cg == 3 && rb + 1 < 2) awn = aread(rb + 1);
+                            __builtin_amdgcn_sched_barrier(0);
+                            conv(va, awc.x, 0);
+                            __builtin_amdgcn_sched_barrier(0);
+                            if (cg + 1 < 4) {
+                                tread(a0, cg + 1, 0, va);
+                            } else if (rb + 1 < 2) {
+                                a0n = addr(awn.x);
+                                a1n = addr(awn.y);
+                                tread(a0n, 0, 0, va);
+                            }
+                            __builtin_amdgcn_sched_barrier(0);
+                            conv(vb, awc.y, 1);
+                        } else {
+                            __builtin_amdgcn_sched_barrier(0);
+                            tread(a0, cg, 0, va);
+                            conv(va, awc.x, 0);
+                            tread(a1, cg, 1, va);
+                            if (cg == 3 && rb + 1 < 2) awn = aread(rb + 1);
+                            conv(va, awc.y, 1);
+                        }
+                        dq[4 * rb + cg] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(av, sel, dq[4 * rb + cg], XF ? 1 : 0, 0, 0, 127, 0, 127);
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
+                    awc = awn;
+                    if (PIPE == 1 && rb + 1 < 2) {
+                        a0n = addr(awc.x);
+                        a1n = addr(awc.y);
+                    }
+                    a0 = a0n;
+                    a1 = a1n;
+                }
+            } else if constexpr (PIPE != 0) {
                 // one K-step's table reads (one v_and_or_b32, four ds_read_b64) / its eight conversions
                 auto tread = [&](uint32_t aword, int h, uint2(&v)[4]) {
                     uint32_t a;
@@ -1080,11 +1173,13 @@ __global__ __launch_bounds__(256, (XmWaves<AF32, EMIT>::value)) void gemm_f8mx_k
         if (h > 0) __syncthreads();  // the previous slab is read (the K loop's last barrier covers h = 0)
 #pragma unroll
         for (int b = 0; b < RB; ++b) {
-            const int rb = 16 * (RB * wr + b) - SR * h;  // the block's first row in the slab (wave-uniform)
+            // (WROWS: accumulator b is row block 2 wv + b / 4, column group b % 4)
+            const int rb = 16 * (WROWS ? 2 * wvu + b / 4 : RB * wr + b) - SR * h;  // the block's first row in the slab (wave-uniform)
+            const int cg = WROWS ? b % 4 : wc;
             if (rb >= 0 && rb < SR) {
 #pragma unroll
                 for (int i = 0; i < 4; ++i)
-                    ct[(rb + 4 * (lane >> 4) + i) * CP + 16 * wc + (lane & 15)] = dq[b][i] * f8S;
+                    ct[(rb + 4 * (lane >> 4) + i) * CP + 16 * cg + (lane & 15)] = dq[b][i] * f8S;
             }
         }
         __syncthreads();

@@ -30,6 +30,14 @@ static void launch_shape(const GemmArgs &a, hipStream_t s) {
                     return;
                 }
             }
+            // option "xm_wave_rows": the 128 x 64 instances with the math loop's waves by rows (gemm_f8mx.h WROWS)
+            if constexpr (NCG == 4) {
+                if (a.xm_wave_rows) {
+                    if (emit) gemm_f8mx_kernel<NCG, RB, false, XF, true, false, XmPipe<NCG, true, false>::value, true><<<g, Cf::NT, 0, s>>>(a);
+                    else gemm_f8mx_kernel<NCG, RB, false, XF, false, false, XmPipe<NCG, false, false>::value, true><<<g, Cf::NT, 0, s>>>(a);
+                    return;
+                }
+            }
             if (emit) gemm_f8mx_kernel<NCG, RB, false, XF, true, false, XmPipe<NCG, true, false>::value><<<g, Cf::NT, 0, s>>>(a);
             else gemm_f8mx_kernel<NCG, RB, false, XF, false, false, XmPipe<NCG, false, false>::value><<<g, Cf::NT, 0, s>>>(a);
             return;

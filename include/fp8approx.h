@@ -145,6 +145,9 @@ int fp8a_kernel_time(double *out, int reset);
  * "xm_pipe" (default 1; FP8A_XM_PIPE) -- gemm_f8mx_kernel's word-staged E4M3 / E5M2 launches run the
  * instances whose K loop issues its LDS reads one stage ahead of the conversions that use them (0: the loop
  * without the pipelining).
+ * "xm_wave_rows" (default 1; FP8A_XM_WAVE_ROWS) -- with "xm_pipe", the 128 x 64 instances of gemm_f8mx_kernel
+ * map the math loop's waves by rows (a wave 32 rows x all 64 columns: one table address per row block and
+ * K-step instead of one per wave; 0: waves by columns).
  * All of these change the schedule only: the outputs are bit-identical.  Returns the previous value, or FP8A_EINVAL
  * for an unknown name.  Not synchronised with launches in flight on other threads.
  */

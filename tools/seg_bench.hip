@@ -15,6 +15,15 @@
 // (b, h); nothing is read across the tile's closing barrier.  PC: the build issues both units'
 // static-table reads before its first packed add.  PD: the MFMA's code operand in two buffers.
 //
+// PW (with PA, or PA | PB): waves by rows.  The tile stays 128 x 64 on 4 waves, but wave w
+// owns tile rows 32 w .. 32 w + 31 (two 16-row blocks) and all four 16-column groups: per row block one A pair
+// read and one v_and_or_b32 per K-step (no wave term), whose address serves the 16 table reads of the four
+// column groups (the group in the reads' immediates) -- 2 A reads and 4 address ops per staged tile and lane
+// instead of 8 and 16; the same 64 table reads, 128 conversions and 8 MFMAs.  PB here: the four table reads of
+// step (row block, column group, h) + 1 before the eight conversions of the current one.  PL (with PW): the
+// second row block's A pair is read after the first block's last table reads are issued (its two addresses
+// are dead by then) instead of a whole block ahead -- the form the kernel's register bound admits.
+//
 //   hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -o tools/bin/seg_bench tools/seg_bench.hip
 //   tools/bin/seg_bench [tiles]
 #include <hip/hip_runtime.h>
@@ -41,7 +50,7 @@ enum { P_LDS = 1, P_CVT = 2, P_MFMA = 4, P_BUILD = 8, P_BAR = 16, P_STAGE = 32, 
 // at compile time -- the bound.  P_POSRT: the same chosen by a wave-uniform word read once before
 // the loop (`negrows`, 0 here), i.e. the in-loop uniform branch a product kernel would carry.
 
-enum { PA = 1, PB = 2, PC = 4, PD = 8 };
+enum { PA = 1, PB = 2, PC = 4, PD = 8, PW = 16, PL = 32 };
 
 template <int P, int WAVES, int PIPE = 0>
 __global__ __launch_bounds__(256, WAVES) void seg(const uint32_t *seed, float *out, unsigned long long *cyc, int tiles,
@@ -143,7 +152,87 @@ __global__ __launch_bounds__(256, WAVES) void seg(const uint32_t *seed, float *o
             const int r16 = lane & 15, g = lane >> 4;
             const uint32_t base = wvo + (uint32_t)(2 * g) * (uint32_t)(TTK * 4);
             const char *tt0 = reinterpret_cast<const char *>(&sm.tt[0][0]);
-            if constexpr ((PIPE & (PA | PB | PD)) != 0) {
+            if constexpr ((PIPE & PW) != 0) {
+                static_assert((PIPE & PA) && (P & P_LDS) && (P & P_CVT) && (P & P_MFMA), "waves by rows: pipelined, the whole segment");
+                const uint32_t rbase = (uint32_t)(2 * g) * (uint32_t)(TTK * 4);  // no wave term
+                auto addr = [&](uint32_t aword) {
+                    uint32_t a;
+                    asm("v_and_or_b32 %0, %1, %2, %3" : "=v"(a) : "v"(aword), "s"(0x78u), "v"(rbase));
+                    return a;
+                };
+                // the four table reads of (column group cg, K-step h) at immediates (4 cg + c) * 128 + h * TTK * 4
+                auto tread = [&](uint32_t a, int cg, int h, uint2(&v)[4]) {
+                    __builtin_assume((a & 7u) == 0u);
+                    lds_u64 *ttk = (lds_u64 *)(tt0 + h * TTK * 4 + cg * 512);
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) {
+                        const uint64_t w = ttk[(a >> 3) + 16 * c];
+                        v[c] = make_uint2((uint32_t)w, (uint32_t)(w >> 32));
+                    }
+                };
+                auto conv = [&](const uint2(&v)[4], uint32_t aword, int h, v8i &o) {
+                    const float sc = __uint_as_float(aword);
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) {
+                        s2 cv;
+                        asm("v_cvt_scalef32_pk_fp8_bf16 %0, %1, %2" : "=v"(cv) : "v"(v[c].x), "v"(sc));
+                        cv = __builtin_amdgcn_cvt_scalef32_pk_fp8_bf16(cv, __builtin_bit_cast(b2, v[c].y), sc, true);
+                        o[4 * h + c] = __builtin_bit_cast(int, cv);
+                    }
+                };
+                auto aread = [&](int rb) {
+                    const uint64_t w = *(lds_u64 *)&sm.aw[g][2 * (16 * (2 * wv + rb) + r16)];
+                    return make_uint2((uint32_t)w, (uint32_t)(w >> 32));
+                };
+                uint2 va[4], vb[4];
+                uint2 awc = aread(0), awn = awc;
+                uint32_t a0 = addr(awc.x), a1 = addr(awc.y);
+                if (PIPE & PB) tread(a0, 0, 0, va);
+#pragma unroll
+                for (int rb = 0; rb < 2; ++rb) {
+                    if (!(PIPE & PL) && rb + 1 < 2) awn = aread(rb + 1);
+                    uint32_t a0n = a0, a1n = a1;
+#pragma unroll
+                    for (int cg = 0; cg < 4; ++cg) {
+                        if (PIPE & PB) {
+                            tread(a1, cg, 1, vb);
+                            if ((PIPE & PL) && cg == 3 && rb + 1 < 2) awn = aread(rb + 1);
+                            __builtin_amdgcn_sched_barrier(0);
+                            conv(va, awc.x, 0, av);
+                            __builtin_amdgcn_sched_barrier(0);
+                            if (cg + 1 < 4) {
+                                tread(a0, cg + 1, 0, va);
+                            } else if (rb + 1 < 2) {
+                                a0n = addr(awn.x);
+                                a1n = addr(awn.y);
+                                tread(a0n, 0, 0, va);
+                            }
+                            __builtin_amdgcn_sched_barrier(0);
+                            conv(vb, awc.y, 1, av);
+                        } else {
+                            __builtin_amdgcn_sched_barrier(0);
+                            tread(a0, cg, 0, va);
+                            conv(va, awc.x, 0, av);
+                            tread(a1, cg, 1, va);
+                            if ((PIPE & PL) && cg == 3 && rb + 1 < 2) awn = aread(rb + 1);
+                            conv(va, awc.y, 1, av);
+                            if (!(PIPE & PL) && cg == 3 && rb + 1 < 2) {
+                                a0n = addr(awn.x);
+                                a1n = addr(awn.y);
+                            }
+                        }
+                        dq[4 * rb + cg] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(av, sel, dq[4 * rb + cg], 0, 0, 0, 127, 0, 127);
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
+                    awc = awn;
+                    if ((PIPE & PL) && !(PIPE & PB) && rb + 1 < 2) {
+                        a0n = addr(awc.x);
+                        a1n = addr(awc.y);
+                    }
+                    a0 = a0n;
+                    a1 = a1n;
+                }
+            } else if constexpr ((PIPE & (PA | PB | PD)) != 0) {
                 static_assert(PIPE == 0 || ((P & P_LDS) && (P & P_CVT) && (P & P_MFMA)), "pipelined forms: the whole segment");
                 // the table reads of one K-step (one v_and_or_b32, four ds_read_b64) / its eight conversions
                 auto tread = [&](uint32_t aword, int h, uint2(&v)[4]) {
@@ -362,6 +451,10 @@ int main(int argc, char **argv) {
         run_form<PA | PC>("(a)+(c)", cus, seed, out, cyc, tiles, gbuf);
         run_form<PA | PB | PC>("(a)+(b)+(c)", cus, seed, out, cyc, tiles, gbuf);
         run_form<PA | PB | PC | PD>("(a)+(b)+(c)+(d) two code buffers", cus, seed, out, cyc, tiles, gbuf);
+        run_form<PW | PA>("waves by rows, (a)", cus, seed, out, cyc, tiles, gbuf);
+        run_form<PW | PA | PB>("waves by rows, (a)+(b)", cus, seed, out, cyc, tiles, gbuf);
+        run_form<PW | PL | PA>("waves by rows, (a) with the late A read", cus, seed, out, cyc, tiles, gbuf);
+        run_form<PW | PL | PA | PB>("waves by rows, (a)+(b) with the late A read", cus, seed, out, cyc, tiles, gbuf);
     }
     return 0;
 }
