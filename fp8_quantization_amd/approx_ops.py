@@ -512,14 +512,12 @@ def approx_conv2d_check(x, w, E, M, bA, bW, bR, table=None, flags=None, stride=(
     Cout, cig, kh, kw = w.shape
     if groups <= 0 or Cin % groups or Cout % groups or cig != Cin // groups:
         raise AssertionError(f"approx_conv2d_check: weight {tuple(w.shape)} does not fit {Cin} channels in {groups} groups")
-    (sh, sw), (ph, pw), (dh, dw) = [int(v) for v in stride], [int(v) for v in padding], [int(v) for v in dilation]
-    Ho = (H + 2 * ph - dh * (kh - 1) - 1) // sh + 1
-    Wo = (W + 2 * pw - dw * (kw - 1) - 1) // sw + 1
-    geo = (Bn, Cin, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, int(groups))
+    stride, padding, dilation = [int(v) for v in stride], [int(v) for v in padding], [int(v) for v in dilation]
+    geo = (*_conv_geometry(x, w, stride, padding, dilation), int(groups))
     nbytes = L.fp8a_conv2d_check_workspace_size(*geo)
     if nbytes == 0:
         raise AssertionError("approx_conv2d_check: empty or inconsistent convolution geometry")
-    y = torch.empty((Bn, Cout, Ho, Wo), dtype=torch.float32, device=dev)
+    y = torch.empty(_conv_out_shape(x, w, stride, padding, dilation), dtype=torch.float32, device=dev)
     G = torch.empty_like(y)
     prod = _check_prod(prod, y)
     stats = torch.empty(CHECK_STATS_BYTES, dtype=torch.uint8, device=dev)
@@ -591,6 +589,24 @@ def float_to_fpany_absint_torch(values, expo_width, mant_width, custom_bias, cli
 
 
 # ----------------------------------------------------------------------------------- conv
+def _conv_geometry(x, w, stride, padding, dilation):
+    """(Bn, Cin, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw): the C-ABI's geometry arguments."""
+    Bn, Cin, H, W = x.shape
+    Cout, _, kh, kw = w.shape
+    return (Bn, Cin, H, W, Cout, kh, kw, stride[0], stride[1], padding[0], padding[1], dilation[0], dilation[1])
+
+
+def _conv_out_shape(x, w, stride, padding, dilation):
+    Bn, _, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw = _conv_geometry(x, w, stride, padding, dilation)
+    return (Bn, Cout, (H + 2 * ph - dh * (kh - 1) - 1) // sh + 1, (W + 2 * pw - dw * (kw - 1) - 1) // sw + 1)
+
+
+def _conv_lead_args(x, w, y, geo, groups, E, M, bA, bW, bR, table, flags):
+    """The leading arguments of fp8a_conv2d and its bn_act / block / chain forms."""
+    return (_lib.dev_ptr(x), _lib.dev_ptr(w), _lib.dev_ptr(y), *geo, groups, E, M, _lib.dev_ptr(bA), _lib.dev_ptr(bW),
+            _lib.dev_ptr(bR), _lib.host_ptr(table), flags)
+
+
 @torch.library.custom_op("fp8approx::conv2d", mutates_args=())
 def _conv2d_op(x: torch.Tensor, w: torch.Tensor, bA: torch.Tensor, bW: torch.Tensor, bR: torch.Tensor,
                table: torch.Tensor, E: int, M: int, flags: int, stride: list[int], padding: list[int],
@@ -599,41 +615,77 @@ def _conv2d_op(x: torch.Tensor, w: torch.Tensor, bA: torch.Tensor, bW: torch.Ten
     L = _lib.load()
     x = x.contiguous()
     w = w.contiguous()
-    Bn, Cin, H, W = x.shape
-    Cout, _, kh, kw = w.shape
-    sh, sw = stride
-    ph, pw = padding
-    dh, dw = dilation
-    Ho = (H + 2 * ph - dh * (kh - 1) - 1) // sh + 1
-    Wo = (W + 2 * pw - dw * (kw - 1) - 1) // sw + 1
-    y = torch.empty((Bn, Cout, Ho, Wo), dtype=torch.float32, device=x.device)
-    nbytes = L.fp8a_conv2d_workspace_size(Bn, Cin, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, groups)
-    ws = _workspace(x.device, nbytes)
+    geo = _conv_geometry(x, w, stride, padding, dilation)
+    y = torch.empty(_conv_out_shape(x, w, stride, padding, dilation), dtype=torch.float32, device=x.device)
+    ws = _workspace(x.device, L.fp8a_conv2d_workspace_size(*geo, groups))
+    lead = _conv_lead_args(x, w, y, geo, groups, E, M, bA, bW, bR, table, flags)
+    tail = (_lib.dev_ptr(ws), ws.numel(), _lib.stream_ptr(x.device))
     if bn is None:
-        rc = L.fp8a_conv2d(_lib.dev_ptr(x), _lib.dev_ptr(w), _lib.dev_ptr(y), Bn, Cin, H, W, Cout, kh, kw, sh, sw,
-                           ph, pw, dh, dw, groups, E, M, _lib.dev_ptr(bA), _lib.dev_ptr(bW), _lib.dev_ptr(bR),
-                           _lib.host_ptr(table), flags, _lib.dev_ptr(ws), ws.numel(), _lib.stream_ptr(x.device))
-        _lib.check(rc, "fp8a_conv2d")
+        _lib.check(L.fp8a_conv2d(*lead, *tail), "fp8a_conv2d")
         return y
+    Cout = w.shape[0]
     if bn.shape != (Cout, 2) or bn.dtype != torch.float32 or not bn.is_contiguous() or bn.device != x.device:
         raise AssertionError(f"approx_conv2d: epilogue parameters must be contiguous float32 [{Cout}, 2] "
                              f"on {x.device}, got {tuple(bn.shape)} {bn.dtype} on {bn.device}")
-    rc = L.fp8a_conv2d_bn_act(_lib.dev_ptr(x), _lib.dev_ptr(w), _lib.dev_ptr(y), Bn, Cin, H, W, Cout, kh, kw, sh, sw,
-                              ph, pw, dh, dw, groups, E, M, _lib.dev_ptr(bA), _lib.dev_ptr(bW), _lib.dev_ptr(bR),
-                              _lib.host_ptr(table), flags, _lib.dev_ptr(bn), int(act), float(act_lo), float(act_hi),
-                              _lib.dev_ptr(ws), ws.numel(), _lib.stream_ptr(x.device))
+    rc = L.fp8a_conv2d_bn_act(*lead, _lib.dev_ptr(bn), int(act), float(act_lo), float(act_hi), *tail)
     _lib.check(rc, "fp8a_conv2d_bn_act")
     return y
 
 
-@_conv2d_op.register_fake
-def _(x, w, bA, bW, bR, table, E, M, flags, stride, padding, dilation, groups, bn=None, act=0, act_lo=0.0,
-      act_hi=0.0):
-    Bn, _, H, W = x.shape
-    Cout, _, kh, kw = w.shape
-    Ho = (H + 2 * padding[0] - dilation[0] * (kh - 1) - 1) // stride[0] + 1
-    Wo = (W + 2 * padding[1] - dilation[1] * (kw - 1) - 1) // stride[1] + 1
-    return x.new_empty((Bn, Cout, Ho, Wo))
+def _conv2d_fake(x, w, bA, bW, bR, table, E, M, flags, stride, padding, dilation, *rest, **kw):
+    return x.new_empty(_conv_out_shape(x, w, stride, padding, dilation))
+
+
+_conv2d_op.register_fake(_conv2d_fake)
+
+
+def _block_call(entry, x, w, bA, bW, bR, table, E, M, flags, stride, padding, dilation, groups, in_q, res, post,
+                out_q, bn, act, chain=None):
+    """fp8a_conv2d_block, or fp8a_conv2d_chain with chain = (in_image, out_image, next_ph, next_pw, next_maxval,
+    next_nbits, next_mbits, next_sign_bits, next_bR, next_Mw, next_form).  in_q / out_q: (maxval, n_bits,
+    mantissa bits, sign bits); post: (clamp, lo, hi); act: (act, lo, hi)."""
+    L = _lib.load()
+    x = x.contiguous()
+    w = w.contiguous()
+    dev = x.device
+    geo = _conv_geometry(x, w, stride, padding, dilation)
+    Bn, Cin, H, W, Cout = geo[:5]
+    y = torch.empty(_conv_out_shape(x, w, stride, padding, dilation), dtype=torch.float32, device=dev)
+    # the input / output quantizers' float and int32 biases
+    ib, iib, ob, oib = (torch.empty(1, dtype=t, device=dev) for t in (torch.float32, torch.int32) * 2)
+    if res is not None:
+        res = res.contiguous()
+        if res.shape != y.shape or res.dtype != torch.float32 or res.device != dev:
+            raise AssertionError(f"approx_conv2d: residual must be float32 {tuple(y.shape)} on {dev}")
+    if bn is not None and (bn.shape != (Cout, 2) or bn.dtype != torch.float32 or not bn.is_contiguous()):
+        raise AssertionError(f"approx_conv2d: epilogue parameters must be contiguous float32 [{Cout}, 2]")
+    extra = ()
+    if chain is not None:
+        in_image, out_image, next_ph, next_pw, next_maxval, *next_q, next_bR, next_Mw, next_form = chain
+        # (a single-output-channel-group consumer reads table-form words: an image without border)
+        in_pad = tuple(padding) if groups == 1 else (0, 0)
+        # (form 1, the table form, has no border; forms 0 and 2 -- matrix-core and v5 words -- carry the
+        # consumer's padding, as fp8a_conv2d_chain sizes them)
+        out_pad = (0, 0) if next_form == 1 else (next_ph, next_pw)
+        for img, shp in ((in_image, (Bn, Cin, H, W) + in_pad), (out_image, tuple(y.shape) + out_pad)):
+            if img is not None and img.numel() < L.fp8a_word_image_bytes(*shp):
+                raise AssertionError("approx_conv2d: word image smaller than fp8a_word_image_bytes")
+        extra = (_lib.dev_ptr(in_image), _lib.dev_ptr(out_image), int(next_ph), int(next_pw), _lib.dev_ptr(next_maxval),
+                 *map(int, next_q), _lib.dev_ptr(next_bR), int(next_Mw), int(next_form))
+    ws = _workspace(dev, L.fp8a_conv2d_block_workspace_size(*geo, groups))
+    rc = getattr(L, entry)(*_conv_lead_args(x, w, y, geo, groups, E, M, bA, bW, bR, table, flags), _lib.dev_ptr(bn),
+                           int(act[0]), float(act[1]), float(act[2]), _lib.dev_ptr(in_q[0]), *map(int, in_q[1:]),
+                           _lib.dev_ptr(ib), _lib.dev_ptr(iib), _lib.dev_ptr(res), int(post[0]), float(post[1]),
+                           float(post[2]), _lib.dev_ptr(out_q[0]), *map(int, out_q[1:]), _lib.dev_ptr(ob),
+                           _lib.dev_ptr(oib), *extra, _lib.dev_ptr(ws), ws.numel(), _lib.stream_ptr(dev))
+    _lib.check(rc, entry)
+    return y, ib, iib, ob, oib
+
+
+def _block_fake(x, w, *args, **kw):
+    one = x.new_empty((1,))
+    onei = x.new_empty((1,), dtype=torch.int32)
+    return _conv2d_fake(x, w, *args, **kw), one, onei, one.clone(), onei.clone()
 
 
 @torch.library.custom_op("fp8approx::conv2d_block", mutates_args=())
@@ -647,50 +699,12 @@ def _conv2d_block_op(x: torch.Tensor, w: torch.Tensor, bA: Optional[torch.Tensor
                      ) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
     """fp8a_conv2d_block: y = fq_out(clamp(bn_act(conv(fq_in(x))) + res)); returns y and the input /
     output quantizers' float and int32 biases (1-element tensors, unset when unused)."""
-    L = _lib.load()
-    x = x.contiguous()
-    w = w.contiguous()
-    Bn, Cin, H, W = x.shape
-    Cout, _, kh, kw = w.shape
-    sh, sw = stride
-    ph, pw = padding
-    dh, dw = dilation
-    Ho = (H + 2 * ph - dh * (kh - 1) - 1) // sh + 1
-    Wo = (W + 2 * pw - dw * (kw - 1) - 1) // sw + 1
-    y = torch.empty((Bn, Cout, Ho, Wo), dtype=torch.float32, device=x.device)
-    ib, iib = torch.empty(1, device=x.device), torch.empty(1, dtype=torch.int32, device=x.device)
-    ob, oib = torch.empty(1, device=x.device), torch.empty(1, dtype=torch.int32, device=x.device)
-    if res is not None:
-        res = res.contiguous()
-        if res.shape != y.shape or res.dtype != torch.float32 or res.device != x.device:
-            raise AssertionError(f"approx_conv2d: residual must be float32 {tuple(y.shape)} on {x.device}")
-    if bn is not None and (bn.shape != (Cout, 2) or bn.dtype != torch.float32 or not bn.is_contiguous()):
-        raise AssertionError(f"approx_conv2d: epilogue parameters must be contiguous float32 [{Cout}, 2]")
-    ws = _workspace(x.device, L.fp8a_conv2d_block_workspace_size(Bn, Cin, H, W, Cout, kh, kw, sh, sw, ph, pw, dh,
-                                                                 dw, groups))
-    opt = lambda t: _lib.dev_ptr(t) if t is not None else None  # noqa: E731
-    rc = L.fp8a_conv2d_block(_lib.dev_ptr(x), _lib.dev_ptr(w), _lib.dev_ptr(y), Bn, Cin, H, W, Cout, kh, kw, sh, sw,
-                             ph, pw, dh, dw, groups, E, M, opt(bA), _lib.dev_ptr(bW), _lib.dev_ptr(bR),
-                             _lib.host_ptr(table), flags, opt(bn), int(act), float(act_lo), float(act_hi),
-                             opt(in_maxval), int(in_nbits), int(in_mbits), int(in_sign_bits), _lib.dev_ptr(ib),
-                             _lib.dev_ptr(iib), opt(res), int(post_act), float(post_lo), float(post_hi),
-                             opt(out_maxval), int(out_nbits), int(out_mbits), int(out_sign_bits), _lib.dev_ptr(ob),
-                             _lib.dev_ptr(oib), _lib.dev_ptr(ws), ws.numel(), _lib.stream_ptr(x.device))
-    _lib.check(rc, "fp8a_conv2d_block")
-    return y, ib, iib, ob, oib
+    return _block_call("fp8a_conv2d_block", x, w, bA, bW, bR, table, E, M, flags, stride, padding, dilation, groups,
+                       (in_maxval, in_nbits, in_mbits, in_sign_bits), res, (post_act, post_lo, post_hi),
+                       (out_maxval, out_nbits, out_mbits, out_sign_bits), bn, (act, act_lo, act_hi))
 
 
-@_conv2d_block_op.register_fake
-def _(x, w, bA, bW, bR, table, E, M, flags, stride, padding, dilation, groups, in_maxval, in_nbits, in_mbits,
-      in_sign_bits, res, post_act, post_lo, post_hi, out_maxval, out_nbits, out_mbits, out_sign_bits, bn=None, act=0,
-      act_lo=0.0, act_hi=0.0):
-    Bn, _, H, W = x.shape
-    Cout, _, kh, kw = w.shape
-    Ho = (H + 2 * padding[0] - dilation[0] * (kh - 1) - 1) // stride[0] + 1
-    Wo = (W + 2 * padding[1] - dilation[1] * (kw - 1) - 1) // stride[1] + 1
-    one = x.new_empty((1,))
-    onei = x.new_empty((1,), dtype=torch.int32)
-    return x.new_empty((Bn, Cout, Ho, Wo)), one, onei, one.clone(), onei.clone()
+_conv2d_block_op.register_fake(_block_fake)
 
 
 # in_image is mutated too: an image that arrived invalid is re-decoded in place by the consumer's
@@ -709,61 +723,14 @@ def _conv2d_chain_op(x: torch.Tensor, w: torch.Tensor, bA: Optional[torch.Tensor
                      ) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
     """fp8a_conv2d_chain: fp8a_conv2d_block that reads its input's word image (in_image) and / or
     emits the next convolution's (out_image); same results and return values as conv2d_block."""
-    L = _lib.load()
-    x = x.contiguous()
-    w = w.contiguous()
-    Bn, Cin, H, W = x.shape
-    Cout, _, kh, kw = w.shape
-    sh, sw = stride
-    ph, pw = padding
-    dh, dw = dilation
-    Ho = (H + 2 * ph - dh * (kh - 1) - 1) // sh + 1
-    Wo = (W + 2 * pw - dw * (kw - 1) - 1) // sw + 1
-    y = torch.empty((Bn, Cout, Ho, Wo), dtype=torch.float32, device=x.device)
-    ib, iib = torch.empty(1, device=x.device), torch.empty(1, dtype=torch.int32, device=x.device)
-    ob, oib = torch.empty(1, device=x.device), torch.empty(1, dtype=torch.int32, device=x.device)
-    if res is not None:
-        res = res.contiguous()
-        if res.shape != y.shape or res.dtype != torch.float32 or res.device != x.device:
-            raise AssertionError(f"approx_conv2d: residual must be float32 {tuple(y.shape)} on {x.device}")
-    if bn is not None and (bn.shape != (Cout, 2) or bn.dtype != torch.float32 or not bn.is_contiguous()):
-        raise AssertionError(f"approx_conv2d: epilogue parameters must be contiguous float32 [{Cout}, 2]")
-    # (a single-output-channel-group consumer reads table-form words: an image without border)
-    in_pad = (ph, pw) if groups == 1 else (0, 0)
-    # (form 1, the table form, has no border; forms 0 and 2 -- matrix-core and v5 words -- carry the
-    # consumer's padding, as fp8a_conv2d_chain sizes them)
-    out_pad = (0, 0) if next_form == 1 else (next_ph, next_pw)
-    for img, shp in ((in_image, (Bn, Cin, H, W) + in_pad), (out_image, (Bn, Cout, Ho, Wo) + out_pad)):
-        if img is not None and img.numel() < L.fp8a_word_image_bytes(*shp):
-            raise AssertionError("approx_conv2d: word image smaller than fp8a_word_image_bytes")
-    ws = _workspace(x.device, L.fp8a_conv2d_block_workspace_size(Bn, Cin, H, W, Cout, kh, kw, sh, sw, ph, pw, dh,
-                                                                 dw, groups))
-    opt = lambda t: _lib.dev_ptr(t) if t is not None else None  # noqa: E731
-    rc = L.fp8a_conv2d_chain(_lib.dev_ptr(x), _lib.dev_ptr(w), _lib.dev_ptr(y), Bn, Cin, H, W, Cout, kh, kw, sh, sw,
-                             ph, pw, dh, dw, groups, E, M, opt(bA), _lib.dev_ptr(bW), _lib.dev_ptr(bR),
-                             _lib.host_ptr(table), flags, opt(bn), int(act), float(act_lo), float(act_hi),
-                             opt(in_maxval), int(in_nbits), int(in_mbits), int(in_sign_bits), _lib.dev_ptr(ib),
-                             _lib.dev_ptr(iib), opt(res), int(post_act), float(post_lo), float(post_hi),
-                             opt(out_maxval), int(out_nbits), int(out_mbits), int(out_sign_bits), _lib.dev_ptr(ob),
-                             _lib.dev_ptr(oib), opt(in_image), opt(out_image), int(next_ph), int(next_pw),
-                             opt(next_maxval), int(next_nbits), int(next_mbits), int(next_sign_bits), opt(next_bR),
-                             int(next_Mw), int(next_form), _lib.dev_ptr(ws), ws.numel(), _lib.stream_ptr(x.device))
-    _lib.check(rc, "fp8a_conv2d_chain")
-    return y, ib, iib, ob, oib
+    return _block_call("fp8a_conv2d_chain", x, w, bA, bW, bR, table, E, M, flags, stride, padding, dilation, groups,
+                       (in_maxval, in_nbits, in_mbits, in_sign_bits), res, (post_act, post_lo, post_hi),
+                       (out_maxval, out_nbits, out_mbits, out_sign_bits), bn, (act, act_lo, act_hi),
+                       (in_image, out_image, next_ph, next_pw, next_maxval, next_nbits, next_mbits, next_sign_bits,
+                        next_bR, next_Mw, next_form))
 
 
-@_conv2d_chain_op.register_fake
-def _(x, w, bA, bW, bR, table, E, M, flags, stride, padding, dilation, groups, in_maxval, in_nbits, in_mbits,
-      in_sign_bits, res, post_act, post_lo, post_hi, out_maxval, out_nbits, out_mbits, out_sign_bits, in_image,
-      out_image, next_ph, next_pw, next_maxval, next_nbits, next_mbits, next_sign_bits, next_bR, next_Mw, bn=None,
-      act=0, act_lo=0.0, act_hi=0.0, next_form=0):
-    Bn, _, H, W = x.shape
-    Cout, _, kh, kw = w.shape
-    Ho = (H + 2 * padding[0] - dilation[0] * (kh - 1) - 1) // stride[0] + 1
-    Wo = (W + 2 * padding[1] - dilation[1] * (kw - 1) - 1) // stride[1] + 1
-    one = x.new_empty((1,))
-    onei = x.new_empty((1,), dtype=torch.int32)
-    return x.new_empty((Bn, Cout, Ho, Wo)), one, onei, one.clone(), onei.clone()
+_conv2d_chain_op.register_fake(_block_fake)
 
 
 def word_image_bytes(Bn, C, H, W, ph, pw):
@@ -843,50 +810,41 @@ def approx_conv2d(x, w, E, M, bA, bW, bR, table=None, flags=None, stride=(1, 1),
     if bW_.numel() != w.shape[0]:
         raise AssertionError(f"approx_conv2d: {bW_.numel()} weight biases for {w.shape[0]} output channels")
     ev = _prof_start()
-    if chain is not None:
-        iq = _quantizer_args(qin) if qin is not None else (None, 0, 0, 0)
-        res, pact, plo, phi, oq = post if post is not None else (None, 0, 0.0, 0.0, None)
-        oq = _quantizer_args(oq) if oq is not None else (None, 0, 0, 0)
+    macs = w.shape[0] * w.shape[1] * w.shape[2] * w.shape[3]  # per output pixel
+    lead = (_as_f32(x), _as_f32(w), None if qin is not None else _bias_dev(bA, dev), bW_, _bias_dev(bR, dev), tab,
+            int(E), int(M), int(flags), [int(s) for s in stride], [int(p) for p in padding],
+            [int(d) for d in dilation], int(groups))
+    if qin is None and post is None and chain is None:
+        y = _conv2d_op(*lead, *(epilogue or ()))
+        _prof_end(ev, y.shape[0] * y.shape[2] * y.shape[3] * macs)
+        return y
+
+    def quantizer(q):  # (maxval on the device, n_bits, mantissa bits, sign bits), or none
+        if q is None:
+            return (None, 0, 0, 0)
+        mx, *bits = _quantizer_args(q)
+        return (mx.to(dev), *bits)
+
+    res, pact, plo, phi, oq = post if post is not None else (None, 0, 0.0, 0.0, None)
+    block = (*lead, *quantizer(qin), res, int(pact), float(plo), float(phi), *quantizer(oq))
+    if chain is None:
+        y, ib, iib, ob, oib = _conv2d_block_op(*block, *(epilogue or ()))
+    else:
         in_img, out = chain
         if in_img is not None and qin is None:
             raise AssertionError("approx_conv2d: an input word image needs the fused input quantizer")
         if out is not None:
             oimg, (nph, npw), nq, nbR, nM = out[:5]
             nform = out[5] if len(out) > 5 else 0
-            nq = _quantizer_args(nq)
             nbR = _bias_dev(nbR, dev)
         else:
-            oimg, nph, npw, nq, nbR, nM, nform = None, 0, 0, (None, 0, 0, 0), None, 0, 0
-        y, ib, iib, ob, oib = _conv2d_chain_op(
-            _as_f32(x), _as_f32(w), None if qin is not None else _bias_dev(bA, dev), bW_, _bias_dev(bR, dev), tab,
-            int(E), int(M), int(flags), [int(s) for s in stride], [int(p) for p in padding],
-            [int(d) for d in dilation], int(groups), iq[0].to(dev) if iq[0] is not None else None, iq[1], iq[2],
-            iq[3], res, int(pact), float(plo), float(phi), oq[0].to(dev) if oq[0] is not None else None, oq[1],
-            oq[2], oq[3], in_img, oimg, int(nph), int(npw), nq[0].to(dev) if nq[0] is not None else None, nq[1],
-            nq[2], nq[3], nbR, int(nM), *(epilogue or ()), next_form=int(nform))
-        ib._fp8a_i32 = iib
-        ob._fp8a_i32 = oib
-        _prof_end(ev, y.shape[0] * y.shape[2] * y.shape[3] * w.shape[0] * w.shape[1] * w.shape[2] * w.shape[3])
-        return y, (ib if qin is not None else None), (ob if oq[0] is not None else None)
-    if qin is not None or post is not None:
-        iq = _quantizer_args(qin) if qin is not None else (None, 0, 0, 0)
-        res, pact, plo, phi, oq = post if post is not None else (None, 0, 0.0, 0.0, None)
-        oq = _quantizer_args(oq) if oq is not None else (None, 0, 0, 0)
-        y, ib, iib, ob, oib = _conv2d_block_op(
-            _as_f32(x), _as_f32(w), None if qin is not None else _bias_dev(bA, dev), bW_, _bias_dev(bR, dev), tab,
-            int(E), int(M), int(flags), [int(s) for s in stride], [int(p) for p in padding],
-            [int(d) for d in dilation], int(groups), iq[0].to(dev) if iq[0] is not None else None, iq[1], iq[2],
-            iq[3], res, int(pact), float(plo), float(phi), oq[0].to(dev) if oq[0] is not None else None, oq[1],
-            oq[2], oq[3], *(epilogue or ()))
-        ib._fp8a_i32 = iib
-        ob._fp8a_i32 = oib
-        _prof_end(ev, y.shape[0] * y.shape[2] * y.shape[3] * w.shape[0] * w.shape[1] * w.shape[2] * w.shape[3])
-        return y, (ib if qin is not None else None), (ob if oq[0] is not None else None)
-    y = _conv2d_op(_as_f32(x), _as_f32(w), _bias_dev(bA, dev), bW_, _bias_dev(bR, dev), tab,
-                   int(E), int(M), int(flags), [int(s) for s in stride], [int(p) for p in padding],
-                   [int(d) for d in dilation], int(groups), *(epilogue or ()))
-    _prof_end(ev, y.shape[0] * y.shape[2] * y.shape[3] * w.shape[0] * w.shape[1] * w.shape[2] * w.shape[3])
-    return y
+            oimg, nph, npw, nq, nbR, nM, nform = None, 0, 0, None, None, 0, 0
+        y, ib, iib, ob, oib = _conv2d_chain_op(*block, in_img, oimg, int(nph), int(npw), *quantizer(nq), nbR, int(nM),
+                                               *(epilogue or ()), next_form=int(nform))
+    ib._fp8a_i32 = iib
+    ob._fp8a_i32 = oib
+    _prof_end(ev, y.shape[0] * y.shape[2] * y.shape[3] * macs)
+    return y, (ib if qin is not None else None), (ob if oq is not None else None)
 
 
 def bn_act_epilogue(running_mean, running_var, gamma, beta, eps, activation=None):
@@ -1089,16 +1047,11 @@ def qamaa_conv2d(x, w, maxval, n_bits, mantissa_bits, sign_bits=1, stride=(1, 1)
     L = _lib.load()
     x = _as_f32(x).contiguous()
     w = _as_f32(w).contiguous()
-    Bn, Cin, H, W = x.shape
-    Cout, _, kh, kw = w.shape
-    Ho = (H + 2 * padding[0] - dilation[0] * (kh - 1) - 1) // stride[0] + 1
-    Wo = (W + 2 * padding[1] - dilation[1] * (kw - 1) - 1) // stride[1] + 1
     mx = _as_f32(maxval).reshape(-1).to(x.device).contiguous()
-    y = torch.empty((Bn, Cout, Ho, Wo), dtype=torch.float32, device=x.device)
-    rc = L.fp8a_conv2d_qamaa(_lib.dev_ptr(x), _lib.dev_ptr(w), _lib.dev_ptr(y), Bn, Cin, H, W, Cout, kh, kw,
-                             stride[0], stride[1], padding[0], padding[1], dilation[0], dilation[1], groups,
-                             _lib.dev_ptr(mx), int(n_bits), int(mantissa_bits), int(sign_bits),
-                             _lib.stream_ptr(x.device))
+    y = torch.empty(_conv_out_shape(x, w, stride, padding, dilation), dtype=torch.float32, device=x.device)
+    rc = L.fp8a_conv2d_qamaa(_lib.dev_ptr(x), _lib.dev_ptr(w), _lib.dev_ptr(y),
+                             *_conv_geometry(x, w, stride, padding, dilation), groups, _lib.dev_ptr(mx),
+                             int(n_bits), int(mantissa_bits), int(sign_bits), _lib.stream_ptr(x.device))
     _lib.check(rc, "fp8a_conv2d_qamaa")
     return y
 
@@ -1156,12 +1109,8 @@ def dense_matmul(A, B, fmt):
 def _dense_conv2d_op(x: torch.Tensor, w: torch.Tensor, fmt: int, stride: list[int], padding: list[int],
                      dilation: list[int]) -> torch.Tensor:
     L = _lib.load()
-    Bn, Cin, H, W = x.shape
-    Cout, _, kh, kw = w.shape
-    Ho = (H + 2 * padding[0] - dilation[0] * (kh - 1) - 1) // stride[0] + 1
-    Wo = (W + 2 * padding[1] - dilation[1] * (kw - 1) - 1) // stride[1] + 1
-    y = torch.empty((Bn, Cout, Ho, Wo), dtype=torch.float32, device=x.device)
-    geo = (Bn, Cin, H, W, Cout, kh, kw, stride[0], stride[1], padding[0], padding[1], dilation[0], dilation[1])
+    y = torch.empty(_conv_out_shape(x, w, stride, padding, dilation), dtype=torch.float32, device=x.device)
+    geo = _conv_geometry(x, w, stride, padding, dilation)
     ws = _workspace(x.device, L.fp8a_dense_conv2d_workspace_size(*geo))
     rc = L.fp8a_dense_conv2d(_lib.dev_ptr(x), _lib.dev_ptr(w), _lib.dev_ptr(y), *geo, int(fmt), _lib.dev_ptr(ws),
                              ws.numel(), _lib.stream_ptr(x.device))
@@ -1171,11 +1120,7 @@ def _dense_conv2d_op(x: torch.Tensor, w: torch.Tensor, fmt: int, stride: list[in
 
 @_dense_conv2d_op.register_fake
 def _(x, w, fmt, stride, padding, dilation):
-    Bn, _, H, W = x.shape
-    Cout, _, kh, kw = w.shape
-    Ho = (H + 2 * padding[0] - dilation[0] * (kh - 1) - 1) // stride[0] + 1
-    Wo = (W + 2 * padding[1] - dilation[1] * (kw - 1) - 1) // stride[1] + 1
-    return x.new_empty((Bn, Cout, Ho, Wo), dtype=torch.float32)
+    return x.new_empty(_conv_out_shape(x, w, stride, padding, dilation), dtype=torch.float32)
 
 
 def dense_conv2d(x, w, fmt, stride=(1, 1), padding=(0, 0), dilation=(1, 1)):
@@ -1198,13 +1143,9 @@ def dense_conv2d(x, w, fmt, stride=(1, 1), padding=(0, 0), dilation=(1, 1)):
 def _grouped_conv2d_op(x: torch.Tensor, w: torch.Tensor, groups: int, stride: list[int], padding: list[int],
                        dilation: list[int]) -> torch.Tensor:
     L = _lib.load()
-    Bn, Cin, H, W = x.shape
-    Cout, _, kh, kw = w.shape
-    Ho = (H + 2 * padding[0] - dilation[0] * (kh - 1) - 1) // stride[0] + 1
-    Wo = (W + 2 * padding[1] - dilation[1] * (kw - 1) - 1) // stride[1] + 1
-    y = torch.empty((Bn, Cout, Ho, Wo), dtype=torch.float32, device=x.device)
-    rc = L.fp8a_grouped_conv2d(_lib.dev_ptr(x), _lib.dev_ptr(w), _lib.dev_ptr(y), Bn, Cin, H, W, Cout, int(groups),
-                               kh, kw, stride[0], stride[1], padding[0], padding[1], dilation[0], dilation[1],
+    geo = _conv_geometry(x, w, stride, padding, dilation)
+    y = torch.empty(_conv_out_shape(x, w, stride, padding, dilation), dtype=torch.float32, device=x.device)
+    rc = L.fp8a_grouped_conv2d(_lib.dev_ptr(x), _lib.dev_ptr(w), _lib.dev_ptr(y), *geo[:5], int(groups), *geo[5:],
                                _lib.stream_ptr(x.device))
     _lib.check(rc, "fp8a_grouped_conv2d")
     return y
@@ -1212,11 +1153,7 @@ def _grouped_conv2d_op(x: torch.Tensor, w: torch.Tensor, groups: int, stride: li
 
 @_grouped_conv2d_op.register_fake
 def _(x, w, groups, stride, padding, dilation):
-    Bn, _, H, W = x.shape
-    Cout, _, kh, kw = w.shape
-    Ho = (H + 2 * padding[0] - dilation[0] * (kh - 1) - 1) // stride[0] + 1
-    Wo = (W + 2 * padding[1] - dilation[1] * (kw - 1) - 1) // stride[1] + 1
-    return x.new_empty((Bn, Cout, Ho, Wo), dtype=torch.float32)
+    return x.new_empty(_conv_out_shape(x, w, stride, padding, dilation), dtype=torch.float32)
 
 
 def grouped_conv2d(x, w, groups, stride=(1, 1), padding=(0, 0), dilation=(1, 1)):
@@ -1247,11 +1184,9 @@ def dense_conv2d_fused(x, w, groups=1, stride=(1, 1), padding=(0, 0), dilation=(
     L = _lib.load()
     x = _as_f32(x).contiguous()
     w = _as_f32(w).contiguous()
-    Bn, Cin, H, W = x.shape
-    Cout, _, kh, kw = w.shape
-    Ho = (H + 2 * padding[0] - dilation[0] * (kh - 1) - 1) // stride[0] + 1
-    Wo = (W + 2 * padding[1] - dilation[1] * (kw - 1) - 1) // stride[1] + 1
-    y = torch.empty((Bn, Cout, Ho, Wo), dtype=torch.float32, device=x.device)
+    geo = _conv_geometry(x, w, stride, padding, dilation)
+    Cout, kh, kw = geo[4:7]
+    y = torch.empty(_conv_out_shape(x, w, stride, padding, dilation), dtype=torch.float32, device=x.device)
     keep, biases, qargs = [], {}, []
     for name, q in (("wq", wq), ("qin", qin), ("rq", rq), ("oq", oq)):
         if q is None:
@@ -1275,7 +1210,6 @@ def dense_conv2d_fused(x, w, groups=1, stride=(1, 1), padding=(0, 0), dilation=(
     ep, act, lo, hi = (None, 0, 0.0, 0.0) if bn is None else bn
     if ep is not None:
         ep = _as_f32(ep).to(x.device).contiguous()
-    geo = (Bn, Cin, H, W, Cout, kh, kw, stride[0], stride[1], padding[0], padding[1], dilation[0], dilation[1])
     ws = _workspace(x.device, L.fp8a_dense_conv2d_workspace_size(*geo) if groups == 1 else 16)
     fmt = dense_format(3) if fmt is None else fmt
     ev = _prof_start()

@@ -591,29 +591,67 @@ static void launch_f8mx(const GemmArgs &a, hipStream_t s) {
     }
 }
 
+// ------------------------------------------------------------------------- options
+// One table for fp8a_set_option and the FP8A_<NAME> environment variables read at load (documented in
+// include/fp8approx.h).  kind: how fp8a_set_option normalises a value -- as given, != 0, max(lo, v) or
+// min(hi, max(lo, v)); the environment's value takes the same normalisation unless env_raw.
+enum OptKind { OPT_RAW, OPT_BOOL, OPT_AT_LEAST, OPT_CLAMP };
+enum OptId { OPT_XM_NCG, OPT_XM_SIGN_ROWS, OPT_XM_PIPE, OPT_XM_WAVE_ROWS, OPT_SPLITK_FIXUP, OPT_SPLITK, OPT_FQ_FAST,
+             OPT_AF32_MAXCT, OPT_TT_BAND, OPT_TT16_MINK, OPT_TBX_RW, OPT_TBS, OPT_DW_LDS, OPT_DW_TARGET, OPT_DN_DIRECT,
+             OPT_V5DS, OPT_DW3, OPT_MSE_GROUP, OPT_N };
+struct Option {
+    const char *name, *env;
+    int def, kind, lo, hi;
+    bool env_raw;
+    int value;
+};
+static Option g_opts[OPT_N] = {
+    {"xm_ncg", "FP8A_XM_NCG", 0, OPT_RAW},  // gemm_f8mx_kernel's tile width (1 | 2 | 4; 0: xm_ncg's choice)
+    {"xm_sign_rows", "FP8A_XM_SIGN_ROWS", 1, OPT_BOOL, 0, 0, true},  // tile table: only the sign rows A addresses
+    {"xm_pipe", "FP8A_XM_PIPE", 1, OPT_BOOL},            // K loop's LDS reads one stage ahead
+    {"xm_wave_rows", "FP8A_XM_WAVE_ROWS", 1, OPT_BOOL},  // 128 x 64 instances: waves by rows
+    {"splitk_fixup", "FP8A_SPLITK_FIXUP", 0, OPT_BOOL},  // split-K partials summed inside the launch (3v: slower)
+    {"splitk", "FP8A_SPLITK", 0, OPT_AT_LEAST, 0},       // the forced split count (0: choose_splits)
+    {"fq_fast", "FP8A_FQ_FAST", 1, OPT_BOOL},  // the matrix-core path's fake quantizers run fq_apply_fast / fq_word
+    {"af32_maxct", "FP8A_AF32_MAXCT", 1, OPT_AT_LEAST, 0},  // column tiles up to which A is staged from fp32 (xm_af32)
+    {"tt_band", "FP8A_TT_BAND", 1, OPT_RAW},                // gemm_tt_kernel's band / zero wave-tile forms
+    {"tt16_mink", "FP8A_TT16_MINK", 64, OPT_AT_LEAST, 0},   // smallest K of an unsigned-table launch on gemm_tt16
+    {"tbx_rw", "FP8A_TBX_RW", 2, OPT_RAW},  // output rows per thread of conv_tbx_kernel (2 needs undilated rows)
+    {"tbs", "FP8A_TBS", 2, OPT_RAW},        // table-form depthwise 3x3: conv_tbsg (2), conv_tbs (1), conv_tbx (0)
+    {"dw_lds", "FP8A_DW_LDS", 40960, OPT_CLAMP, 4096, 65536, true},   // LDS bytes the staged depthwise plans allow
+    {"dw_target", "FP8A_DW_TARGET", 4096, OPT_AT_LEAST, 256, 0, true},  // outputs per workgroup those plans aim at
+    {"dn_direct", "FP8A_DN_DIRECT", 1, OPT_RAW},  // exact convs with K <= 32, N <= 64 on dn_direct_kernel
+    {"v5ds", "FP8A_V5DS", 1, OPT_RAW},            // v5 depthwise 3x3 on conv_v5ds_kernel (0: conv_v5dw_kernel)
+    {"dw3", "FP8A_DW3", 2, OPT_RAW},              // exact depthwise 3x3: dn_dw3g (2), dn_dw3 (1), dn_group_conv (0)
+    {"mse_group", "FP8A_MSE_GROUP", 1, OPT_BOOL},  // fp8a_fp8_mse_search's grouped kernel (fq_mse.h)
+};
+static int opt_norm(const Option &o, int v) {
+    return o.kind == OPT_BOOL ? v != 0 : o.kind == OPT_AT_LEAST ? std::max(o.lo, v)
+         : o.kind == OPT_CLAMP ? std::min(o.hi, std::max(o.lo, v)) : v;
+}
+static const bool g_opts_loaded = [] {
+    for (Option &o : g_opts) {
+        const char *e = getenv(o.env);
+        o.value = !e ? o.def : o.env_raw ? atoi(e) : opt_norm(o, atoi(e));
+    }
+    return true;
+}();
+static inline int opt(OptId id) { return g_opts[id].value; }
+
+// The FP8A_NO_* switches of A/B runs (set means on; FP8A_CHAIN_TBX: a nonzero number), read once at load.
+struct EnvSwitches {
+    bool no_f8 = getenv("FP8A_NO_F8") != nullptr, no_f8_e5m2 = getenv("FP8A_NO_F8_E5M2") != nullptr;
+    bool no_v5mx = getenv("FP8A_NO_V5MX") != nullptr, no_tt = getenv("FP8A_NO_TT") != nullptr;
+    bool no_tt16 = getenv("FP8A_NO_TT16") != nullptr, no_mx = getenv("FP8A_NO_MX") != nullptr;
+    bool no_tbx = getenv("FP8A_NO_TBX") != nullptr, no_v5dw = getenv("FP8A_NO_V5DW") != nullptr;
+    bool chain_tbx = getenv("FP8A_CHAIN_TBX") != nullptr && atoi(getenv("FP8A_CHAIN_TBX")) != 0;
+};
+static const EnvSwitches g_env{};
+
 // gemm_f8mx_kernel's tile width: the fewest padded columns, ties to the wider tile (N = 16 -> 16,
-// 24 / 32 / 96 / 160 -> 32, multiples of 64 -> 64).  Option "xm_ncg" / FP8A_XM_NCG=<1|2|4> forces it
-// (0 = this choice; A/B runs and identity tests).
-static int g_opt_xm_ncg = getenv("FP8A_XM_NCG") ? atoi(getenv("FP8A_XM_NCG")) : 0;  // option "xm_ncg"
-// "xm_sign_rows": gemm_f8mx_kernel builds the negative-sign half of its tile table only for launches
-// whose A words address it (1, the default); 0: always both halves (the same bits, for A/B runs)
-static int g_opt_xm_sign_rows = getenv("FP8A_XM_SIGN_ROWS") ? atoi(getenv("FP8A_XM_SIGN_ROWS")) : 1;
-// "xm_pipe": gemm_f8mx_kernel's word-staged E4M3 / E5M2 launches run the instances whose K loop issues
-// its LDS reads one stage ahead of the conversions that use them (1, the default; gemm_f8mx.h PIPE,
-// DESIGN.md 3x); 0: the loop without it (the same conversions and MFMAs in the same order: the same bits)
-static int g_opt_xm_pipe = getenv("FP8A_XM_PIPE") ? atoi(getenv("FP8A_XM_PIPE")) != 0 : 1;
-// "xm_wave_rows": with "xm_pipe", the 128 x 64 instances (unsplit, or split through the reduce pass) run with
-// the math loop's waves mapped by rows -- wave w the tile's rows 32 w .. 32 w + 31 and all 64 columns, one table
-// address per (row block, K-step) for the four column groups (1, the default; gemm_f8mx.h WROWS, DESIGN.md
-// 3aa); 0: waves by columns (every accumulator the same MFMAs over the same codes in the same order: the same bits)
-static int g_opt_xm_wave_rows = getenv("FP8A_XM_WAVE_ROWS") ? atoi(getenv("FP8A_XM_WAVE_ROWS")) != 0 : 1;
-// "fq_fast": the matrix-core path's fake quantizers (the post quantizer, the emitted words' quantizer,
-// the fused input quantizer of the A pre-pass, the split-K reduction; not the fp32 staging) run
-// fq_apply_fast and the emitted word is formed from the quantized value's bits (fq_word), wherever the
-// uniform guards hold (fp8approx_common.h); 0 restores the literal forms.  Same bits either way.
-static int g_opt_fq_fast = getenv("FP8A_FQ_FAST") ? atoi(getenv("FP8A_FQ_FAST")) != 0 : 1;
+// 24 / 32 / 96 / 160 -> 32, multiples of 64 -> 64); option "xm_ncg" forces it.
 static int xm_ncg(int64_t N) {
-    const int forced = g_opt_xm_ncg;
+    const int forced = opt(OPT_XM_NCG);
     if (forced == 1 || forced == 2 || forced == 4) return forced;
     int best = 4;
     int64_t bp = (N + 63) / 64 * 64;
@@ -694,30 +732,6 @@ static hipEvent_t pool_event() {
     }
     return e;
 }
-// Options (fp8a_set_option):
-// "tbx_rw": output rows per thread of conv_tbx_kernel (1 or 2; 2 needs undilated rows).
-// FP8A_TBX_RW=<n> sets it at load.
-static int g_opt_tbx_rw = getenv("FP8A_TBX_RW") ? atoi(getenv("FP8A_TBX_RW")) : 2;
-// "tbs": the table-form depthwise 3x3 on the LDS-DMA-staged conv_tbsg_kernel (2, default:
-// MobileNetV2 E4M3 21.7k -> 22.8k, config 3 v9 19.6k -> 20.5k images/s), the register-staged
-// conv_tbs_kernel (1), both with the word pre-pass fused, or on tbx_decode_a + conv_tbx_kernel (0);
-// the same bits.  FP8A_TBS=<n>.
-static int g_opt_tbs = getenv("FP8A_TBS") ? atoi(getenv("FP8A_TBS")) : 2;
-// "dw3": the exact depthwise 3x3 on the LDS-DMA-staged, 4-outputs-per-thread dn_dw3g_kernel (2,
-// default: config 1 26.1k -> 28.3k images/s), the register-staged dn_dw3_kernel (1) or the general
-// dn_group_conv (0); the same bits.  FP8A_DW3=<n> sets it at load.
-static int g_opt_dw3 = getenv("FP8A_DW3") ? atoi(getenv("FP8A_DW3")) : 2;
-// "dn_direct": exact convolutions with K <= 32 and N <= 64 on dn_direct_kernel (1, default) or on
-// the bf16 matrix-core GEMM (0).  FP8A_DN_DIRECT=<n> sets it at load.
-static int g_opt_dn_direct = getenv("FP8A_DN_DIRECT") ? atoi(getenv("FP8A_DN_DIRECT")) : 1;
-// "v5ds": the v5 depthwise 3 x 3 on the staged conv_v5ds_kernel (1, default) or on the word
-// pre-passes + conv_v5dw_kernel (0); the same bits.  FP8A_V5DS=<n> sets it at load.
-static int g_opt_v5ds = getenv("FP8A_V5DS") ? atoi(getenv("FP8A_V5DS")) : 1;
-// "dw_target": outputs per workgroup the LDS-staged depthwise kernels aim at (plan_dw3 / plan_tbs;
-// halved until the window fits dw_lds).  FP8A_DW_TARGET=<n>.
-static int g_opt_dw_target = getenv("FP8A_DW_TARGET") ? atoi(getenv("FP8A_DW_TARGET")) : 4096;
-// "dw_lds": the LDS bytes per workgroup those plans allow (FP8A_DW_LDS=<n>, at most 64 KB).
-static int g_opt_dw_lds = getenv("FP8A_DW_LDS") ? atoi(getenv("FP8A_DW_LDS")) : 40960;
 
 // Compute units of the current device (cached); 256 (MI355X) when no device is visible.
 static int device_cus() {
@@ -748,15 +762,8 @@ static int device_cus() {
 // FP8A_SPLITK=<S> forces S (experiments).  g_splitk_launches: launches that ran split (their
 // splitk_reduce_kernel stores the output), host-side, fp8a_splitk_stats.
 static uint64_t g_splitk_launches = 0;
-// "splitk" (FP8A_SPLITK): the forced split count (0: chosen per launch).  "splitk_fixup" (default 0;
-// FP8A_SPLITK_FIXUP): the split E4M3 matrix-core launches sum their partials inside the launch (the tile's
-// last-arriving block, gemm_f8mx.h) instead of in splitk_reduce_kernel; same bits.  Off by default: it
-// measured slower than the separate pass on every workload (the last block reads S x 32 KB serially while
-// the reduce kernel streams at the memory rate).
-static int g_opt_splitk = getenv("FP8A_SPLITK") ? std::max(0, atoi(getenv("FP8A_SPLITK"))) : 0;
-static int g_opt_splitk_fixup = getenv("FP8A_SPLITK_FIXUP") ? atoi(getenv("FP8A_SPLITK_FIXUP")) != 0 : 0;
 static int choose_splits(int64_t M, int64_t N, int64_t K) {
-    const int forced = g_opt_splitk;
+    const int forced = opt(OPT_SPLITK);
     const int64_t kt = (K + BK - 1) / BK;
     if (forced > 0) return (int)std::max<int64_t>(1, std::min<int64_t>(forced, kt));
     const int64_t tiles = ((M + BM - 1) / BM) * ((N + BN - 1) / BN);
@@ -830,18 +837,15 @@ static size_t gemm_workspace_bytes(int64_t M, int64_t N, int64_t K, int64_t conv
 // TM_F8 form builds its V' from the raw table as xm_lut_word does, in fp32, so it takes the same tables.)
 // FP8A_NO_F8=1 keeps the arithmetic forms; FP8A_NO_F8_E5M2=1 only for E5M2 (A/B runs).
 static bool f8_form(int E, int Mw, uint32_t flags, const TablePack &tab) {
-    static const bool no_f8 = getenv("FP8A_NO_F8") != nullptr;
-    static const bool no_f8_e5 = getenv("FP8A_NO_F8_E5M2") != nullptr;
-    const bool fmt = (E == 4 && Mw == 3) || (E == 5 && Mw == 2 && !no_f8_e5);
-    return !no_f8 && !(flags & F_V5) && fmt && xm_table_form(tab, Mw, nullptr) &&
+    const bool fmt = (E == 4 && Mw == 3) || (E == 5 && Mw == 2 && !g_env.no_f8_e5m2);
+    return !g_env.no_f8 && !(flags & F_V5) && fmt && xm_table_form(tab, Mw, nullptr) &&
            (flags & F_S2N) && (flags & F_QBMA) && !(flags & F_GCLIP) && !(flags & F_TB);
 }
 
 // v5 (E5M2, adder wrap on): the matrix-core form of gemm_v5mx.h; FP8A_NO_V5MX=1 keeps
 // gemm_fast_kernel<TM_V5> (A/B runs)
 static bool v5mx_form(int Mw, uint32_t flags, int table_mode) {
-    static const bool no_v5mx = getenv("FP8A_NO_V5MX") != nullptr;
-    return table_mode == TM_V5 && Mw == 2 && (flags & F_OFUF) && !no_v5mx;
+    return table_mode == TM_V5 && Mw == 2 && (flags & F_OFUF) && !g_env.no_v5mx;
 }
 
 // The tile-table kernel (gemm_tt_kernel) applies: E3M4 / E2M5 (mantissa 4 or 5), any table mode
@@ -849,8 +853,7 @@ static bool v5mx_form(int Mw, uint32_t flags, int table_mode) {
 // not E2M5 with a signed table: its F7 form (two 32-row tables, one K-step per staged tile) was
 // measured slower than gemm_fast_kernel.
 static bool tt_form(int Mw, uint32_t flags, const TablePack &tab) {
-    static const bool no_tt = getenv("FP8A_NO_TT") != nullptr;
-    if (no_tt || (flags & F_V5) || !(Mw == 4 || Mw == 5) || !(flags & F_S2N) || !(flags & F_QBMA) ||
+    if (g_env.no_tt || (flags & F_V5) || !(Mw == 4 || Mw == 5) || !(flags & F_S2N) || !(flags & F_QBMA) ||
         (flags & F_GCLIP) || (flags & F_TB))
         return false;
     bool neg = false;
@@ -865,17 +868,29 @@ static bool tt_form(int Mw, uint32_t flags, const TablePack &tab) {
 // (option "tt16_mink": the smallest K of an unsigned-table launch on the f16 form; default 64 since
 // round 5: ResNet-50 E3M4 2,045 -> 2,082 images/s with its K = 64 / 128 / 147 launches on the f16
 // form, profiles/r05_tt16_mink/ -- round 3's tt16 lost 3 % there)
-static int g_opt_tt16_mink = getenv("FP8A_TT16_MINK") ? std::max(0, atoi(getenv("FP8A_TT16_MINK"))) : 64;
-// option "tt_band" (default 1; FP8A_TT_BAND): gemm_tt_kernel's band / zero wave-tile forms (gemm_tt.h)
-static int g_opt_tt_band = getenv("FP8A_TT_BAND") ? atoi(getenv("FP8A_TT_BAND")) : 1;
 static bool tt16_form(int Mw, bool f7, int64_t K) {
-    static const bool no_tt16 = getenv("FP8A_NO_TT16") != nullptr;
-    return !no_tt16 && Mw == 4 && (f7 || K >= g_opt_tt16_mink);
+    return !g_env.no_tt16 && Mw == 4 && (f7 || K >= opt(OPT_TT16_MINK));
 }
 
-static bool no_mx() {
-    static const bool v = getenv("FP8A_NO_MX") != nullptr;
-    return v;
+// Which matrix-core form (if any) a GEMM of this format, table and shape can take, and whether its
+// pre-decoded operands lie within the kernels' 32-bit byte offsets: the part of the decision that
+// run_gemm and the callers that fuse an input quantizer ahead of it share.  on: not FP8A_NO_MX.
+struct MxPlan {
+    bool f8, tt, v5mx, on, fits32;
+    int64_t kpad, npad;
+    bool any() const { return (f8 || tt || v5mx) && on; }
+};
+static MxPlan mx_plan(int E, int Mw, uint32_t flags, const TablePack &tab, int mode, int64_t N, int64_t K,
+                      int64_t a_words) {
+    MxPlan p;
+    p.f8 = f8_form(E, Mw, flags, tab);
+    p.tt = !p.f8 && tt_form(Mw, flags, tab);
+    p.v5mx = !p.f8 && v5mx_form(Mw, flags, mode);
+    p.on = !g_env.no_mx;
+    p.kpad = (K + BK - 1) / BK * BK;
+    p.npad = (N + BN - 1) / BN * BN;
+    p.fits32 = a_words < (1ll << 30) && p.kpad * p.npad * 4 < (1ll << 32);
+    return p;
 }
 
 // The conv word image: every plane is the input plane inside a zero border at least as wide as
@@ -917,13 +932,12 @@ static int64_t xm_a_words(const GemmArgs &a) {
 // 3; with round 5's pre-pass (4 loads in flight per thread) at most 1 tile wins everywhere:
 // MobileNetV2 E4M3 23,877 -> 24,482, E5M2 v9 21,225 -> 21,561, ResNet-50 E4M3 4,790 -> 4,840
 // (profiles/r05_af32/).
-static int g_opt_af32_maxct = getenv("FP8A_AF32_MAXCT") ? std::max(0, atoi(getenv("FP8A_AF32_MAXCT"))) : 1;
 // (a strided 1x1 conv's pre-pass decodes sh x sw input pixels per one the product reads, so the
 // fp32 staging is allowed up to sh x sw times as many column tiles: ResNet-18's downsampling convs)
-static int64_t af32_maxct(int sh, int sw) { return (int64_t)g_opt_af32_maxct * sh * sw; }
+static int64_t af32_maxct(int sh, int sw) { return (int64_t)opt(OPT_AF32_MAXCT) * sh * sw; }
 static bool xm_af32(const GemmArgs &a) {
     const int64_t bnt = 16 * a.xncg, ct = (a.N + bnt - 1) / bnt;
-    if (ct > (a.conv ? af32_maxct(a.sh, a.sw) : g_opt_af32_maxct)) return false;  // option "af32_maxct"
+    if (ct > (a.conv ? af32_maxct(a.sh, a.sw) : opt(OPT_AF32_MAXCT))) return false;  // option "af32_maxct"
     if (a.conv) {
         if (a.kh != 1 || a.kw != 1 || a.ph != 0 || a.pw != 0) return false;
         const int64_t bn = a.M / (a.Ho * a.Wo);
@@ -1086,7 +1100,9 @@ static int run_gemm(GemmArgs &a, const int32_t *table, void *ws, size_t ws_bytes
     const int mode0 = mode;
     // E4M3 / E5M2 with a non-negative (or no) table (xm_table_form), s2n and per-product quantization:
     // the LUT + hardware fp8 / bf8 form (FP8A_NO_F8=1 keeps the arithmetic form, for comparison)
-    if (f8_form(a.E, a.Mw, a.flags, a.tab)) mode = TM_F8;
+    const int64_t a_words = xm_a_words(a);
+    const MxPlan mx = mx_plan(a.E, a.Mw, a.flags, a.tab, mode, a.N, a.K, a_words);
+    if (mx.f8) mode = TM_F8;
     const int64_t total = a.M * a.N;
     const unsigned eblocks = (unsigned)std::min<int64_t>((total + 255) / 256, 4096);
     if (a.flags & F_TB) {
@@ -1124,17 +1140,15 @@ static int run_gemm(GemmArgs &a, const int32_t *table, void *ws, size_t ws_bytes
     // the matrix-core E4M3 kernel and the tile-table kernel (E3M4 / E2M5) need their pre-decoded
     // operands in the workspace (else gemm_fast_kernel runs); FP8A_NO_MX=1 forces the latter
     a.aw = nullptr;
-    const bool tt = mode != TM_F8 && tt_form(a.Mw, a.flags, a.tab);
-    const bool v5mx = v5mx_form(a.Mw, a.flags, mode);
-    if ((mode == TM_F8 || tt || v5mx) && !no_mx()) {
-        const int64_t kpad = kt * BK, npad = (a.N + BN - 1) / BN * BN;
+    const bool tt = mx.tt, v5mx = mx.v5mx;
+    if (mx.any()) {
+        const int64_t kpad = mx.kpad, npad = mx.npad;
         const size_t off = head + (a.splits > 1 ? splitk_bytes(a.M, a.N, a.K) : 0);
-        // gemm_f8mx_kernel reads its operands with 32-bit byte offsets
-        const int64_t a_words = xm_a_words(a);
         const WordImage wi = word_image(a.H, a.W, a.ph, a.pw);
         a.awH = wi.H; a.awW = wi.W; a.awph = wi.ph; a.awpw = wi.pw;
-        const bool fits32 = a_words < (1ll << 30) && kpad * npad * 4 < (1ll << 32);
-        if (fits32 && ws_bytes >= off + xm_operand_bytes(a.N, a.K, a_words)) {
+        // (the exact test: the operands behind this launch's own split-K partials; the callers that fuse
+        // an input quantizer test gemm_workspace_bytes, which is never smaller)
+        if (mx.fits32 && ws_bytes >= off + xm_operand_bytes(a.N, a.K, a_words)) {
             char *base = (char *)ws + off;
             a.aw = (const uint32_t *)base;
             a.awld = kpad;
@@ -1147,15 +1161,15 @@ static int run_gemm(GemmArgs &a, const int32_t *table, void *ws, size_t ws_bytes
             a.ttf7 = 0;
             for (int i = 0; tt && i < (1 << (2 * a.Mw)); ++i) a.ttf7 |= a.tab.raw[i] < 0;
             a.wfmt = v5mx ? 4 : tt ? (tt16_form(a.Mw, a.ttf7, a.K) ? 2 : 1) : 0;
-            if (a.wfmt == 1 && !g_opt_tt_band) a.ebr = nullptr;  // (gemm_tt_kernel: no band test)
+            if (a.wfmt == 1 && !opt(OPT_TT_BAND)) a.ebr = nullptr;  // (gemm_tt_kernel: no band test)
             a.xncg = tt ? 4 : xm_ncg(a.N);
-            a.xm_signs = g_opt_xm_sign_rows;
-            a.xm_pipe = g_opt_xm_pipe;
-            a.xm_wave_rows = g_opt_xm_wave_rows;
+            a.xm_signs = opt(OPT_XM_SIGN_ROWS);
+            a.xm_pipe = opt(OPT_XM_PIPE);
+            a.xm_wave_rows = opt(OPT_XM_WAVE_ROWS);
             // the in-launch split-K sum: the E4M3 matrix-core kernel (the E5M2 form's halved-block rerun
             // writes a tile's partials a second time, after its counter has run out: it keeps the reduce pass)
             a.skcnt = nullptr;
-            if (a.splits > 1 && g_opt_splitk_fixup && a.wfmt == 0 && a.Mw == 3) {
+            if (a.splits > 1 && opt(OPT_SPLITK_FIXUP) && a.wfmt == 0 && a.Mw == 3) {
                 a.skcnt = (uint32_t *)((char *)ws + head + splitk_part_bytes(a.splits, a.M, a.N));
                 a.sk_words = splitk_counter_words(a.M, a.N);
             }
@@ -1315,7 +1329,7 @@ static int run_dense(DenseArgs a, void *ws, size_t wsb, hipStream_t s) {
     }
     // a small convolution (the stem: K = 27, N = 32) as direct fp32 FMAs (dn_direct_kernel; option
     // "dn_direct", default 1): a 128 x 128 MFMA tile would carry 32 live columns and 27 of 64 k
-    if (g_opt_dn_direct && a.conv && a.K <= DD_K && a.N <= DD_N) {
+    if (opt(OPT_DN_DIRECT) && a.conv && a.K <= DD_K && a.N <= DD_N) {
         KernelEv kev{};
         if (g_ktime) {
             kev.a = pool_event();
@@ -1430,7 +1444,7 @@ static void launch_group_conv(const GcArgs &a, hipStream_t s) {
 // 40 KB, four workgroups per CU: measured against 2 / 8 / 16 KB-windowed plans, §3l); false when even 256 outputs' window does not fit (very wide rows).
 static bool plan_dw3(DwArgs &a, int S, size_t &lds, bool raw = false, int tap_bytes = 4) {
     const int64_t op = (int64_t)a.Ho * a.Wo;
-    for (int target = std::max(256, g_opt_dw_target); target >= 256; target /= 2) {
+    for (int target = std::max(256, opt(OPT_DW_TARGET)); target >= 256; target /= 2) {
         int PB, RB;
         if (op <= target) {
             RB = a.Ho;
@@ -1446,7 +1460,7 @@ static bool plan_dw3(DwArgs &a, int S, size_t &lds, bool raw = false, int tap_by
         const int64_t nsrc = RB == a.Ho ? (int64_t)PB * a.H * a.W : (int64_t)std::min(RS, a.H) * a.W;
         a.nimg = (int)(4 * ((nsrc + 6) / 4));
         const int64_t bytes = (raw ? (int64_t)a.nimg : (int64_t)PB * RS * WS) * 4 + (int64_t)PB * 9 * tap_bytes;
-        if (bytes > std::min(65536, std::max(4096, g_opt_dw_lds))) continue;
+        if (bytes > std::min(65536, std::max(4096, opt(OPT_DW_LDS)))) continue;
         a.PB = PB; a.RB = RB; a.nb = (a.Ho + RB - 1) / RB; a.RS = RS; a.WS = WS;
         a.inv_c = 1.0f / a.C; a.inv_ws = 1.0f / WS; a.inv_pst = 1.0f / (RS * WS);
         a.inv_wo = 1.0f / a.Wo; a.inv_pout = 1.0f / (RB * a.Wo);
@@ -1467,7 +1481,7 @@ static bool plan_tbs(TbsArgs &a, int S, int64_t planes, int64_t C, int64_t H, in
     const int nq = (int)((Wo + TBX_TW - 1) / TBX_TW);
     const int WS = ((4 * nq - 1) * S + 3 + 3) / 4 * 4;
     const int64_t op = Ho * Wo;
-    for (int target = std::max(256, g_opt_dw_target); target >= 256; target /= 2) {
+    for (int target = std::max(256, opt(OPT_DW_TARGET)); target >= 256; target /= 2) {
         int PB, RB;
         if (op <= target) {
             RB = (int)Ho;
@@ -1479,7 +1493,7 @@ static bool plan_tbs(TbsArgs &a, int S, int64_t planes, int64_t C, int64_t H, in
         }
         const int RS = (RB - 1) * S + 3;
         const int64_t bytes = (int64_t)PB * RS * WS * 4 + 512 + (int64_t)PB * 9 * 8;
-        if (bytes > std::min(65536, std::max(4096, g_opt_dw_lds))) continue;
+        if (bytes > std::min(65536, std::max(4096, opt(OPT_DW_LDS)))) continue;
         a.PB = PB; a.RB = RB; a.nb = (int)((Ho + RB - 1) / RB); a.RS = RS; a.WS = WS; a.nq = nq;
         a.inv_c = 1.0f / a.C; a.inv_ws = 1.0f / WS; a.inv_pst = 1.0f / (RS * WS);
         a.inv_nq = 1.0f / nq; a.inv_pq = 1.0f / (RB * nq);
@@ -1488,6 +1502,90 @@ static bool plan_tbs(TbsArgs &a, int S, int64_t planes, int64_t C, int64_t H, in
         return ((planes + PB - 1) / PB) * a.nb < (1ll << 24);
     }
     return false;
+}
+
+// ------------------------------------------------------------------------- convolution calls
+// A convolution's geometry: the caller's fields, and what conv_shape derives from them.
+struct ConvShape {
+    int64_t Bn, Cin, H, W, Cout;
+    int kh, kw, sh, sw, ph, pw, dh, dw, groups;
+    int64_t Ho, Wo, cog, cig, Mrows, Kg;  // output size, channels per group, the implicit GEMM's M and K
+};
+static bool groups_ok(int groups, int64_t Cin, int64_t Cout) {
+    return groups > 0 && Cout % groups == 0 && Cin % groups == 0;
+}
+static bool bad_geometry(const ConvShape &c) {
+    return c.kh < 1 || c.kw < 1 || c.sh < 1 || c.sw < 1 || c.dh < 1 || c.dw < 1 || c.ph < 0 || c.pw < 0;
+}
+// Checks the caller's fields (groups, then kernel / stride / dilation / padding, then the output size)
+// and fills the derived ones.  Entry points without groups pass 1.
+static int conv_shape(ConvShape &c) {
+    if (!groups_ok(c.groups, c.Cin, c.Cout)) return fail(FP8A_EINVAL, "bad groups");
+    if (bad_geometry(c)) return fail(FP8A_EINVAL, "bad convolution geometry");
+    c.Ho = (c.H + 2 * c.ph - c.dh * (c.kh - 1) - 1) / c.sh + 1;
+    c.Wo = (c.W + 2 * c.pw - c.dw * (c.kw - 1) - 1) / c.sw + 1;
+    if (c.Ho <= 0 || c.Wo <= 0) return fail(FP8A_EINVAL, "empty convolution output");
+    c.cog = c.Cout / c.groups;
+    c.cig = c.Cin / c.groups;
+    c.Mrows = c.Bn * c.Ho * c.Wo;
+    c.Kg = c.cig * c.kh * c.kw;
+    return FP8A_OK;
+}
+
+// One convolution launch family (conv2d_impl): every public entry point fills the fields it has.
+struct ConvCall {
+    ConvShape g;
+    const float *x, *w;
+    float *y;
+    int E, Mw;
+    const int32_t *bA, *bW, *bR, *table;
+    uint32_t flags;
+    const float *bn;  // the BN / activation epilogue
+    int act;
+    float act_lo, act_hi;
+    void *workspace;
+    size_t workspace_bytes;
+    hipStream_t s;
+    FqIn fq;  // the input quantizer (fq.mx set: x is not yet quantized), its bias outputs, the fake-quant buffer
+    float *fqb;
+    int32_t *fqi;
+    float *xq;
+    const float *res;  // the block tail
+    int post_act;
+    float post_lo, post_hi;
+    FqIn post_fq;
+    float *post_bout;
+    int32_t *post_ibout;
+    const uint32_t *in_img;  // the chain's word images
+    EmitW em;
+};
+
+// A fused quantizer's arguments (none when mx is null): format, then its bias outputs.
+static int fused_quantizer(const float *mx, int nbits, int mbits, int sign_bits, float *bias_out, int32_t *ibias_out,
+                           FqIn &f) {
+    f = FqIn{};
+    if (!mx) return FP8A_OK;
+    const int qE = nbits - sign_bits - mbits;
+    if (mbits < 1 || qE < 1) return fail(FP8A_EFORMAT, "bad FP8 quantizer format");
+    if (!bias_out || !ibias_out) return fail(FP8A_EINVAL, "null pointer");
+    f = FqIn{mx, qE, mbits, sign_bits};
+    return FP8A_OK;
+}
+
+// The fake-quant buffer of the non-fused paths (elems floats; elems < 0: none) sits at the workspace's
+// end: rest = the bytes before it.
+static int carve_xq(void *workspace, size_t workspace_bytes, int64_t elems, const char *name, size_t &rest,
+                    float *&xq) {
+    const size_t xq_bytes = elems < 0 ? 0 : align256((size_t)elems * sizeof(float));
+    if (workspace == nullptr || workspace_bytes < FLAG_BYTES + xq_bytes)
+        return fail(FP8A_EINVAL, std::string(name) + " workspace too small");
+    rest = (workspace_bytes - xq_bytes) & ~(size_t)255;
+    xq = elems < 0 ? nullptr : (float *)((char *)workspace + rest);
+    return FP8A_OK;
+}
+
+static int invalidate_image(const EmitW &em, hipStream_t s) {
+    return dev_fill(em.invalid, 1, sizeof(uint32_t), s) != hipSuccess ? hip_check("fp8a word image header") : FP8A_OK;
 }
 
 extern "C" {
@@ -1538,102 +1636,14 @@ int fp8a_kernel_time(double *out, int reset) {
     return FP8A_OK;
 }
 
-// "mse_group": fp8a_fp8_mse_search runs the grouped form of the search kernel (fq_mse.h; same bytes,
-// 2.0-2.6 x faster on the DESIGN.md 3u tensors)
-static int g_opt_mse_group = getenv("FP8A_MSE_GROUP") ? atoi(getenv("FP8A_MSE_GROUP")) != 0 : 1;
-
 int fp8a_set_option(const char *name, int value) {
     if (name == nullptr) return fail(FP8A_EINVAL, "null pointer");
-    if (strcmp(name, "xm_ncg") == 0) {
-        const int old = g_opt_xm_ncg;
-        g_opt_xm_ncg = value;
-        return old;
-    }
-    if (strcmp(name, "xm_sign_rows") == 0) {
-        const int old = g_opt_xm_sign_rows;
-        g_opt_xm_sign_rows = value != 0;
-        return old;
-    }
-    if (strcmp(name, "xm_pipe") == 0) {
-        const int old = g_opt_xm_pipe;
-        g_opt_xm_pipe = value != 0;
-        return old;
-    }
-    if (strcmp(name, "xm_wave_rows") == 0) {
-        const int old = g_opt_xm_wave_rows;
-        g_opt_xm_wave_rows = value != 0;
-        return old;
-    }
-    if (strcmp(name, "splitk_fixup") == 0) {
-        const int old = g_opt_splitk_fixup;
-        g_opt_splitk_fixup = value != 0;
-        return old;
-    }
-    if (strcmp(name, "splitk") == 0) {
-        const int old = g_opt_splitk;
-        g_opt_splitk = std::max(0, value);
-        return old;
-    }
-    if (strcmp(name, "fq_fast") == 0) {
-        const int old = g_opt_fq_fast;
-        g_opt_fq_fast = value != 0;
-        return old;
-    }
-    if (strcmp(name, "af32_maxct") == 0) {
-        const int old = g_opt_af32_maxct;
-        g_opt_af32_maxct = std::max(0, value);
-        return old;
-    }
-    if (strcmp(name, "tt_band") == 0) {
-        const int old = g_opt_tt_band;
-        g_opt_tt_band = value;
-        return old;
-    }
-    if (strcmp(name, "tt16_mink") == 0) {
-        const int old = g_opt_tt16_mink;
-        g_opt_tt16_mink = std::max(0, value);
-        return old;
-    }
-    if (strcmp(name, "tbx_rw") == 0) {
-        const int old = g_opt_tbx_rw;
-        g_opt_tbx_rw = value;
-        return old;
-    }
-    if (strcmp(name, "tbs") == 0) {
-        const int old = g_opt_tbs;
-        g_opt_tbs = value;
-        return old;
-    }
-    if (strcmp(name, "dw_lds") == 0) {
-        const int old = g_opt_dw_lds;
-        g_opt_dw_lds = std::min(65536, std::max(4096, value));
-        return old;
-    }
-    if (strcmp(name, "dw_target") == 0) {
-        const int old = g_opt_dw_target;
-        g_opt_dw_target = std::max(256, value);
-        return old;
-    }
-    if (strcmp(name, "dn_direct") == 0) {
-        const int old = g_opt_dn_direct;
-        g_opt_dn_direct = value;
-        return old;
-    }
-    if (strcmp(name, "v5ds") == 0) {
-        const int old = g_opt_v5ds;
-        g_opt_v5ds = value;
-        return old;
-    }
-    if (strcmp(name, "dw3") == 0) {
-        const int old = g_opt_dw3;
-        g_opt_dw3 = value;
-        return old;
-    }
-    if (strcmp(name, "mse_group") == 0) {
-        const int old = g_opt_mse_group;
-        g_opt_mse_group = value != 0;
-        return old;
-    }
+    for (Option &o : g_opts)
+        if (strcmp(name, o.name) == 0) {
+            const int old = o.value;
+            o.value = opt_norm(o, value);
+            return old;
+        }
     return fail(FP8A_EINVAL, std::string("unknown option ") + name);
 }
 
@@ -1727,28 +1737,32 @@ int fp8a_dense_matmul(const float *A, int64_t sam, int64_t sak, const float *B, 
 
 size_t fp8a_dense_conv2d_workspace_size(int64_t Bn, int64_t Cin, int64_t H, int64_t W, int64_t Cout, int kh, int kw,
                                         int sh, int sw, int ph, int pw, int dh, int dw) {
-    const int64_t Ho = (H + 2 * ph - dh * (kh - 1) - 1) / sh + 1;
-    const int64_t Wo = (W + 2 * pw - dw * (kw - 1) - 1) / sw + 1;
-    if (Ho <= 0 || Wo <= 0) return 0;
-    return dense_ws_bytes(Bn * Ho * Wo, Cout, Cin * kh * kw);
+    ConvShape c{Bn, Cin, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, 1};
+    return conv_shape(c) ? 0 : dense_ws_bytes(c.Mrows, Cout, c.Kg);
+}
+
+// The exact convolution as run_dense's implicit GEMM (geometry rejected as conv_shape does, + negative counts).
+static int dense_conv(ConvShape c, const float *x, const float *w, float *y, int fmt, const DnFuse &fz, void *ws,
+                      size_t ws_bytes, hipStream_t s) {
+    if (bad_geometry(c) || c.Bn < 0 || c.Cin < 0 || c.Cout < 0) return fail(FP8A_EINVAL, "bad convolution geometry");
+    const int rc = conv_shape(c);
+    if (rc) return rc;
+    DenseArgs a = dense_args();
+    a.x = x; a.w = w; a.y = y; a.conv = 1;
+    a.C = c.Cin; a.H = c.H; a.W = c.W; a.Ho = c.Ho; a.Wo = c.Wo;
+    a.kh = c.kh; a.kw = c.kw; a.sh = c.sh; a.sw = c.sw; a.ph = c.ph; a.pw = c.pw; a.dh = c.dh; a.dw = c.dw;
+    a.M = c.Mrows; a.N = c.Cout; a.K = c.Kg;
+    a.sbk = 1; a.sbn = a.K;  // w [Cout][Cin][kh][kw]: B(k, n) = w[n * K + k]
+    a.ldc = c.Cout; a.fmt = fmt;
+    a.fz = fz;
+    return run_dense(a, ws, ws_bytes, s);
 }
 
 int fp8a_dense_conv2d(const float *x, const float *w, float *y, int64_t Bn, int64_t Cin, int64_t H, int64_t W,
                       int64_t Cout, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw, int fmt,
                       void *workspace, size_t workspace_bytes, fp8a_stream_t stream) {
-    if (kh < 1 || kw < 1 || sh < 1 || sw < 1 || dh < 1 || dw < 1 || ph < 0 || pw < 0 || Bn < 0 || Cin < 0 || Cout < 0)
-        return fail(FP8A_EINVAL, "bad convolution geometry");
-    const int64_t Ho = (H + 2 * ph - dh * (kh - 1) - 1) / sh + 1;
-    const int64_t Wo = (W + 2 * pw - dw * (kw - 1) - 1) / sw + 1;
-    if (Ho <= 0 || Wo <= 0) return fail(FP8A_EINVAL, "empty convolution output");
-    DenseArgs a = dense_args();
-    a.x = x; a.w = w; a.y = y; a.conv = 1;
-    a.C = Cin; a.H = H; a.W = W; a.Ho = Ho; a.Wo = Wo;
-    a.kh = kh; a.kw = kw; a.sh = sh; a.sw = sw; a.ph = ph; a.pw = pw; a.dh = dh; a.dw = dw;
-    a.M = Bn * Ho * Wo; a.N = Cout; a.K = Cin * kh * kw;
-    a.sbk = 1; a.sbn = a.K;  // w [Cout][Cin][kh][kw]: B(k, n) = w[n * K + k]
-    a.ldc = Cout; a.fmt = fmt;
-    return run_dense(a, workspace, workspace_bytes, (hipStream_t)stream);
+    return dense_conv(ConvShape{Bn, Cin, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, 1}, x, w, y, fmt, DnFuse{}, workspace,
+                      workspace_bytes, (hipStream_t)stream);
 }
 
 static int grouped_conv_impl(const float *x, const float *w, float *y, int64_t Bn, int64_t Cin, int64_t H, int64_t W,
@@ -1765,17 +1779,17 @@ int fp8a_grouped_conv2d(const float *x, const float *w, float *y, int64_t Bn, in
 static int grouped_conv_impl(const float *x, const float *w, float *y, int64_t Bn, int64_t Cin, int64_t H, int64_t W,
                              int64_t Cout, int groups, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw,
                              const DnFuse &fz, hipStream_t stream) {
-    if (kh < 1 || kw < 1 || sh < 1 || sw < 1 || dh < 1 || dw < 1 || ph < 0 || pw < 0 || Bn < 0 || Cin < 0 || Cout < 0)
-        return fail(FP8A_EINVAL, "bad convolution geometry");
-    if (groups < 1 || Cin % groups != 0 || Cout % groups != 0) return fail(FP8A_EINVAL, "channels not divisible by groups");
-    const int64_t Ho = (H + 2 * ph - dh * (kh - 1) - 1) / sh + 1;
-    const int64_t Wo = (W + 2 * pw - dw * (kw - 1) - 1) / sw + 1;
-    if (Ho <= 0 || Wo <= 0) return fail(FP8A_EINVAL, "empty convolution output");
+    ConvShape c{Bn, Cin, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, groups};
+    if (bad_geometry(c) || Bn < 0 || Cin < 0 || Cout < 0) return fail(FP8A_EINVAL, "bad convolution geometry");
+    if (!groups_ok(groups, Cin, Cout)) return fail(FP8A_EINVAL, "channels not divisible by groups");
+    const int rc = conv_shape(c);
+    if (rc) return rc;
+    const int64_t Ho = c.Ho, Wo = c.Wo;
     GcArgs a{};
     a.x = x; a.w = w; a.y = y;
     a.Cin = Cin; a.H = H; a.W = W; a.Cout = Cout; a.Ho = Ho; a.Wo = Wo;
     a.total = Bn * Cout * Ho * ((Wo + GC_OW - 1) / GC_OW);
-    a.cig = (int)(Cin / groups); a.cog = (int)(Cout / groups);
+    a.cig = (int)c.cig; a.cog = (int)c.cog;
     a.kh = kh; a.kw = kw; a.sh = sh; a.sw = sw; a.ph = ph; a.pw = pw; a.dh = dh; a.dw = dw;
     a.fz = fz;
     if (a.total == 0) {  // (no kernel to leave the fused quantizers' biases)
@@ -1786,7 +1800,7 @@ static int grouped_conv_impl(const float *x, const float *w, float *y, int64_t B
         return FP8A_OK;
     }
     if (!x || !w || !y) return fail(FP8A_EINVAL, "null pointer");
-    if (g_opt_dw3 && a.cig == 1 && a.cog == 1 && kh == 3 && kw == 3 && dh == 1 && dw == 1 && sh == sw && pw <= DW_OX &&
+    if (opt(OPT_DW3) && a.cig == 1 && a.cog == 1 && kh == 3 && kw == 3 && dh == 1 && dw == 1 && sh == sw && pw <= DW_OX &&
         (sh == 1 || sh == 2)) {
         DwArgs d{};
         d.x = x; d.w = w; d.y = y; d.fz = fz;
@@ -1796,7 +1810,7 @@ static int grouped_conv_impl(const float *x, const float *w, float *y, int64_t B
         // (the staged kernels index a plane in 32-bit ints and divide by float reciprocals, dw_div:
         // planes of at most 2^22 values; larger ones take dn_group_conv)
         d.nx = Bn * Cin * H * W;
-        const bool raw = g_opt_dw3 == 2;
+        const bool raw = opt(OPT_DW3) == 2;
         if (H < (1 << 20) && W < (1 << 20) && Cout < (1 << 20) && H * W < (1ll << 22) && plan_dw3(d, sh, lds, raw)) {
             const unsigned g = (unsigned)(((d.planes + d.PB - 1) / d.PB) * d.nb);
             if (raw && sh == 1) dn_dw3g_kernel<1><<<g, 256, lds, stream>>>(d);
@@ -1893,7 +1907,7 @@ static GemmArgs make_args(const float *A, int64_t lda, const float *B, int64_t s
     a.bA = bA; a.bB = bB; a.bBs = bBs; a.bR = bR;
     a.flags = flags; a.nchw = 0; a.hw = 1; a.ctot = N; a.coff = 0;
     a.splits = 1; a.kchunk = K; a.part = nullptr;
-    a.fq_fast = g_opt_fq_fast;
+    a.fq_fast = opt(OPT_FQ_FAST);
     return a;
 }
 
@@ -2064,11 +2078,9 @@ int fp8a_matmul_check(const float *A, int64_t lda, const float *B, int64_t sbk, 
 
 size_t fp8a_conv2d_check_workspace_size(int64_t Bn, int64_t Cin, int64_t H, int64_t W, int64_t Cout, int kh, int kw,
                                         int sh, int sw, int ph, int pw, int dh, int dw, int groups) {
-    if (groups <= 0 || Cout % groups != 0 || Cin % groups != 0 || sh <= 0 || sw <= 0) return 0;
-    const int64_t Ho = (H + 2 * ph - dh * (kh - 1) - 1) / sh + 1;
-    const int64_t Wo = (W + 2 * pw - dw * (kw - 1) - 1) / sw + 1;
-    if (Ho <= 0 || Wo <= 0 || Bn <= 0 || Cout <= 0 || Cin <= 0 || kh <= 0 || kw <= 0) return 0;
-    return check_ws_bytes(Bn * Cout * Ho * Wo, Bn * Ho * Wo, Cout / groups, groups);
+    ConvShape c{Bn, Cin, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, groups};
+    if (conv_shape(c) || Bn <= 0 || Cout <= 0 || Cin <= 0) return 0;
+    return check_ws_bytes(Cout * c.Mrows, c.Mrows, c.cog, groups);
 }
 
 int fp8a_conv2d_check(const float *x, const float *w, float *y, int64_t Bn, int64_t Cin, int64_t H, int64_t W,
@@ -2078,14 +2090,13 @@ int fp8a_conv2d_check(const float *x, const float *w, float *y, int64_t Bn, int6
                       size_t workspace_bytes, fp8a_stream_t stream) {
     int rc = check_format(E, Mw);
     if (rc) return rc;
-    if (groups <= 0 || Cout <= 0 || Cin <= 0 || Cout % groups != 0 || Cin % groups != 0)
-        return fail(FP8A_EINVAL, "bad groups");
-    if (kh <= 0 || kw <= 0 || sh <= 0 || sw <= 0 || dh <= 0 || dw <= 0 || ph < 0 || pw < 0 || Bn <= 0 || H <= 0 || W <= 0)
-        return fail(FP8A_EINVAL, "bad convolution geometry");
-    const int64_t Ho = (H + 2 * ph - dh * (kh - 1) - 1) / sh + 1;
-    const int64_t Wo = (W + 2 * pw - dw * (kw - 1) - 1) / sw + 1;
-    if (Ho <= 0 || Wo <= 0) return fail(FP8A_EINVAL, "empty convolution output");
-    const int64_t cog = Cout / groups, cig = Cin / groups, Kg = cig * kh * kw, Mrows = Bn * Ho * Wo;
+    // (the self-check wants positive extents on top of conv_shape's checks)
+    ConvShape g{Bn, Cin, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, groups};
+    if (!groups_ok(groups, Cin, Cout) || Cout <= 0 || Cin <= 0) return fail(FP8A_EINVAL, "bad groups");
+    if (bad_geometry(g) || Bn <= 0 || H <= 0 || W <= 0) return fail(FP8A_EINVAL, "bad convolution geometry");
+    rc = conv_shape(g);
+    if (rc) return rc;
+    const int64_t Ho = g.Ho, Wo = g.Wo, cog = g.cog, cig = g.cig, Kg = g.Kg, Mrows = g.Mrows;
     // single-output-channel groups: the tensor-bias semantics, as fp8a_conv2d (approx_calculation.py:800-809)
     const uint32_t fl = (flags & ~F_TB) | ((cog == 1 && !(flags & F_V5)) ? (uint32_t)F_TB : 0u);
     GemmArgs a = make_args(nullptr, 0, w, 1, Kg, y, 0, Mrows, cog, Kg, E, Mw, bA, bW, 1, bR, fl);
@@ -2104,10 +2115,10 @@ int fp8a_conv2d_check(const float *x, const float *w, float *y, int64_t Bn, int6
 
 int fp8a_im2col(const float *x, float *out, int64_t Bn, int64_t Cin, int64_t H, int64_t W, int kh, int kw, int sh,
                 int sw, int ph, int pw, int dh, int dw, fp8a_stream_t stream) {
-    const int64_t Ho = (H + 2 * ph - dh * (kh - 1) - 1) / sh + 1;
-    const int64_t Wo = (W + 2 * pw - dw * (kw - 1) - 1) / sw + 1;
-    if (Ho <= 0 || Wo <= 0) return fail(FP8A_EINVAL, "empty convolution output");
-    const int64_t total = Bn * Ho * Wo * Cin * kh * kw;
+    ConvShape c{Bn, Cin, H, W, Cin, kh, kw, sh, sw, ph, pw, dh, dw, 1};
+    const int rc = conv_shape(c);
+    if (rc) return rc;
+    const int64_t Ho = c.Ho, Wo = c.Wo, total = c.Mrows * c.Kg;
     if (total == 0) return FP8A_OK;
     const int64_t blocks = std::min<int64_t>((total + 255) / 256, 65536);
     im2col_kernel<<<(unsigned)blocks, 256, 0, (hipStream_t)stream>>>(x, out, Bn, Cin, H, W, kh, kw, sh, sw, ph, pw,
@@ -2117,12 +2128,10 @@ int fp8a_im2col(const float *x, float *out, int64_t Bn, int64_t Cin, int64_t H, 
 
 size_t fp8a_conv2d_workspace_size(int64_t Bn, int64_t Cin, int64_t H, int64_t W, int64_t Cout, int kh, int kw,
                                   int sh, int sw, int ph, int pw, int dh, int dw, int groups) {
-    if (groups <= 0 || Cout % groups != 0 || Cin % groups != 0) return 0;
-    const int64_t Ho = (H + 2 * ph - dh * (kh - 1) - 1) / sh + 1;
-    const int64_t Wo = (W + 2 * pw - dw * (kw - 1) - 1) / sw + 1;
-    if (Ho <= 0 || Wo <= 0) return 0;
+    ConvShape c{Bn, Cin, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, groups};
+    if (conv_shape(c)) return 0;
     // implicit GEMM (no im2col image): the off-grid flag word + split-K partials of one group
-    const int64_t Mrows = Bn * Ho * Wo, cog = Cout / groups, Kg = (Cin / groups) * kh * kw;
+    const int64_t Mrows = c.Mrows, cog = c.cog, Kg = c.Kg;
     if (Mrows <= 0 || Kg <= 0) return FLAG_BYTES;
     // tensor-bias kernels: A words (+ the v5 depthwise form's B words)
     if (cog == 1) return FLAG_BYTES + align256((size_t)(Bn * Cin * H * W) * 4) + (size_t)(Cout * kh * kw) * 8;
@@ -2152,305 +2161,343 @@ __global__ void fq_bias_kernel(FqIn fq, float *bias_out, int32_t *ibias_out) {
     *ibias_out = (int32_t)b;
 }
 
-static int conv2d_impl(const float *x, const float *w, float *y, int64_t Bn, int64_t Cin, int64_t H, int64_t W,
-                       int64_t Cout, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw, int groups,
-                       int E, int Mw, const int32_t *bA, const int32_t *bW, const int32_t *bR, const int32_t *table,
-                       uint32_t flags, const float *bn, int act, float act_lo, float act_hi, void *workspace,
-                       size_t workspace_bytes, hipStream_t s, FqIn fq, float *fqb, int32_t *fqi, float *xq,
-                       const float *res = nullptr, int post_act = 0, float post_lo = 0.0f, float post_hi = 0.0f,
-                       FqIn post_fq = FqIn{}, const uint32_t *in_img = nullptr, const EmitW &em_in = EmitW{},
-                       float *post_bout = nullptr, int32_t *post_ibout = nullptr) {
-    const float2 *ep = reinterpret_cast<const float2 *>(bn);
-    if (ep && (((uintptr_t)bn) & 7) != 0) return fail(FP8A_EINVAL, "bn parameters must be 8-byte aligned");
-    int rc = check_format(E, Mw);
-    if (rc) return rc;
-    if (groups <= 0 || Cout % groups != 0 || Cin % groups != 0) return fail(FP8A_EINVAL, "bad groups");
-    const int64_t Ho = (H + 2 * ph - dh * (kh - 1) - 1) / sh + 1;
-    const int64_t Wo = (W + 2 * pw - dw * (kw - 1) - 1) / sw + 1;
-    if (Ho <= 0 || Wo <= 0) return fail(FP8A_EINVAL, "empty convolution output");
-    const int64_t cog = Cout / groups, cig = Cin / groups;
-    const int64_t Mrows = Bn * Ho * Wo, Ktot = Cin * kh * kw, Kg = cig * kh * kw;
-    if (Mrows == 0) {  // (the output quantizer's bias is still set, as its forward would)
-        if (post_bout) fq_bias_kernel<<<1, 1, 0, s>>>(post_fq, post_bout, post_ibout);
-        return post_bout ? hip_check("fp8a output-quantizer bias") : FP8A_OK;
-    }
-    // non-fused input quantization: one fake-quant pass into xq, then the plain path on it
-    auto materialize = [&]() -> int {
-        const int64_t nx = Bn * Cin * H * W;
-        fp8_quantize_kernel<<<(unsigned)std::max<int64_t>(1, std::min<int64_t>((nx + 255) / 256, 65536)), 256, 0, s>>>(
-            x, 1, nx, fq.mx, 0, fq.E, fq.M, fq.S, xq, fqb, fqi);
-        x = xq;
-        bA = fqi;
-        fq.mx = nullptr;
-        return hip_check("fp8a input fake-quant");
-    };
-    const bool post = res || post_act || post_fq.mx;
-    // v5 words (form 2) come from the staged v5 depthwise kernel only: any other launch flags them invalid
-    EmitW em = em_in;
-    if (em.w && (em.form == 2) != ((flags & F_V5) && cog == 1 && !post && groups > 1)) {
-        if (dev_fill(em.invalid, 1, sizeof(uint32_t), s) != hipSuccess) return hip_check("fp8a word image header");
-        em = EmitW{};
-    }
-    if (res && (res == y || (((uintptr_t)res) & 15) != 0))
-        return fail(FP8A_EINVAL, "the residual must be a 16-byte aligned tensor other than the output");
-    if (cog == 1 && !(flags & F_V5)) {  // v5 never had tensor-bias semantics: it takes the GEMM path
-        if (post) return fail(FP8A_EINVAL, "no block-output epilogue for single-output-channel groups");
-        TablePack tp;
-        int mode;
-        rc = pack_table(table, Mw, flags & F_APPROX, tp, mode);
-        if (rc) return rc;
-        const int64_t total = Bn * Cout * Ho * Wo;
-        uint32_t *gate = nullptr;
-        ArenaLease lease;  // (gate: a slot of the stream's flag arena, flag_arena)
-        bool emitted = false;  // (a requested word image: only the staged table-form kernel writes it)
-        // fast form: needs s2n on and golden_clip_OF off (else every launch would fall back)
-        const bool fast_ok = (flags & F_S2N) && !(flags & F_GCLIP) && workspace != nullptr &&
-                             workspace_bytes >= FLAG_BYTES && Cout <= 65535 && Bn <= 65535;
-        // E4M3 / E5M2 table form (conv_tbx.h): a table of xm_table_form, qbma, 3-wide kernel rows, stride 1 or 2
-        const int64_t nwg = (Wo + TBX_TW - 1) / TBX_TW, items = Bn * Cout * Ho * nwg;
-        static const bool no_tbx = getenv("FP8A_NO_TBX") != nullptr;
-        const bool tbx_ok = fast_ok && !no_tbx && ((E == 4 && Mw == 3) || (E == 5 && Mw == 2)) &&
-                            xm_table_form(tp, Mw, nullptr) &&
-                            (flags & F_QBMA) && kw == 3 && dw == 1 && sh == sw && (sw == 1 || sw == 2) &&
-                            items < (1ll << 31) && Ho * Wo < (1ll << 31) &&
-                            workspace_bytes >= FLAG_BYTES + (size_t)(Bn * Cin * H * W) * 4;
-        if (fq.mx && !tbx_ok) {
-            rc = materialize();
-            if (rc) return rc;
-        }
-        if (tbx_ok) {
-            if (!dw_lease(s, workspace, workspace_bytes, lease)) return lease_error();
-            gate = lease.mine;
-            // the input's table-form words from the producing launch (fp8a_conv2d_chain, next_form 1:
-            // header + [Bn][Cin][H][W] words of fq_in(x)); the pre-pass then runs gated on its header
-            const bool use_img = in_img != nullptr && fq.mx != nullptr;
-            uint32_t *aw = use_img ? const_cast<uint32_t *>(in_img) + 64 : (uint32_t *)((char *)workspace + FLAG_BYTES);
-            TbsArgs tb{};
-            size_t tlds = 0;
-            // tbs = 2 (default): the LDS-DMA-staged conv_tbsg_kernel
-            DwArgs dg{};
-            size_t glds = 0;
-            const bool tbsg = g_opt_tbs == 2 && !use_img && cig == 1 && kh == 3 && dh == 1 && H < (1 << 20) &&
-                              W < (1 << 20) && Cout < (1 << 20) && H * W < (1ll << 22) && [&]() {
-                                  dg.planes = Bn * Cout; dg.C = (int)Cout; dg.H = (int)H; dg.W = (int)W;
-                                  dg.Ho = (int)Ho; dg.Wo = (int)Wo; dg.ph = ph; dg.pw = pw; dg.nx = Bn * Cin * H * W;
-                                  if (!plan_dw3(dg, sw, glds, true, tbsg_tap_bytes())) return false;
-                                  glds = tbsg_lds_bytes(dg.PB, dg.nimg);
-                                  return glds <= 65536;
-                              }();
-            if (tbsg) {
-                const unsigned gb = (unsigned)(((dg.planes + dg.PB - 1) / dg.PB) * dg.nb);
-                // (it emits the next matrix-core convolution's words when fp8a_conv2d_chain asked, em.form 0)
-                const EmitW emt = em.w && em.form == 0 ? em : EmitW{};
-                emitted = emt.w != nullptr;
+// Non-fused input quantization: one fake-quant pass into xq, then the plain path on it.
+static int materialize_input(ConvCall &c) {
+    const int64_t nx = c.g.Bn * c.g.Cin * c.g.H * c.g.W;
+    fp8_quantize_kernel<<<(unsigned)std::max<int64_t>(1, std::min<int64_t>((nx + 255) / 256, 65536)), 256, 0, c.s>>>(
+        c.x, 1, nx, c.fq.mx, 0, c.fq.E, c.fq.M, c.fq.S, c.xq, c.fqb, c.fqi);
+    c.x = c.xq;
+    c.bA = c.fqi;
+    c.fq.mx = nullptr;
+    return hip_check("fp8a input fake-quant");
+}
+
+// The plan of the LDS-DMA-staged depthwise 3 x 3 kernels over the convolution's planes: plan_dw3's raw form,
+// then the kernel's own LDS size (conv_tbsg_kernel: tbsg_lds_bytes; conv_v5ds_kernel: 8-byte tap words).
+static bool plan_staged_dw(DwArgs &d, const ConvShape &g, int stride, bool tbsg, size_t &lds) {
+    if (g.H >= (1 << 20) || g.W >= (1 << 20) || g.Cout >= (1 << 20) || g.H * g.W >= (1ll << 22)) return false;
+    d.planes = g.Bn * g.Cout; d.C = (int)g.Cout; d.H = (int)g.H; d.W = (int)g.W;
+    d.Ho = (int)g.Ho; d.Wo = (int)g.Wo; d.ph = g.ph; d.pw = g.pw; d.nx = g.Bn * g.Cin * g.H * g.W;
+    if (!plan_dw3(d, stride, lds, true, tbsg ? tbsg_tap_bytes() : 4)) return false;
+    lds = tbsg ? tbsg_lds_bytes(d.PB, d.nimg) : (size_t)d.nimg * 4 + (size_t)d.PB * 9 * 8;
+    return lds <= 65536;
+}
+
+static TbxArgs tbx_args(const ConvShape &g, int64_t nwg, int64_t items) {
+    TbxArgs ta;
+    ta.Cin = g.Cin; ta.H = g.H; ta.W = g.W; ta.Cout = g.Cout; ta.Ho = g.Ho; ta.Wo = g.Wo;
+    ta.kh = g.kh; ta.ph = g.ph; ta.pw = g.pw; ta.dh = g.dh; ta.cpg = (int)g.cig;
+    ta.nwg = (uint32_t)nwg;
+    ta.items = (uint32_t)items;
+    return ta;
+}
+
+// The (stride, Mw[, rows per thread]) instances of the table-form depthwise kernels (conv_tbx.h), one launch
+// macro per kernel family; they name conv_tensor_bias's locals.
 #define FP8A_TBSG(S_, M_) conv_tbsg_kernel<S_, M_><<<gb, 256, glds, s>>>(x, w, y, dg, fq, fqb, fqi, bA, bW, bR, tp, gate, ep, act, act_lo, act_hi, emt)
-                if (Mw == 2) { if (sw == 1) FP8A_TBSG(1, 2); else FP8A_TBSG(2, 2); }
-                else { if (sw == 1) FP8A_TBSG(1, 3); else FP8A_TBSG(2, 3); }
-#undef FP8A_TBSG
-                if (fq.mx) bA = fqi;
-                rc = hip_check("fp8a_conv2d (tensor-bias groups, LDS-DMA staged table form)");
-                if (rc) return rc;
-            } else if (g_opt_tbs && !use_img && cig == 1 && kh == 3 && dh == 1 && plan_tbs(tb, sw, Bn * Cout, Cout, H, W, Ho, Wo,
-                                                                                  ph, pw, tlds)) {
-                const unsigned gb = (unsigned)(((tb.planes + tb.PB - 1) / tb.PB) * tb.nb);
 #define FP8A_TBS(S_, M_) conv_tbs_kernel<S_, M_><<<gb, 256, tlds, s>>>(x, w, y, tb, fq, fqb, fqi, bA, bW, bR, tp, gate, ep, act, act_lo, act_hi)
-                if (Mw == 2) { if (sw == 1) FP8A_TBS(1, 2); else FP8A_TBS(2, 2); }
-                else { if (sw == 1) FP8A_TBS(1, 3); else FP8A_TBS(2, 3); }
-#undef FP8A_TBS
-                if (fq.mx) bA = fqi;
-                rc = hip_check("fp8a_conv2d (tensor-bias groups, staged table form)");
-                if (rc) return rc;
-            } else {
+#define FP8A_TBX(S_, M_) do { \
+        if (rw2) conv_tbx_kernel<S_, M_, 2><<<gb, 256, 0, s>>>(aw, w, y, ta, bA, bW, bR, tp, gate, ep, act, act_lo, act_hi); \
+        else conv_tbx_kernel<S_, M_, 1><<<gb, 256, 0, s>>>(aw, w, y, ta, bA, bW, bR, tp, gate, ep, act, act_lo, act_hi); \
+    } while (0)
+#define FP8A_BY_STRIDE_MW(LAUNCH_) do { \
+        if (Mw == 2) { if (sw == 1) LAUNCH_(1, 2); else LAUNCH_(2, 2); } \
+        else { if (sw == 1) LAUNCH_(1, 3); else LAUNCH_(2, 3); } \
+    } while (0)
+
+// Single-output-channel groups of the v9 model: the tensor-bias semantics (approx_calculation.py:800-809) on
+// the table-form depthwise kernels, the general fast kernel, and the gated literal kernel behind them.
+static int conv_tensor_bias(ConvCall &c) {
+    const ConvShape &g = c.g;
+    const int64_t Bn = g.Bn, Cin = g.Cin, H = g.H, W = g.W, Cout = g.Cout, Ho = g.Ho, Wo = g.Wo, cig = g.cig;
+    const int kh = g.kh, kw = g.kw, sh = g.sh, sw = g.sw, ph = g.ph, pw = g.pw, dh = g.dh, dw = g.dw, groups = g.groups;
+    const int E = c.E, Mw = c.Mw, act = c.act;
+    const uint32_t flags = c.flags;
+    const float act_lo = c.act_lo, act_hi = c.act_hi, *w = c.w;
+    float *y = c.y, *fqb = c.fqb;
+    int32_t *fqi = c.fqi;
+    const int32_t *bW = c.bW, *bR = c.bR;
+    const float2 *ep = reinterpret_cast<const float2 *>(c.bn);
+    void *workspace = c.workspace;
+    const size_t workspace_bytes = c.workspace_bytes;
+    hipStream_t s = c.s;
+    const EmitW &em = c.em;
+    if (c.res || c.post_act || c.post_fq.mx)
+        return fail(FP8A_EINVAL, "no block-output epilogue for single-output-channel groups");
+    TablePack tp;
+    int mode;
+    int rc = pack_table(c.table, Mw, flags & F_APPROX, tp, mode);
+    if (rc) return rc;
+    const int64_t total = Bn * Cout * Ho * Wo;
+    uint32_t *gate = nullptr;
+    ArenaLease lease;  // (gate: a slot of the stream's flag arena, flag_arena)
+    bool emitted = false;  // (a requested word image: only the staged table-form kernel writes it)
+    // fast form: needs s2n on and golden_clip_OF off (else every launch would fall back)
+    const bool fast_ok = (flags & F_S2N) && !(flags & F_GCLIP) && workspace != nullptr &&
+                         workspace_bytes >= FLAG_BYTES && Cout <= 65535 && Bn <= 65535;
+    // E4M3 / E5M2 table form (conv_tbx.h): a table of xm_table_form, qbma, 3-wide kernel rows, stride 1 or 2
+    const int64_t nwg = (Wo + TBX_TW - 1) / TBX_TW, items = Bn * Cout * Ho * nwg;
+    const bool tbx_ok = fast_ok && !g_env.no_tbx && ((E == 4 && Mw == 3) || (E == 5 && Mw == 2)) &&
+                        xm_table_form(tp, Mw, nullptr) &&
+                        (flags & F_QBMA) && kw == 3 && dw == 1 && sh == sw && (sw == 1 || sw == 2) &&
+                        items < (1ll << 31) && Ho * Wo < (1ll << 31) &&
+                        workspace_bytes >= FLAG_BYTES + (size_t)(Bn * Cin * H * W) * 4;
+    if (c.fq.mx && !tbx_ok) {
+        rc = materialize_input(c);
+        if (rc) return rc;
+    }
+    const float *x = c.x;
+    const int32_t *bA = c.bA;
+    const FqIn fq = c.fq;
+    if (tbx_ok) {
+        if (!dw_lease(s, workspace, workspace_bytes, lease)) return lease_error();
+        gate = lease.mine;
+        // the input's table-form words from the producing launch (fp8a_conv2d_chain, next_form 1:
+        // header + [Bn][Cin][H][W] words of fq_in(x)); the pre-pass then runs gated on its header
+        const bool use_img = c.in_img != nullptr && fq.mx != nullptr;
+        uint32_t *aw = use_img ? const_cast<uint32_t *>(c.in_img) + 64 : (uint32_t *)((char *)workspace + FLAG_BYTES);
+        TbsArgs tb{};
+        size_t tlds = 0;
+        // tbs = 2 (default): the LDS-DMA-staged conv_tbsg_kernel
+        DwArgs dg{};
+        size_t glds = 0;
+        const bool staged = !use_img && cig == 1 && kh == 3 && dh == 1;
+        if (opt(OPT_TBS) == 2 && staged && plan_staged_dw(dg, g, sw, true, glds)) {
+            const unsigned gb = (unsigned)(((dg.planes + dg.PB - 1) / dg.PB) * dg.nb);
+            // (it emits the next matrix-core convolution's words when fp8a_conv2d_chain asked, em.form 0)
+            const EmitW emt = em.w && em.form == 0 ? em : EmitW{};
+            emitted = emt.w != nullptr;
+            FP8A_BY_STRIDE_MW(FP8A_TBSG);
+            if (fq.mx) bA = fqi;
+            rc = hip_check("fp8a_conv2d (tensor-bias groups, LDS-DMA staged table form)");
+            if (rc) return rc;
+        } else if (opt(OPT_TBS) && staged && plan_tbs(tb, sw, Bn * Cout, Cout, H, W, Ho, Wo, ph, pw, tlds)) {
+            const unsigned gb = (unsigned)(((tb.planes + tb.PB - 1) / tb.PB) * tb.nb);
+            FP8A_BY_STRIDE_MW(FP8A_TBS);
+            if (fq.mx) bA = fqi;
+            rc = hip_check("fp8a_conv2d (tensor-bias groups, staged table form)");
+            if (rc) return rc;
+        } else {
             const int64_t nx = Bn * Cin * H * W;
             tbx_decode_a<<<(unsigned)std::min<int64_t>((nx + 255) / 256, use_img ? 1024 : 8192), 256, 0, s>>>(
-                x, nx, aw, gate, fq, fqb, fqi, Mw, use_img ? in_img : nullptr);
+                x, nx, aw, gate, fq, fqb, fqi, Mw, use_img ? c.in_img : nullptr);
             if (fq.mx) bA = fqi;
-            TbxArgs ta;
-            ta.Cin = Cin; ta.H = H; ta.W = W; ta.Cout = Cout; ta.Ho = Ho; ta.Wo = Wo;
-            ta.kh = kh; ta.ph = ph; ta.pw = pw; ta.dh = dh; ta.cpg = (int)cig;
-            ta.nwg = (uint32_t)nwg;
-            const bool rw2 = g_opt_tbx_rw == 2 && dh == 1;
-            ta.items = (uint32_t)(rw2 ? Bn * Cout * ((Ho + 1) / 2) * nwg : items);
+            const bool rw2 = opt(OPT_TBX_RW) == 2 && dh == 1;
+            const TbxArgs ta = tbx_args(g, nwg, rw2 ? Bn * Cout * ((Ho + 1) / 2) * nwg : items);
             const unsigned gb = (unsigned)std::min<int64_t>((ta.items + 255) / 256, 8 * 1024);
-#define FP8A_TBX(SW_, M_, RW_) conv_tbx_kernel<SW_, M_, RW_><<<gb, 256, 0, s>>>(aw, w, y, ta, bA, bW, bR, tp, gate, ep, act, act_lo, act_hi)
-            if (Mw == 2) {
-                if (sw == 1) { if (rw2) FP8A_TBX(1, 2, 2); else FP8A_TBX(1, 2, 1); }
-                else { if (rw2) FP8A_TBX(2, 2, 2); else FP8A_TBX(2, 2, 1); }
-            } else {
-                if (sw == 1) { if (rw2) FP8A_TBX(1, 3, 2); else FP8A_TBX(1, 3, 1); }
-                else { if (rw2) FP8A_TBX(2, 3, 2); else FP8A_TBX(2, 3, 1); }
-            }
-#undef FP8A_TBX
+            FP8A_BY_STRIDE_MW(FP8A_TBX);
             rc = hip_check("fp8a_conv2d (tensor-bias groups, E4M3 / E5M2 table form)");
             if (rc) return rc;
-            }
-        } else if (fast_ok) {
-            if (!dw_lease(s, workspace, workspace_bytes, lease)) return lease_error();
-            gate = lease.mine;
-            dim3 grid((unsigned)((Ho * Wo + 255) / 256), (unsigned)Cout, (unsigned)Bn);
-            conv_tb_fast_kernel<<<grid, 256, 0, s>>>(x, w, y, Cin, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, groups,
-                                                     Ho, Wo, Mw, bA, bW, bR, tp, flags | F_TB, gate, ep, act, act_lo,
-                                                     act_hi);
-            rc = hip_check("fp8a_conv2d (tensor-bias groups, fast)");
-            if (rc) return rc;
         }
-        // (gated: at most 1024 blocks -- a no-op launch unless the fast kernel flagged)
-        const unsigned eb = (unsigned)(fast_ok ? std::min<int64_t>((total + 255) / 256, 1024) : (total + 255) / 256);
-        if (fast_ok) {  // gated, grid-capped: a no-op launch unless the fast kernel flagged
-            conv_tb_direct_kernel<true><<<std::max(eb, clear_blocks(lease)), 256, 0, s>>>(
-                x, w, y, Bn, Cin, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, groups, Ho, Wo, E, Mw, bA, bW, bR, tp,
-                flags | F_TB, gate, (uint32_t *)workspace, lease.clr, lease.clr16, ep, act, act_lo, act_hi, fq);
-        } else {
-            conv_tb_direct_kernel<true><<<eb, 256, 0, s>>>(x, w, y, Bn, Cin, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw,
-                                                     groups, Ho, Wo, E, Mw, bA, bW, bR, tp, flags | F_TB, nullptr,
-                                                     nullptr, nullptr, 0u, ep, act, act_lo, act_hi, FqIn{});
-        }
-        if (em.w && !emitted && dev_fill(em.invalid, 1, sizeof(uint32_t), s) != hipSuccess)  // (no emission here)
-            return hip_check("fp8a word image header");
-        return hip_check("fp8a_conv2d (tensor-bias groups)");
-    }
-    // (a workspace below fp8a_conv2d_workspace_size but holding the flag word runs unsplit)
-    if (workspace == nullptr || workspace_bytes < FLAG_BYTES) return fail(FP8A_EINVAL, "conv2d workspace too small");
-    if (Kg >= (1ll << 31)) return fail(FP8A_EINVAL, "conv2d window too large");
-    (void)Ktot;
-    if (fq.mx) {  // fuse into the matrix-core pre-decode only where run_gemm will take that path
-        TablePack tp;
-        int mode;
-        rc = pack_table(table, Mw, (flags & (F_APPROX | F_V5)) != 0, tp, mode);
+    } else if (fast_ok) {
+        if (!dw_lease(s, workspace, workspace_bytes, lease)) return lease_error();
+        gate = lease.mine;
+        dim3 grid((unsigned)((Ho * Wo + 255) / 256), (unsigned)Cout, (unsigned)Bn);
+        conv_tb_fast_kernel<<<grid, 256, 0, s>>>(x, w, y, Cin, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, groups,
+                                                 Ho, Wo, Mw, bA, bW, bR, tp, flags | F_TB, gate, ep, act, act_lo,
+                                                 act_hi);
+        rc = hip_check("fp8a_conv2d (tensor-bias groups, fast)");
         if (rc) return rc;
-        if (flags & F_V5) mode = TM_V5;  // (as run_gemm)
-        const WordImage wi = word_image(H, W, ph, pw);
-        const int64_t a_words = Bn * cig * wi.H * wi.W;  // as xm_a_words / run_gemm
-        const int64_t kpad = (Kg + BK - 1) / BK * BK, npad = (cog + BN - 1) / BN * BN;
-        // (run_gemm's matrix-core forms: every one applies fq in its A pre-decode, xm_decode_a)
-        const uint32_t gf = flags & ~F_TB;
-        const bool form = f8_form(E, Mw, gf, tp) || tt_form(Mw, gf, tp) || v5mx_form(Mw, gf, mode);
-        const bool fused = form && !no_mx() && a_words < (1ll << 30) &&
-                           kpad * npad * 4 < (1ll << 32) &&
-                           workspace_bytes >= gemm_workspace_bytes(Mrows, cog, Kg, a_words);
-        if (!fused) {
-            rc = materialize();
-            if (rc) return rc;
-        }
     }
-    // v5 depthwise: one direct launch (a GEMM per single-column group would be `groups` launches of
-    // N = 1 tiles: MobileNetV2 E5M2 v5 ran at ~500 images/s that way)
-    if ((flags & F_V5) && cog == 1 && !post && groups > 1) {
-        TablePack tp;
-        int mode;
-        rc = pack_table(table, Mw, true, tp, mode);
+    // (gated: at most 1024 blocks -- a no-op launch unless the fast kernel flagged)
+    const unsigned eb = (unsigned)(fast_ok ? std::min<int64_t>((total + 255) / 256, 1024) : (total + 255) / 256);
+    if (fast_ok) {  // gated, grid-capped: a no-op launch unless the fast kernel flagged
+        conv_tb_direct_kernel<true><<<std::max(eb, clear_blocks(lease)), 256, 0, s>>>(
+            x, w, y, Bn, Cin, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, groups, Ho, Wo, E, Mw, bA, bW, bR, tp,
+            flags | F_TB, gate, (uint32_t *)workspace, lease.clr, lease.clr16, ep, act, act_lo, act_hi, fq);
+    } else {
+        conv_tb_direct_kernel<true><<<eb, 256, 0, s>>>(x, w, y, Bn, Cin, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw,
+                                                 groups, Ho, Wo, E, Mw, bA, bW, bR, tp, flags | F_TB, nullptr,
+                                                 nullptr, nullptr, 0u, ep, act, act_lo, act_hi, FqIn{});
+    }
+    if (em.w && !emitted && (rc = invalidate_image(em, s))) return rc;  // (no emission here)
+    return hip_check("fp8a_conv2d (tensor-bias groups)");
+}
+
+// v5 depthwise: one direct launch (a GEMM per single-column group would be `groups` launches of N = 1
+// tiles: MobileNetV2 E5M2 v5 ran at ~500 images/s that way) -- the staged kernel, the word form, or
+// the literal kernel alone.
+static int conv_v5_depthwise(ConvCall &c) {
+    const ConvShape &g = c.g;
+    const int64_t Bn = g.Bn, Cin = g.Cin, H = g.H, W = g.W, Cout = g.Cout, Ho = g.Ho, Wo = g.Wo, cig = g.cig;
+    const int kh = g.kh, kw = g.kw, sh = g.sh, sw = g.sw, ph = g.ph, pw = g.pw, dh = g.dh, dw = g.dw, groups = g.groups;
+    const int E = c.E, Mw = c.Mw, act = c.act;
+    const uint32_t flags = c.flags;
+    const float act_lo = c.act_lo, act_hi = c.act_hi, *x = c.x, *w = c.w;
+    float *y = c.y, *fqb = c.fqb;
+    int32_t *fqi = c.fqi;
+    const int32_t *bA = c.bA, *bW = c.bW, *bR = c.bR;
+    const float2 *ep = reinterpret_cast<const float2 *>(c.bn);
+    void *workspace = c.workspace;
+    const size_t workspace_bytes = c.workspace_bytes;
+    hipStream_t s = c.s;
+    const FqIn fq = c.fq;
+    const EmitW &em = c.em;
+    TablePack tp;
+    int mode;
+    int rc = pack_table(c.table, Mw, true, tp, mode);
+    if (rc) return rc;
+    const int64_t total = Bn * Cout * Ho * Wo;
+    // the word form (conv_v5dw_kernel, conv_tbx.h): E5M2 with the adder wrap, depthwise 3-wide
+    // rows, stride 1 / 2; the literal kernel behind it runs only if its gate is raised
+    const int64_t nx = Bn * Cin * H * W, nwg = (Wo + TBX_TW - 1) / TBX_TW, items = Bn * Cout * Ho * nwg;
+    const size_t awb = align256((size_t)nx * 4);
+    const bool v5dw_ok = !g_env.no_v5dw && Mw == 2 && (flags & F_OFUF) && cig == 1 && kw == 3 && kh <= 5 && dw == 1 &&
+                         sh == sw && (sw == 1 || sw == 2) && items < (1ll << 31) && Ho * Wo < (1ll << 31) &&
+                         workspace != nullptr && workspace_bytes >= FLAG_BYTES + awb + (size_t)(Cout * kh * kw) * 8;
+    uint32_t *gate = nullptr;
+    ArenaLease lease;  // (gate: a slot of the stream's flag arena, flag_arena)
+    // the staged form (conv_v5ds_kernel: both pre-passes fused): depthwise 3 x 3, dilation 1
+    DwArgs d{};
+    size_t lds = 0;
+    if (v5dw_ok && opt(OPT_V5DS) && kh == 3 && kw == 3 && dh == 1 && plan_staged_dw(d, g, sh, false, lds)) {
+        if (!dw_lease(s, workspace, workspace_bytes, lease)) return lease_error();
+        gate = lease.mine;
+        const unsigned gb = (unsigned)(((d.planes + d.PB - 1) / d.PB) * d.nb);
+        // (it emits the next convolution's v5 words when fp8a_conv2d_chain asked for them, em.form 2)
+        const EmitW emv = em.w && em.form == 2 ? em : EmitW{};
+        if (sh == 1)
+            conv_v5ds_kernel<1><<<gb, 256, lds, s>>>(x, w, y, d, fq, fqb, fqi, bA, bW, bR, tp, flags, E, gate, ep,
+                                                     act, act_lo, act_hi, emv);
+        else
+            conv_v5ds_kernel<2><<<gb, 256, lds, s>>>(x, w, y, d, fq, fqb, fqi, bA, bW, bR, tp, flags, E, gate, ep,
+                                                     act, act_lo, act_hi, emv);
+        rc = hip_check("fp8a_conv2d (v5 depthwise, staged)");
         if (rc) return rc;
-        const int64_t total = Bn * Cout * Ho * Wo;
-        // the word form (conv_v5dw_kernel, conv_tbx.h): E5M2 with the adder wrap, depthwise 3-wide
-        // rows, stride 1 / 2; the literal kernel behind it runs only if its gate is raised
-        const int64_t nx = Bn * Cin * H * W, nwg = (Wo + TBX_TW - 1) / TBX_TW, items = Bn * Cout * Ho * nwg;
-        const size_t awb = align256((size_t)nx * 4);
-        static const bool no_v5dw = getenv("FP8A_NO_V5DW") != nullptr;
-        const bool v5dw_ok = !no_v5dw && Mw == 2 && (flags & F_OFUF) && cig == 1 && kw == 3 && kh <= 5 && dw == 1 &&
-                             sh == sw && (sw == 1 || sw == 2) && items < (1ll << 31) && Ho * Wo < (1ll << 31) &&
-                             workspace != nullptr && workspace_bytes >= FLAG_BYTES + awb + (size_t)(Cout * kh * kw) * 8;
-        uint32_t *gate = nullptr;
-        ArenaLease lease;  // (gate: a slot of the stream's flag arena, flag_arena)
-        // the staged form (conv_v5ds_kernel: both pre-passes fused): depthwise 3 x 3, dilation 1
-        DwArgs d{};
-        size_t lds = 0;
-        const bool v5ds = v5dw_ok && g_opt_v5ds && kh == 3 && kw == 3 && dh == 1 && H < (1 << 20) && W < (1 << 20) &&
-                          Cout < (1 << 20) && H * W < (1ll << 22) && [&]() {
-                              d.planes = Bn * Cout; d.C = (int)Cout; d.H = (int)H; d.W = (int)W;
-                              d.Ho = (int)Ho; d.Wo = (int)Wo; d.ph = ph; d.pw = pw; d.nx = nx;
-                              if (!plan_dw3(d, sh, lds, true)) return false;
-                              lds = (size_t)d.nimg * 4 + (size_t)d.PB * 9 * 8;  // (tap words: 8 B)
-                              return lds <= 65536;
-                          }();
-        if (v5ds) {
-            if (!dw_lease(s, workspace, workspace_bytes, lease)) return lease_error();
-            gate = lease.mine;
-            const unsigned g = (unsigned)(((d.planes + d.PB - 1) / d.PB) * d.nb);
-            // (it emits the next convolution's v5 words when fp8a_conv2d_chain asked for them, em.form 2)
-            const EmitW emv = em.w && em.form == 2 ? em : EmitW{};
-            if (sh == 1)
-                conv_v5ds_kernel<1><<<g, 256, lds, s>>>(x, w, y, d, fq, fqb, fqi, bA, bW, bR, tp, flags, E, gate, ep,
-                                                        act, act_lo, act_hi, emv);
-            else
-                conv_v5ds_kernel<2><<<g, 256, lds, s>>>(x, w, y, d, fq, fqb, fqi, bA, bW, bR, tp, flags, E, gate, ep,
-                                                        act, act_lo, act_hi, emv);
-            rc = hip_check("fp8a_conv2d (v5 depthwise, staged)");
-            if (rc) return rc;
-            if (fq.mx) bA = fqi;
-            ++g_paths[PATH_FAST];
-        } else if (v5dw_ok) {
-            if (em.w && dev_fill(em.invalid, 1, sizeof(uint32_t), s) != hipSuccess)  // (no emission here)
-                return hip_check("fp8a word image header");
-            if (!dw_lease(s, workspace, workspace_bytes, lease)) return lease_error();
-            gate = lease.mine;
-            uint32_t *aw = (uint32_t *)((char *)workspace + FLAG_BYTES);
-            uint2 *bwd = (uint2 *)((char *)workspace + FLAG_BYTES + awb);
-            // (the input quantizer applied here, its bias written for the kernels after: bA = fqi)
-            v5dw_decode_a<<<(unsigned)std::min<int64_t>((nx + 255) / 256, 8192), 256, 0, s>>>(x, nx, aw, E, Mw, bA, fq,
-                                                                                               fqb, fqi);
-            if (fq.mx) bA = fqi;
-            const int64_t nb = Cout * kh * kw;
-            v5dw_decode_b<<<(unsigned)std::min<int64_t>((nb + 255) / 256, 1024), 256, 0, s>>>(w, nb, kh * kw, bwd, E, Mw,
-                                                                                               bA, bW, bR, tp);
-            TbxArgs ta;
-            ta.Cin = Cin; ta.H = H; ta.W = W; ta.Cout = Cout; ta.Ho = Ho; ta.Wo = Wo;
-            ta.kh = kh; ta.ph = ph; ta.pw = pw; ta.dh = dh; ta.cpg = 1;
-            ta.nwg = (uint32_t)nwg;
-            ta.items = (uint32_t)items;
-            const unsigned gb = (unsigned)std::min<int64_t>((items + 255) / 256, 8 * 1024);
-            if (sw == 1)
-                conv_v5dw_kernel<1><<<gb, 256, 0, s>>>(aw, bwd, y, ta, bR, flags, E, gate, ep, act, act_lo, act_hi);
-            else
-                conv_v5dw_kernel<2><<<gb, 256, 0, s>>>(aw, bwd, y, ta, bR, flags, E, gate, ep, act, act_lo, act_hi);
-            rc = hip_check("fp8a_conv2d (v5 depthwise, word form)");
-            if (rc) return rc;
-            ++g_paths[PATH_FAST];
-        } else {
-            ++g_paths[PATH_EXACT];
-            if (em.w && dev_fill(em.invalid, 1, sizeof(uint32_t), s) != hipSuccess)  // (no emission here)
-                return hip_check("fp8a word image header");
-            if (fq.mx) {
-                fq_bias_kernel<<<1, 1, 0, s>>>(fq, fqb, fqi);
-                bA = fqi;
-            }
-        }
-        // (x unquantized when fq is set: the literal kernel applies fq to every loaded value)
-        conv_tb_direct_kernel<false><<<std::max((unsigned)std::min<int64_t>((total + 255) / 256, 16384),
-                                                clear_blocks(lease)), 256, 0, s>>>(
-            x, w, y, Bn, Cin, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, groups, Ho, Wo, E, Mw, bA, bW, bR, tp, flags,
-            gate, gate ? (uint32_t *)workspace : nullptr, lease.clr, lease.clr16, ep, act, act_lo, act_hi, fq);
-        return hip_check("fp8a_conv2d (v5 depthwise, direct)");
-    }
-    for (int g = 0; g < groups; ++g) {
-        GemmArgs a = make_args(nullptr, 0, w + g * cog * Kg, 1, Kg, y, 0, Mrows, cog, Kg, E, Mw, bA, bW + g * cog, 1,
-                               bR, flags & ~F_TB);
-        a.nchw = 1;
-        a.hw = Ho * Wo;
-        a.ctot = Cout;
-        a.coff = g * cog;
-        a.conv = 1;
-        a.X = x;
-        a.Cin = Cin; a.H = H; a.W = W; a.Ho = Ho; a.Wo = Wo; a.cbase = g * cig; a.aw_c = cig;
-        a.kh = kh; a.kw = kw; a.sh = sh; a.sw = sw; a.ph = ph; a.pw = pw; a.dh = dh; a.dw = dw;
-        fastdiv_params((uint32_t)(kh * kw), a.kk_mul, a.kk_shift);
-        fastdiv_params((uint32_t)kw, a.kw_mul, a.kw_shift);
-        a.ep = ep; a.ep_act = act; a.ep_lo = act_lo; a.ep_hi = act_hi;
+        if (fq.mx) bA = fqi;
+        ++g_paths[PATH_FAST];
+    } else if (v5dw_ok) {
+        if (em.w && (rc = invalidate_image(em, s))) return rc;  // (no emission here)
+        if (!dw_lease(s, workspace, workspace_bytes, lease)) return lease_error();
+        gate = lease.mine;
+        uint32_t *aw = (uint32_t *)((char *)workspace + FLAG_BYTES);
+        uint2 *bwd = (uint2 *)((char *)workspace + FLAG_BYTES + awb);
+        // (the input quantizer applied here, its bias written for the kernels after: bA = fqi)
+        v5dw_decode_a<<<(unsigned)std::min<int64_t>((nx + 255) / 256, 8192), 256, 0, s>>>(x, nx, aw, E, Mw, bA, fq,
+                                                                                           fqb, fqi);
+        if (fq.mx) bA = fqi;
+        const int64_t nb = Cout * kh * kw;
+        v5dw_decode_b<<<(unsigned)std::min<int64_t>((nb + 255) / 256, 1024), 256, 0, s>>>(w, nb, kh * kw, bwd, E, Mw,
+                                                                                           bA, bW, bR, tp);
+        const TbxArgs ta = tbx_args(g, nwg, items);
+        const unsigned gb = (unsigned)std::min<int64_t>((items + 255) / 256, 8 * 1024);
+        if (sw == 1)
+            conv_v5dw_kernel<1><<<gb, 256, 0, s>>>(aw, bwd, y, ta, bR, flags, E, gate, ep, act, act_lo, act_hi);
+        else
+            conv_v5dw_kernel<2><<<gb, 256, 0, s>>>(aw, bwd, y, ta, bR, flags, E, gate, ep, act, act_lo, act_hi);
+        rc = hip_check("fp8a_conv2d (v5 depthwise, word form)");
+        if (rc) return rc;
+        ++g_paths[PATH_FAST];
+    } else {
+        ++g_paths[PATH_EXACT];
+        if (em.w && (rc = invalidate_image(em, s))) return rc;  // (no emission here)
         if (fq.mx) {
-            a.fqin = fq;
-            a.fq_bias = fqb;
-            a.fq_ibias = fqi;
-            a.bA = fqi;  // written by the A pre-decode before any kernel reads it
+            fq_bias_kernel<<<1, 1, 0, s>>>(fq, fqb, fqi);
+            bA = fqi;
         }
-        a.res = res; a.post_act = post_act; a.post_lo = post_lo; a.post_hi = post_hi; a.post_fq = post_fq;
-        a.post_bout = post_bout; a.post_ibout = post_ibout;
-        if (groups == 1) {  // (fp8a_conv2d_chain only asks for these on ungrouped convolutions)
-            a.in_img = in_img;
-            a.em = em;
+    }
+    // (x unquantized when fq is set: the literal kernel applies fq to every loaded value)
+    conv_tb_direct_kernel<false><<<std::max((unsigned)std::min<int64_t>((total + 255) / 256, 16384),
+                                            clear_blocks(lease)), 256, 0, s>>>(
+        x, w, y, Bn, Cin, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, groups, Ho, Wo, E, Mw, bA, bW, bR, tp, flags,
+        gate, gate ? (uint32_t *)workspace : nullptr, lease.clr, lease.clr16, ep, act, act_lo, act_hi, fq);
+    return hip_check("fp8a_conv2d (v5 depthwise, direct)");
+}
+
+// Every other convolution: one implicit GEMM (run_gemm) per group.
+static int conv_grouped_gemm(const ConvCall &c) {
+    const ConvShape &g = c.g;
+    for (int gi = 0; gi < g.groups; ++gi) {
+        GemmArgs a = make_args(nullptr, 0, c.w + gi * g.cog * g.Kg, 1, g.Kg, c.y, 0, g.Mrows, g.cog, g.Kg, c.E, c.Mw, c.bA,
+                               c.bW + gi * g.cog, 1, c.bR, c.flags & ~F_TB);
+        a.nchw = 1;
+        a.hw = g.Ho * g.Wo;
+        a.ctot = g.Cout;
+        a.coff = gi * g.cog;
+        a.conv = 1;
+        a.X = c.x;
+        a.Cin = g.Cin; a.H = g.H; a.W = g.W; a.Ho = g.Ho; a.Wo = g.Wo; a.cbase = gi * g.cig; a.aw_c = g.cig;
+        a.kh = g.kh; a.kw = g.kw; a.sh = g.sh; a.sw = g.sw; a.ph = g.ph; a.pw = g.pw; a.dh = g.dh; a.dw = g.dw;
+        fastdiv_params((uint32_t)(g.kh * g.kw), a.kk_mul, a.kk_shift);
+        fastdiv_params((uint32_t)g.kw, a.kw_mul, a.kw_shift);
+        a.ep = reinterpret_cast<const float2 *>(c.bn); a.ep_act = c.act; a.ep_lo = c.act_lo; a.ep_hi = c.act_hi;
+        if (c.fq.mx) {
+            a.fqin = c.fq;
+            a.fq_bias = c.fqb;
+            a.fq_ibias = c.fqi;
+            a.bA = c.fqi;  // written by the A pre-decode before any kernel reads it
         }
-        rc = run_gemm(a, table, workspace, workspace_bytes, s);
+        a.res = c.res; a.post_act = c.post_act; a.post_lo = c.post_lo; a.post_hi = c.post_hi; a.post_fq = c.post_fq;
+        a.post_bout = c.post_bout; a.post_ibout = c.post_ibout;
+        if (g.groups == 1) {  // (fp8a_conv2d_chain only asks for these on ungrouped convolutions)
+            a.in_img = c.in_img;
+            a.em = c.em;
+        }
+        const int rc = run_gemm(a, c.table, c.workspace, c.workspace_bytes, c.s);
         if (rc) return rc;
     }
     return FP8A_OK;
+}
+
+// The common prologue of every convolution entry point, then one of the three dispatchers above.
+static int conv2d_impl(const ConvCall &call) {
+    ConvCall c = call;  // (materialize_input and the word-image checks rewrite x, bA, fq and em)
+    ConvShape &g = c.g;
+    if (c.bn && (((uintptr_t)c.bn) & 7) != 0) return fail(FP8A_EINVAL, "bn parameters must be 8-byte aligned");
+    int rc = check_format(c.E, c.Mw);
+    if (!rc) rc = conv_shape(g);
+    if (rc) return rc;
+    if (g.Mrows == 0) {  // (the output quantizer's bias is still set, as its forward would)
+        if (c.post_bout) fq_bias_kernel<<<1, 1, 0, c.s>>>(c.post_fq, c.post_bout, c.post_ibout);
+        return c.post_bout ? hip_check("fp8a output-quantizer bias") : FP8A_OK;
+    }
+    const bool post = c.res || c.post_act || c.post_fq.mx;
+    const bool v5_depthwise = (c.flags & F_V5) && g.cog == 1 && !post && g.groups > 1;
+    // v5 words (form 2) come from the staged v5 depthwise kernel only: any other launch flags them invalid
+    if (c.em.w && (c.em.form == 2) != v5_depthwise) {
+        if ((rc = invalidate_image(c.em, c.s))) return rc;
+        c.em = EmitW{};
+    }
+    if (c.res && (c.res == c.y || (((uintptr_t)c.res) & 15) != 0))
+        return fail(FP8A_EINVAL, "the residual must be a 16-byte aligned tensor other than the output");
+    // v5 never had tensor-bias semantics: its single-output-channel groups take the paths below
+    if (g.cog == 1 && !(c.flags & F_V5)) return conv_tensor_bias(c);
+    // (a workspace below fp8a_conv2d_workspace_size but holding the flag word runs unsplit)
+    if (c.workspace == nullptr || c.workspace_bytes < FLAG_BYTES)
+        return fail(FP8A_EINVAL, "conv2d workspace too small");
+    if (g.Kg >= (1ll << 31)) return fail(FP8A_EINVAL, "conv2d window too large");
+    if (c.fq.mx) {  // fuse into the matrix-core pre-decode only where run_gemm will take that path
+        TablePack tp;
+        int mode;
+        rc = pack_table(c.table, c.Mw, (c.flags & (F_APPROX | F_V5)) != 0, tp, mode);
+        if (rc) return rc;
+        if (c.flags & F_V5) mode = TM_V5;  // (as run_gemm)
+        const WordImage wi = word_image(g.H, g.W, g.ph, g.pw);
+        const int64_t a_words = g.Bn * g.cig * wi.H * wi.W;  // as xm_a_words / run_gemm
+        const MxPlan mx = mx_plan(c.E, c.Mw, c.flags & ~F_TB, tp, mode, g.cog, g.Kg, a_words);
+        // every matrix-core form applies fq in its A pre-decode (xm_decode_a), so the convolution fuses for all
+        // three; the workspace test is the conservative one (the whole size query), where run_gemm's is exact
+        const bool fused = mx.any() && mx.fits32 &&
+                           c.workspace_bytes >= gemm_workspace_bytes(g.Mrows, g.cog, g.Kg, a_words);
+        if (!fused) {
+            rc = materialize_input(c);
+            if (rc) return rc;
+        }
+    }
+    return v5_depthwise ? conv_v5_depthwise(c) : conv_grouped_gemm(c);
+}
+
+// The fields every convolution entry point has, in the public argument order.
+static ConvCall conv_call(const float *x, const float *w, float *y, const ConvShape &g, int E, int Mw, const int32_t *bA,
+                          const int32_t *bW, const int32_t *bR, const int32_t *table, uint32_t flags, const float *bn,
+                          int act, float act_lo, float act_hi, void *workspace, size_t workspace_bytes,
+                          fp8a_stream_t stream) {
+    ConvCall c{};
+    c.g = g;
+    c.x = x; c.w = w; c.y = y; c.E = E; c.Mw = Mw; c.bA = bA; c.bW = bW; c.bR = bR; c.table = table; c.flags = flags;
+    c.bn = bn; c.act = act; c.act_lo = act_lo; c.act_hi = act_hi;
+    c.workspace = workspace; c.workspace_bytes = workspace_bytes; c.s = (hipStream_t)stream;
+    return c;
 }
 
 int fp8a_conv2d_bn_act(const float *x, const float *w, float *y, int64_t Bn, int64_t Cin, int64_t H, int64_t W,
@@ -2458,9 +2505,8 @@ int fp8a_conv2d_bn_act(const float *x, const float *w, float *y, int64_t Bn, int
                        int E, int Mw, const int32_t *bA, const int32_t *bW, const int32_t *bR, const int32_t *table,
                        uint32_t flags, const float *bn, int act, float act_lo, float act_hi, void *workspace,
                        size_t workspace_bytes, fp8a_stream_t stream) {
-    return conv2d_impl(x, w, y, Bn, Cin, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, groups, E, Mw, bA, bW, bR, table,
-                       flags, bn, act, act_lo, act_hi, workspace, workspace_bytes, (hipStream_t)stream, FqIn{}, nullptr,
-                       nullptr, nullptr);
+    return conv2d_impl(conv_call(x, w, y, ConvShape{Bn, Cin, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, groups}, E, Mw, bA,
+                                 bW, bR, table, flags, bn, act, act_lo, act_hi, workspace, workspace_bytes, stream));
 }
 
 size_t fp8a_conv2d_qin_workspace_size(int64_t Bn, int64_t Cin, int64_t H, int64_t W, int64_t Cout, int kh, int kw,
@@ -2476,59 +2522,19 @@ int fp8a_conv2d_qin(const float *x, const float *w, float *y, int64_t Bn, int64_
                     int in_mbits, int in_sign_bits, float *in_bias_out, int32_t *in_ibias_out, void *workspace,
                     size_t workspace_bytes, fp8a_stream_t stream) {
     if (!in_maxval || !in_bias_out || !in_ibias_out) return fail(FP8A_EINVAL, "null pointer");
-    const int qE = in_nbits - in_sign_bits - in_mbits;
-    if (in_mbits < 1 || qE < 1) return fail(FP8A_EFORMAT, "bad FP8 quantizer format");
-    const size_t xq_bytes = align256((size_t)(Bn * Cin * H * W) * sizeof(float));
-    if (workspace == nullptr || workspace_bytes < FLAG_BYTES + xq_bytes)
-        return fail(FP8A_EINVAL, "conv2d_qin workspace too small");
-    // the fake-quant buffer of the non-fused paths sits at the workspace's end
-    const size_t rest = (workspace_bytes - xq_bytes) & ~(size_t)255;
-    float *xq = (float *)((char *)workspace + rest);
-    return conv2d_impl(x, w, y, Bn, Cin, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, groups, E, Mw, nullptr, bW, bR,
-                       table, flags, bn, act, act_lo, act_hi, workspace, rest, (hipStream_t)stream,
-                       FqIn{in_maxval, qE, in_mbits, in_sign_bits}, in_bias_out, in_ibias_out, xq);
+    ConvCall c = conv_call(x, w, y, ConvShape{Bn, Cin, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, groups}, E, Mw, nullptr,
+                           bW, bR, table, flags, bn, act, act_lo, act_hi, workspace, workspace_bytes, stream);
+    int rc = fused_quantizer(in_maxval, in_nbits, in_mbits, in_sign_bits, in_bias_out, in_ibias_out, c.fq);
+    if (!rc) rc = carve_xq(workspace, workspace_bytes, Bn * Cin * H * W, "conv2d_qin", c.workspace_bytes, c.xq);
+    if (rc) return rc;
+    c.fqb = in_bias_out;
+    c.fqi = in_ibias_out;
+    return conv2d_impl(c);
 }
-
 
 size_t fp8a_conv2d_block_workspace_size(int64_t Bn, int64_t Cin, int64_t H, int64_t W, int64_t Cout, int kh,
                                         int kw, int sh, int sw, int ph, int pw, int dh, int dw, int groups) {
     return fp8a_conv2d_qin_workspace_size(Bn, Cin, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, groups);
-}
-
-int fp8a_conv2d_block(const float *x, const float *w, float *y, int64_t Bn, int64_t Cin, int64_t H, int64_t W,
-                      int64_t Cout, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw, int groups, int E,
-                      int Mw, const int32_t *bA, const int32_t *bW, const int32_t *bR, const int32_t *table,
-                      uint32_t flags, const float *bn, int act, float act_lo, float act_hi, const float *in_maxval,
-                      int in_nbits, int in_mbits, int in_sign_bits, float *in_bias_out, int32_t *in_ibias_out,
-                      const float *res, int post_act, float post_lo, float post_hi, const float *out_maxval,
-                      int out_nbits, int out_mbits, int out_sign_bits, float *out_bias_out, int32_t *out_ibias_out,
-                      void *workspace, size_t workspace_bytes, fp8a_stream_t stream) {
-    hipStream_t s = (hipStream_t)stream;
-    if (post_act != 0 && post_act != 1) return fail(FP8A_EINVAL, "conv2d_block: post_act is 0 or 1");
-    FqIn fin{}, fout{};
-    if (in_maxval) {
-        const int qE = in_nbits - in_sign_bits - in_mbits;
-        if (in_mbits < 1 || qE < 1) return fail(FP8A_EFORMAT, "bad FP8 quantizer format");
-        if (!in_bias_out || !in_ibias_out) return fail(FP8A_EINVAL, "null pointer");
-        fin = FqIn{in_maxval, qE, in_mbits, in_sign_bits};
-    } else if (!bA) {
-        return fail(FP8A_EINVAL, "null pointer");
-    }
-    if (out_maxval) {
-        const int qE = out_nbits - out_sign_bits - out_mbits;
-        if (out_mbits < 1 || qE < 1) return fail(FP8A_EFORMAT, "bad FP8 quantizer format");
-        if (!out_bias_out || !out_ibias_out) return fail(FP8A_EINVAL, "null pointer");
-        fout = FqIn{out_maxval, qE, out_mbits, out_sign_bits};  // (its bias: written by the launch's gated exact kernel)
-    }
-    const size_t xq_bytes = fin.mx ? align256((size_t)(Bn * Cin * H * W) * sizeof(float)) : 0;
-    if (workspace == nullptr || workspace_bytes < FLAG_BYTES + xq_bytes)
-        return fail(FP8A_EINVAL, "conv2d_block workspace too small");
-    const size_t rest = (workspace_bytes - xq_bytes) & ~(size_t)255;
-    float *xq = fin.mx ? (float *)((char *)workspace + rest) : nullptr;
-    return conv2d_impl(x, w, y, Bn, Cin, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, groups, E, Mw,
-                       fin.mx ? nullptr : bA, bW, bR, table, flags, bn, act, act_lo, act_hi, workspace, rest, s, fin,
-                       in_bias_out, in_ibias_out, xq, res, post_act, post_lo, post_hi, fout, nullptr, EmitW{},
-                       fout.mx ? out_bias_out : nullptr, fout.mx ? out_ibias_out : nullptr);
 }
 
 // ----------------------------------------------------------------------------- word-image chain
@@ -2587,25 +2593,114 @@ int fp8a_conv2d_wants_image(int64_t Cout, int kh, int kw, int ph, int pw, int gr
     if (groups > 1 && Cout == groups) {  // single-output-channel groups: the table form's words
         // opt-in (FP8A_CHAIN_TBX=1): measured on MobileNetV2 E4M3 the producers' emitting stores cost
         // 1.65 ms per forward for 0.85 ms of gated pre-passes saved (19708 -> 19036 images/s)
-        static const bool no_tbx = getenv("FP8A_NO_TBX") != nullptr;
-        static const bool chain_tbx = getenv("FP8A_CHAIN_TBX") != nullptr && atoi(getenv("FP8A_CHAIN_TBX")) != 0;
-        const bool tbx = chain_tbx && !no_tbx && ((E == 4 && Mw == 3) || (E == 5 && Mw == 2)) &&
+        const bool tbx = g_env.chain_tbx && !g_env.no_tbx && ((E == 4 && Mw == 3) || (E == 5 && Mw == 2)) &&
                          xm_table_form(tp, Mw, nullptr) && (flags & F_S2N) && (flags & F_QBMA) &&
                          !(flags & (F_GCLIP | F_V5)) && kw == 3 && dw == 1 && sh == sw && (sw == 1 || sw == 2);
         (void)kh; (void)dh;
         return tbx ? 2 : 0;
     }
-    if (groups != 1 || no_mx()) return 0;
+    // (the forms only: the shape-dependent part of run_gemm's decision -- offsets, workspace -- is not known here)
+    const MxPlan mx = mx_plan(E, Mw, flags & ~F_TB, tp, (flags & F_V5) ? TM_V5 : mode, Cout, 0, 0);
+    if (groups != 1 || !mx.on) return 0;
     // the v5 matrix-core form (gemm_v5mx_kernel): its words (v5_word_a) when unpadded (an image's
     // border holds the E4M3 / E5M2 form's zero word, fp8a_word_image_init); emitted by the staged
     // v5 depthwise kernel only (conv_v5ds_kernel) -- every other producer flags the image invalid
-    if (flags & F_V5) return (v5mx_form(Mw, flags, TM_V5) && ph == 0 && pw == 0) ? 3 : 0;
-    if (!f8_form(E, Mw, flags & ~F_TB, tp)) return 0;
+    if (flags & F_V5) return (mx.v5mx && ph == 0 && pw == 0) ? 3 : 0;
+    if (!mx.f8) return 0;
     if (kh == 1 && kw == 1 && ph == 0 && pw == 0) {  // xm_af32: fp32 staging up to af32_maxct column tiles
         const int64_t bnt = 16 * xm_ncg(Cout), ct = (Cout + bnt - 1) / bnt;
         if (ct <= af32_maxct(sh, sw)) return 0;
     }
     return 1;
+}
+
+// fp8a_conv2d_chain's word-image arguments (fp8a_conv2d_block: none).
+struct ChainArgs {
+    void *in_image, *out_image;
+    int next_ph, next_pw;
+    const float *next_maxval;
+    int next_nbits, next_mbits, next_sign_bits;
+    const int32_t *next_bR;
+    int next_Mw, next_form;
+};
+
+// The header of the word image this launch may emit (valid with the next quantizer's constants, or invalid
+// where it cannot emit) and the producers' EmitW.
+static int emit_setup(const ConvCall &c, const ChainArgs &n, EmitW &em) {
+    ConvShape g = c.g;
+    const bool shape_ok = conv_shape(g) == FP8A_OK;  // (a bad shape: conv2d_impl reports it)
+    const int qE = n.next_nbits - n.next_sign_bits - n.next_mbits;
+    if (!n.next_maxval || !n.next_bR || n.next_mbits < 1 || qE < 1 || !(n.next_Mw == 2 || n.next_Mw == 3) ||
+        n.next_ph < 0 || n.next_pw < 0)
+        return fail(FP8A_EINVAL, "bad next-convolution parameters for the word image");
+    if (n.next_form < 0 || n.next_form > 2) return fail(FP8A_EINVAL, "bad word image form");
+    // (the table form's words: the consumer's plain [Bn][C][Ho][Wo] layout, no border)
+    const WordImage wi = n.next_form == 1 ? word_image(g.Ho, g.Wo, 0, 0) : word_image(g.Ho, g.Wo, n.next_ph, n.next_pw);
+    // (form 2, v5 words: the staged v5 depthwise producer -- conv2d_impl flags the image invalid
+    // where that kernel does not run; form 0 / 1: ungrouped producers)
+    // (form 0 from a depthwise producer: the staged table-form kernel, round 6)
+    const bool dwp = g.groups > 1 && g.Cin == g.groups && g.Cout == g.groups;
+    const bool prod = n.next_form == 2 ? (c.flags & F_V5) && dwp
+                                       : g.groups == 1 || (n.next_form == 0 && dwp && !(c.flags & F_V5));
+    const bool can = prod && g.Cout > 1 && shape_ok && g.Bn * g.Cout * g.Ho * g.Wo < (1ll << 31) &&
+                     g.Bn * g.Cout * wi.H * wi.W < (1ll << 30);
+    if (!can)
+        return dev_fill(n.out_image, 1, sizeof(uint32_t), c.s) != hipSuccess ? hip_check("fp8a word image header") : FP8A_OK;
+    const FqIn next_fq{n.next_maxval, qE, n.next_mbits, n.next_sign_bits};
+    emit_prep_kernel<<<1, 1, 0, c.s>>>((uint32_t *)n.out_image, next_fq, n.next_bR);
+    em.w = (uint32_t *)n.out_image + 64;
+    em.invalid = (uint32_t *)n.out_image;
+    em.awH = (int)wi.H; em.awW = (int)wi.W; em.awph = wi.ph; em.awpw = wi.pw;
+    em.Wo = (int)g.Wo;
+    em.hw = (uint32_t)(g.Ho * g.Wo);
+    fastdiv_params(em.hw, em.hw_mul, em.hw_shift);
+    fastdiv_params((uint32_t)g.Wo, em.wo_mul, em.wo_shift);
+    em.fq = next_fq;
+    em.bR = n.next_bR;
+    em.Mw = n.next_Mw;
+    em.form = n.next_form;
+    return FP8A_OK;
+}
+
+// fp8a_conv2d_block and fp8a_conv2d_chain (name: the entry point's, for its messages): c holds the plain call,
+// the residual and the post clamp; the quantizers, the word images and the fake-quant buffer are added here.
+static int conv_block(const char *name, ConvCall c, const float *in_maxval, int in_nbits, int in_mbits,
+                      int in_sign_bits, float *in_bias_out, int32_t *in_ibias_out, const float *out_maxval, int out_nbits,
+                      int out_mbits, int out_sign_bits, float *out_bias_out, int32_t *out_ibias_out, const ChainArgs &n) {
+    if (c.post_act != 0 && c.post_act != 1) return fail(FP8A_EINVAL, std::string(name) + ": post_act is 0 or 1");
+    if ((n.in_image && ((uintptr_t)n.in_image & 255)) || (n.out_image && ((uintptr_t)n.out_image & 255)))
+        return fail(FP8A_EINVAL, "word images must be 256-byte aligned");
+    int rc = fused_quantizer(in_maxval, in_nbits, in_mbits, in_sign_bits, in_bias_out, in_ibias_out, c.fq);
+    if (rc) return rc;
+    if (!c.fq.mx && !c.bA) return fail(FP8A_EINVAL, "null pointer");
+    // (the output quantizer's bias: written by the launch's gated exact kernel)
+    rc = fused_quantizer(out_maxval, out_nbits, out_mbits, out_sign_bits, out_bias_out, out_ibias_out, c.post_fq);
+    if (!rc && n.out_image) rc = emit_setup(c, n, c.em);
+    if (!rc) rc = carve_xq(c.workspace, c.workspace_bytes, c.fq.mx ? c.g.Bn * c.g.Cin * c.g.H * c.g.W : -1, name,
+                           c.workspace_bytes, c.xq);
+    if (rc) return rc;
+    if (c.fq.mx) c.bA = nullptr;
+    c.fqb = in_bias_out;
+    c.fqi = in_ibias_out;
+    c.post_bout = c.post_fq.mx ? out_bias_out : nullptr;
+    c.post_ibout = c.post_fq.mx ? out_ibias_out : nullptr;
+    c.in_img = (const uint32_t *)n.in_image;
+    return conv2d_impl(c);
+}
+
+int fp8a_conv2d_block(const float *x, const float *w, float *y, int64_t Bn, int64_t Cin, int64_t H, int64_t W,
+                      int64_t Cout, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw, int groups, int E,
+                      int Mw, const int32_t *bA, const int32_t *bW, const int32_t *bR, const int32_t *table,
+                      uint32_t flags, const float *bn, int act, float act_lo, float act_hi, const float *in_maxval,
+                      int in_nbits, int in_mbits, int in_sign_bits, float *in_bias_out, int32_t *in_ibias_out,
+                      const float *res, int post_act, float post_lo, float post_hi, const float *out_maxval,
+                      int out_nbits, int out_mbits, int out_sign_bits, float *out_bias_out, int32_t *out_ibias_out,
+                      void *workspace, size_t workspace_bytes, fp8a_stream_t stream) {
+    ConvCall c = conv_call(x, w, y, ConvShape{Bn, Cin, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, groups}, E, Mw, bA, bW,
+                           bR, table, flags, bn, act, act_lo, act_hi, workspace, workspace_bytes, stream);
+    c.res = res; c.post_act = post_act; c.post_lo = post_lo; c.post_hi = post_hi;
+    return conv_block("conv2d_block", c, in_maxval, in_nbits, in_mbits, in_sign_bits, in_bias_out, in_ibias_out,
+                      out_maxval, out_nbits, out_mbits, out_sign_bits, out_bias_out, out_ibias_out, ChainArgs{});
 }
 
 int fp8a_conv2d_chain(const float *x, const float *w, float *y, int64_t Bn, int64_t Cin, int64_t H, int64_t W,
@@ -2618,72 +2713,13 @@ int fp8a_conv2d_chain(const float *x, const float *w, float *y, int64_t Bn, int6
                       void *in_image, void *out_image, int next_ph, int next_pw, const float *next_maxval,
                       int next_nbits, int next_mbits, int next_sign_bits, const int32_t *next_bR, int next_Mw,
                       int next_form, void *workspace, size_t workspace_bytes, fp8a_stream_t stream) {
-    if (post_act != 0 && post_act != 1) return fail(FP8A_EINVAL, "conv2d_chain: post_act is 0 or 1");
-    hipStream_t s = (hipStream_t)stream;
-    if ((in_image && ((uintptr_t)in_image & 255)) || (out_image && ((uintptr_t)out_image & 255)))
-        return fail(FP8A_EINVAL, "word images must be 256-byte aligned");
-    FqIn fin{}, fout{};
-    if (in_maxval) {
-        const int qE = in_nbits - in_sign_bits - in_mbits;
-        if (in_mbits < 1 || qE < 1) return fail(FP8A_EFORMAT, "bad FP8 quantizer format");
-        if (!in_bias_out || !in_ibias_out) return fail(FP8A_EINVAL, "null pointer");
-        fin = FqIn{in_maxval, qE, in_mbits, in_sign_bits};
-    } else if (!bA) {
-        return fail(FP8A_EINVAL, "null pointer");
-    }
-    if (out_maxval) {
-        const int qE = out_nbits - out_sign_bits - out_mbits;
-        if (out_mbits < 1 || qE < 1) return fail(FP8A_EFORMAT, "bad FP8 quantizer format");
-        if (!out_bias_out || !out_ibias_out) return fail(FP8A_EINVAL, "null pointer");
-        fout = FqIn{out_maxval, qE, out_mbits, out_sign_bits};  // (its bias: written by the launch's gated exact kernel)
-    }
-    EmitW em{};
-    if (out_image) {
-        const int64_t Ho = (H + 2 * ph - dh * (kh - 1) - 1) / sh + 1, Wo = (W + 2 * pw - dw * (kw - 1) - 1) / sw + 1;
-        const int qE = next_nbits - next_sign_bits - next_mbits;
-        if (!next_maxval || !next_bR || next_mbits < 1 || qE < 1 || !(next_Mw == 2 || next_Mw == 3) || next_ph < 0 ||
-            next_pw < 0)
-            return fail(FP8A_EINVAL, "bad next-convolution parameters for the word image");
-        if (next_form < 0 || next_form > 2) return fail(FP8A_EINVAL, "bad word image form");
-        // (the table form's words: the consumer's plain [Bn][C][Ho][Wo] layout, no border)
-        const WordImage wi = next_form == 1 ? word_image(Ho, Wo, 0, 0) : word_image(Ho, Wo, next_ph, next_pw);
-        // (form 2, v5 words: the staged v5 depthwise producer -- conv2d_impl flags the image invalid
-        // where that kernel does not run; form 0 / 1: ungrouped producers)
-        // (form 0 from a depthwise producer: the staged table-form kernel, round 6)
-        const bool dwp = groups > 1 && Cin == groups && Cout == groups;
-        const bool prod = next_form == 2 ? (flags & F_V5) && dwp
-                                         : groups == 1 || (next_form == 0 && dwp && !(flags & F_V5));
-        const bool can = prod && Cout > 1 && Ho > 0 && Wo > 0 && Bn * Cout * Ho * Wo < (1ll << 31) &&
-                         Bn * Cout * wi.H * wi.W < (1ll << 30);
-        // the header: valid (0) with the next quantizer's constants before this launch emits,
-        // invalid (nonzero) when it cannot emit
-        if (!can && dev_fill(out_image, 1, sizeof(uint32_t), s) != hipSuccess)
-            return hip_check("fp8a word image header");
-        if (can) {
-            emit_prep_kernel<<<1, 1, 0, s>>>((uint32_t *)out_image, FqIn{next_maxval, qE, next_mbits, next_sign_bits},
-                                             next_bR);
-            em.w = (uint32_t *)out_image + 64;
-            em.invalid = (uint32_t *)out_image;
-            em.awH = (int)wi.H; em.awW = (int)wi.W; em.awph = wi.ph; em.awpw = wi.pw;
-            em.Wo = (int)Wo;
-            em.hw = (uint32_t)(Ho * Wo);
-            fastdiv_params(em.hw, em.hw_mul, em.hw_shift);
-            fastdiv_params((uint32_t)Wo, em.wo_mul, em.wo_shift);
-            em.fq = FqIn{next_maxval, qE, next_mbits, next_sign_bits};
-            em.bR = next_bR;
-            em.Mw = next_Mw;
-            em.form = next_form;
-        }
-    }
-    const size_t xq_bytes = fin.mx ? align256((size_t)(Bn * Cin * H * W) * sizeof(float)) : 0;
-    if (workspace == nullptr || workspace_bytes < FLAG_BYTES + xq_bytes)
-        return fail(FP8A_EINVAL, "conv2d_chain workspace too small");
-    const size_t rest = (workspace_bytes - xq_bytes) & ~(size_t)255;
-    float *xq = fin.mx ? (float *)((char *)workspace + rest) : nullptr;
-    return conv2d_impl(x, w, y, Bn, Cin, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, groups, E, Mw,
-                       fin.mx ? nullptr : bA, bW, bR, table, flags, bn, act, act_lo, act_hi, workspace, rest, s, fin,
-                       in_bias_out, in_ibias_out, xq, res, post_act, post_lo, post_hi, fout,
-                       (const uint32_t *)in_image, em, fout.mx ? out_bias_out : nullptr, fout.mx ? out_ibias_out : nullptr);
+    ConvCall c = conv_call(x, w, y, ConvShape{Bn, Cin, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, groups}, E, Mw, bA, bW,
+                           bR, table, flags, bn, act, act_lo, act_hi, workspace, workspace_bytes, stream);
+    c.res = res; c.post_act = post_act; c.post_lo = post_lo; c.post_hi = post_hi;
+    return conv_block("conv2d_chain", c, in_maxval, in_nbits, in_mbits, in_sign_bits, in_bias_out, in_ibias_out,
+                      out_maxval, out_nbits, out_mbits, out_sign_bits, out_bias_out, out_ibias_out,
+                      ChainArgs{in_image, out_image, next_ph, next_pw, next_maxval, next_nbits, next_mbits,
+                                next_sign_bits, next_bR, next_Mw, next_form});
 }
 
 size_t fp8a_matmul_block_workspace_size(int64_t M, int64_t N, int64_t K) {
@@ -2710,26 +2746,17 @@ int fp8a_matmul_block(const float *A, int64_t lda, const float *B, int64_t sbk, 
     if (bn && (((uintptr_t)bn) & 7) != 0) return fail(FP8A_EINVAL, "bn parameters must be 8-byte aligned");
     if (res && (res == C || (((uintptr_t)res) & 15) != 0))
         return fail(FP8A_EINVAL, "the residual must be a 16-byte aligned tensor other than the output");
-    FqIn fin{}, fout{};
-    if (in_maxval) {
-        const int qE = in_nbits - in_sign_bits - in_mbits;
-        if (in_mbits < 1 || qE < 1) return fail(FP8A_EFORMAT, "bad FP8 quantizer format");
-        if (!in_bias_out || !in_ibias_out) return fail(FP8A_EINVAL, "null pointer");
-        if (lda != K) return fail(FP8A_EINVAL, "matmul_block: fused input quantization needs a dense A");
-        fin = FqIn{in_maxval, qE, in_mbits, in_sign_bits};
-    } else if (!bA) {
-        return fail(FP8A_EINVAL, "null pointer");
-    }
-    if (out_maxval) {
-        const int qE = out_nbits - out_sign_bits - out_mbits;
-        if (out_mbits < 1 || qE < 1) return fail(FP8A_EFORMAT, "bad FP8 quantizer format");
-        if (!out_bias_out || !out_ibias_out) return fail(FP8A_EINVAL, "null pointer");
-        fout = FqIn{out_maxval, qE, out_mbits, out_sign_bits};  // (its bias: written by the launch's gated exact kernel)
-    }
-    const size_t xq_bytes = fin.mx ? align256((size_t)(M * K) * sizeof(float)) : 0;
-    if (workspace == nullptr || workspace_bytes < FLAG_BYTES + xq_bytes)
-        return fail(FP8A_EINVAL, "matmul_block workspace too small");
-    const size_t rest = (workspace_bytes - xq_bytes) & ~(size_t)255;
+    FqIn fin, fout;
+    int rc = fused_quantizer(in_maxval, in_nbits, in_mbits, in_sign_bits, in_bias_out, in_ibias_out, fin);
+    if (rc) return rc;
+    if (fin.mx && lda != K) return fail(FP8A_EINVAL, "matmul_block: fused input quantization needs a dense A");
+    if (!fin.mx && !bA) return fail(FP8A_EINVAL, "null pointer");
+    // (the output quantizer's bias: written by the launch's gated exact kernel)
+    rc = fused_quantizer(out_maxval, out_nbits, out_mbits, out_sign_bits, out_bias_out, out_ibias_out, fout);
+    size_t rest = 0;
+    float *xq = nullptr;  // one fake-quant pass into the workspace's end where the quantizer is not fused
+    if (!rc) rc = carve_xq(workspace, workspace_bytes, fin.mx ? M * K : -1, "matmul_block", rest, xq);
+    if (rc) return rc;
     GemmArgs a = make_args(A, lda, B, sbk, sbn, C, ldc, M, N, K, E, Mw, fin.mx ? in_ibias_out : bA, bB, bB_stride, bR,
                            flags);
     a.ep = reinterpret_cast<const float2 *>(bn); a.ep_act = act; a.ep_lo = act_lo; a.ep_hi = act_hi;
@@ -2739,22 +2766,21 @@ int fp8a_matmul_block(const float *A, int64_t lda, const float *B, int64_t sbk, 
         a.post_ibout = out_ibias_out;
     }
     if (fin.mx && M > 0 && K > 0) {
-        // fuse into the matrix-core pre-decode only where run_gemm will take that path (as conv2d_impl)
+        // fuse into the matrix-core pre-decode only where run_gemm will take that path
         TablePack tp;
         int mode;
-        int rc = check_format(E, Mw);
+        rc = check_format(E, Mw);
+        if (!rc) rc = pack_table(table, Mw, (flags & F_APPROX) != 0, tp, mode);
         if (rc) return rc;
-        rc = pack_table(table, Mw, (flags & F_APPROX) != 0, tp, mode);
-        if (rc) return rc;
-        const int64_t kpad = (K + BK - 1) / BK * BK, npad = (N + BN - 1) / BN * BN, a_words = M * kpad;
-        const bool fused = f8_form(E, Mw, flags, tp) && !no_mx() && a_words < (1ll << 30) &&
-                           kpad * npad * 4 < (1ll << 32) && rest >= gemm_workspace_bytes(M, N, K, 0);
+        const MxPlan mx = mx_plan(E, Mw, flags, tp, mode, N, K, M * ((K + BK - 1) / BK * BK));
+        // the E4M3 / E5M2 form only (the linear layers' tile-table launches keep the separate fake-quant pass);
+        // the conservative workspace test, as conv2d_impl
+        const bool fused = mx.f8 && mx.on && mx.fits32 && rest >= gemm_workspace_bytes(M, N, K, 0);
         if (fused) {
             a.fqin = fin;
             a.fq_bias = in_bias_out;
             a.fq_ibias = in_ibias_out;  // written by the A pre-decode before any kernel reads it
-        } else {  // one fake-quant pass into the workspace's end, then the plain path on it
-            float *xq = (float *)((char *)workspace + rest);
+        } else {
             const int64_t nx = M * K;
             fp8_quantize_kernel<<<(unsigned)std::max<int64_t>(1, std::min<int64_t>((nx + 255) / 256, 65536)), 256, 0,
                                   s>>>(A, 1, nx, fin.mx, 0, fin.E, fin.M, fin.S, xq, in_bias_out, in_ibias_out);
@@ -2764,7 +2790,7 @@ int fp8a_matmul_block(const float *A, int64_t lda, const float *B, int64_t sbk, 
         }
     } else if (fin.mx) {  // empty product: the quantizer's bias is still set, as its forward would
         fq_bias_kernel<<<1, 1, 0, s>>>(fin, in_bias_out, in_ibias_out);
-        int rc = hip_check("fp8a input-quantizer bias");
+        rc = hip_check("fp8a input-quantizer bias");
         if (rc) return rc;
     }
     return run_gemm(a, table, workspace, rest, s);
@@ -2824,14 +2850,14 @@ int fp8a_conv2d_qamaa(const float *x, const float *w, float *y, int64_t Bn, int6
                       int64_t Cout, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw, int groups,
                       const float *maxval, int n_bits, int Mbits, int sign_bits, fp8a_stream_t stream) {
     hipStream_t s = (hipStream_t)stream;
-    if (groups <= 0 || Cout % groups != 0 || Cin % groups != 0) return fail(FP8A_EINVAL, "bad groups");
+    if (!groups_ok(groups, Cin, Cout)) return fail(FP8A_EINVAL, "bad groups");
     if (Cout / groups == 1)
         return fail(FP8A_EINVAL, "single-output-channel groups take the exact product in the reference "
                                  "(approx_calculation.py:810-811): not a qamaa launch");
-    const int64_t Ho = (H + 2 * ph - dh * (kh - 1) - 1) / sh + 1;
-    const int64_t Wo = (W + 2 * pw - dw * (kw - 1) - 1) / sw + 1;
-    if (Ho <= 0 || Wo <= 0) return fail(FP8A_EINVAL, "empty convolution output");
-    const int64_t cog = Cout / groups, cig = Cin / groups, Kg = cig * kh * kw, Mrows = Bn * Ho * Wo;
+    ConvShape c{Bn, Cin, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, groups};
+    const int rc0 = conv_shape(c);
+    if (rc0) return rc0;
+    const int64_t Ho = c.Ho, Wo = c.Wo, cog = c.cog, cig = c.cig, Kg = c.Kg, Mrows = c.Mrows;
     for (int g = 0; g < groups; ++g) {
         GemmArgs a = make_args(nullptr, 0, w + g * cog * Kg, 1, Kg, y, 0, Mrows, cog, Kg, 1, 1, nullptr, nullptr, 0,
                                nullptr, 0);
@@ -2898,7 +2924,7 @@ int fp8a_fp8_mse_search(const float *x, int64_t rows, int64_t inner, const float
     a.cand = static_cast<MseCand *>(workspace);
     a.part = reinterpret_cast<double *>(a.cand + (size_t)rows * n_cand * n_mbits);
     a.sse = sse;
-    launch_mse(a, g_opt_mse_group != 0, (hipStream_t)stream);
+    launch_mse(a, opt(OPT_MSE_GROUP) != 0, (hipStream_t)stream);
     return hip_check("fp8a_fp8_mse_search");
 }
 
@@ -2951,17 +2977,6 @@ int fp8a_bn_train(const float *x, float *y, int64_t N, int64_t C, int64_t inner,
 // product (groups = 1: run_dense, the matrix core; groups > 1: dn_group_conv), and per output
 // rq -> eval batch norm -> clamp -> fq_out in the store (gemm_dense.h DnFuse).  Each quantizer
 // writes its bias (the reference quantizer's custom_bias) like fp8a_conv2d_qin.
-static int fused_quantizer(const float *mx, int nbits, int mbits, int sign_bits, float *bias_out, int32_t *ibias_out,
-                           FqIn &f) {
-    f = FqIn{};
-    if (!mx) return FP8A_OK;
-    const int qE = nbits - sign_bits - mbits;
-    if (mbits < 1 || qE < 1) return fail(FP8A_EFORMAT, "bad FP8 quantizer format");
-    if (!bias_out || !ibias_out) return fail(FP8A_EINVAL, "null pointer");
-    f = FqIn{mx, qE, mbits, sign_bits};
-    return FP8A_OK;
-}
-
 int fp8a_dense_conv2d_fused(const float *x, const float *w, float *y, int64_t Bn, int64_t Cin, int64_t H, int64_t W,
                             int64_t Cout, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw, int groups,
                             int fmt, const float *w_maxval, int w_per_channel, int w_nbits, int w_mbits,
@@ -2990,20 +3005,8 @@ int fp8a_dense_conv2d_fused(const float *x, const float *w, float *y, int64_t Bn
     fz.hi = act_hi;
     if (groups != 1)
         return grouped_conv_impl(x, w, y, Bn, Cin, H, W, Cout, groups, kh, kw, sh, sw, ph, pw, dh, dw, fz, s);
-    if (kh < 1 || kw < 1 || sh < 1 || sw < 1 || dh < 1 || dw < 1 || ph < 0 || pw < 0 || Bn < 0 || Cin < 0 || Cout < 0)
-        return fail(FP8A_EINVAL, "bad convolution geometry");
-    const int64_t Ho = (H + 2 * ph - dh * (kh - 1) - 1) / sh + 1;
-    const int64_t Wo = (W + 2 * pw - dw * (kw - 1) - 1) / sw + 1;
-    if (Ho <= 0 || Wo <= 0) return fail(FP8A_EINVAL, "empty convolution output");
-    DenseArgs a = dense_args();
-    a.x = x; a.w = w; a.y = y; a.conv = 1;
-    a.C = Cin; a.H = H; a.W = W; a.Ho = Ho; a.Wo = Wo;
-    a.kh = kh; a.kw = kw; a.sh = sh; a.sw = sw; a.ph = ph; a.pw = pw; a.dh = dh; a.dw = dw;
-    a.M = Bn * Ho * Wo; a.N = Cout; a.K = Cin * kh * kw;
-    a.sbk = 1; a.sbn = a.K;
-    a.ldc = Cout; a.fmt = fmt;
-    a.fz = fz;
-    return run_dense(a, workspace, workspace_bytes, s);
+    return dense_conv(ConvShape{Bn, Cin, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, 1}, x, w, y, fmt, fz, workspace,
+                      workspace_bytes, s);
 }
 
 }  // extern "C"
