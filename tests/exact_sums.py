@@ -1,0 +1,711 @@
+"""K > 1 sums that can be compared bit for bit: data and plain helpers shared by
+tests/test_exact_sums_cpu.py and tests/test_gpu_exact_sums.py.  No GPU, no reference code.
+
+Let T[m, k, n] be the oracle's per-product terms of a case (oracle.terms) and u = unit(T) the largest
+power of two that divides every nonzero T.  If
+
+    max over outputs of  sum_k |T|  <=  2^22 * u                                       (the budget)
+
+every partial sum of the terms, in any order and any grouping, is an integer multiple of u below 2^22 u:
+an exact float32.  The float32 sum is then the same for every summation order, equals
+expected(T) = float32(sum_k float64(T)), and a kernel's result can be compared with it by bits
+(pairs_cases.same_bits: zeros by value).  2^22 and not float32's 2^24: the two spare bits keep the condition
+inside what was measured for the matrix core's own adder.  The budget is a condition on the
+inputs, checked on the oracle's terms alone; a case that misses it fails (tests/test_exact_sums_cpu.py).
+
+The operand generator places the operands' exponent codes so that the terms cover the delicate part of the
+result quantizer Q_R: with per-product quantization (qbma) the product exponent e_a + e_b - bA - bB runs
+from three binades below the flush point 2^(-bR - M) (half the subnormal quantum u = 2^(1 - bR - M)) through
+the subnormal band up into the normal range, as far as the budget allows for the case's K; without it the
+terms' unit is the product of the operands' own steps and the windows are a few binades per operand.
+"""
+import functools
+import math
+
+import numpy as np
+
+from tests import pairs_cases as pc
+
+BUDGET_LOG2 = 22
+SEED = 0  # of every draw; tests/test_exact_sums_cpu.py checks what the draws must hold
+
+
+# ------------------------------------------------------------------------------------------ the rule
+def unit(T):
+    """The largest power of two that divides every nonzero element of T (a float32 / float64 array); 0.0
+    if T has no nonzero element."""
+    v = np.abs(np.asarray(T, np.float64).ravel())
+    v = v[v != 0]
+    if v.size == 0:
+        return 0.0
+    m, e = np.frexp(v)                               # v = m 2^e, m in [0.5, 1): m 2^53 is an integer
+    mi = (m * 2.0 ** 53).astype(np.int64)
+    tz = np.log2((mi & -mi).astype(np.float64)).astype(np.int64)  # trailing zero bits of the significand
+    return float(2.0 ** int((e - 53 + tz).min()))
+
+
+def abs_sum(T, axis=1):
+    return np.abs(np.asarray(T, np.float64)).sum(axis=axis)
+
+
+def budget_log2(T, axis=1):
+    """log2(max_outputs sum_k |T| / u): the case meets the budget iff this is <= 22 (-inf: no nonzero term)."""
+    u = unit(T)
+    if u == 0.0:
+        return -math.inf
+    return math.log2(float(abs_sum(T, axis).max()) / u)
+
+
+def within_budget(T, axis=1):
+    return budget_log2(T, axis) <= BUDGET_LOG2
+
+
+def expected(T, axis=1):
+    """float32(sum_k float64(T)): under the budget the float64 sum is exact and so is its cast."""
+    return np.asarray(T, np.float64).sum(axis=axis).astype(np.float32)
+
+
+def old_bar_in_units(T, axis=1):
+    """What golden_io.sum_tolerance allowed per output, 1e-5 sum|T|, in units of u."""
+    u = unit(T)
+    return 1e-5 * abs_sum(T, axis) / u if u else np.zeros(np.asarray(T).shape[:axis] + np.asarray(T).shape[axis + 1:])
+
+
+def mismatches(got, want):
+    """Indices where got and want differ under the comparison rule (equal bits, zeros by value)."""
+    return np.argwhere(~pc.same_bits(got, want))
+
+
+def assert_same(got, want, what, T=None):
+    """Bit equality; on failure names the first output and, given the terms, the difference in units."""
+    bad = mismatches(got, want)
+    if len(bad):
+        i = tuple(int(v) for v in bad[0])
+        extra = ""
+        if T is not None:
+            u = unit(T)
+            diff = (float(np.asarray(got)[i]) - float(np.asarray(want)[i])) / u
+            extra = f" (difference {diff:+g} u, u = 2^{math.log2(u):g})"
+        raise AssertionError(f"{what}: {len(bad)} of {np.asarray(want).size} sums differ from the oracle; first at "
+                             f"{i}: got {np.asarray(got)[i]!r} expected {np.asarray(want)[i]!r}{extra}")
+
+
+# ------------------------------------------------------------------------------------------ shares
+def shares(T, A, B, M, bR):
+    """Among products of two nonzero operands: the shares of terms flushed to zero, in the subnormal band
+    (0 < |T| < 2^(1 - bR): at most 2^M u) and normal, and the number of binades the nonzero terms occupy."""
+    nz = (np.asarray(A)[:, :, None] != 0) & (np.asarray(B)[None, :, :] != 0)
+    t = np.abs(np.asarray(T, np.float64))[nz]
+    n = max(t.size, 1)
+    band_top = 2.0 ** (1 - bR)
+    nzt = t[t != 0]
+    binades = np.unique(np.frexp(nzt)[1]).size if nzt.size else 0
+    return dict(flushed=np.count_nonzero(t == 0) / n, band=np.count_nonzero((t != 0) & (t < band_top)) / n,
+                normal=np.count_nonzero(t >= band_top) / n, binades=binades)
+
+
+# ------------------------------------------------------------------------------------------ operands
+def _clog2(k):
+    return max(0, math.ceil(math.log2(max(1, k))))
+
+
+def windows(E, M, bA, bB, bR, K, flags, spare=0):
+    """Exponent-code windows (inclusive) of the operands: (a_lo, a_hi), and per column (b_lo[n], b_hi[n]).
+
+    With qbma the product exponent P = e_a + e_b - bA - bB of two normal codes is to run from
+    lo = -bR - M - 3 (three binades below the flush point) to hi = (1 - bR - M) + 19 - ceil(log2 K): a term is
+    below 4 * 2^P, so K of them stay below 2^22 u.  Without qbma the unit is the product of the operands' own
+    steps 2^(a_lo - M - bA) 2^(b_lo - M - bB); the terms then are below 4 * 2^(2M + wa + wb + spread of bB) u, which
+    leaves wa + wb = 18 - 2M - ceil(log2 K) - spread code steps by that worst case.  The worst case is far from
+    the draw (a term's mean is about a tenth of it: uniform codes, uniform mantissas), so at least one step per
+    operand is kept; the CPU test decides.  Windows are cut to the codes the format has; code 0 stands for the
+    subnormals (and zero).  The v5 model (one bias b) decodes r = e_a + e_b - b as an exponent code of the
+    (E, M, b) grid: r runs from 1 to 18 - M - ceil(log2 K), so that K terms below 2^(r + 1 - b) stay below 2^22
+    steps 2^(1 - b - M).  v5 cases are drawn from normal codes without zeros: a zero or an underflowing sum wraps
+    (mod 2^M, floor division) to a term far from its neighbours, which spends the budget on one product; the
+    every-code-pair tests pin those."""
+    emax = (1 << E) - 1
+    bB = np.asarray(bB, np.int64).reshape(-1)
+    cl = _clog2(K) + spare  # (spare: bits of the budget a case keeps for an operand off the grid)
+    spread = int(bB.max() - bB.min())
+    if flags & pc.V5:
+        b = int(bA)
+        r_lo, r_hi = 1, min(emax, BUDGET_LOG2 - 4 - M - cl)
+        t_lo, w = b + r_lo, r_hi - r_lo
+        a_lo = max(1, min(t_lo // 2, emax))
+        b_lo = max(1, min(t_lo - a_lo, emax))
+        wa = min((w + 1) // 2, emax - a_lo)
+        wb = min(w - wa, emax - b_lo)
+        return (a_lo, a_lo + wa), (np.full(bB.shape, b_lo, np.int64), np.full(bB.shape, b_lo + wb, np.int64))
+    if not flags & pc.QBMA:
+        w = max(2, BUDGET_LOG2 - 4 - 2 * M - cl - spread)
+        wa = min(w // 2, emax - 1)
+        wb = min(w - wa, emax - 1)
+        b_hi = np.full(bB.shape, emax, np.int64)
+        return (emax - wa, emax), (b_hi - wb, b_hi)
+    lo = -bR - M - 3
+    hi = (1 - bR - M) + (BUDGET_LOG2 - 3) - cl
+    if flags & pc.TB:  # no subnormal floor: Q_R rounds at the term's own binade, u = 2^(lowest binade - M); the
+        lo = -bR - 3   # window straddles the expo-0 binade [2^-bR, 2^(1 - bR)) and the F7 interval above 2^-bR
+        hi = lo + (BUDGET_LOG2 - 3) - cl - M - 2
+    s_lo, s_hi = lo + bA + bB, hi + bA + bB           # sums of the two codes at the window's ends, per column
+    span = hi - lo
+    wa = min(max(span - 2, span // 2), emax)        # A takes all but two binades: P is then close to uniform
+    a_lo = int(np.clip(int(s_lo.min()), 0, emax - wa))
+    a_hi = a_lo + wa
+    b_lo = np.clip(s_lo - a_lo, 0, emax)
+    b_hi = np.clip(s_hi - a_hi, 0, emax)
+    if np.any(b_lo > b_hi) or np.any(s_lo - a_lo > emax) or np.any(s_hi - a_hi < 0):
+        raise ValueError(f"E{E}M{M} biases {bA, bB.min(), bB.max(), bR}: no exponent codes inside the window")
+    return (a_lo, a_hi), (b_lo, b_hi)
+
+
+def draw(rng, E, M, shape, bias, lo, hi, zero_frac):
+    """On-grid values: exponent codes uniform (stratified) in [lo, hi] (broadcast), code 0 = subnormal with a
+    mantissa whose bit length is uniform (small subnormals as likely as large ones), both signs, a share of zeros."""
+    bias = np.broadcast_to(np.asarray(bias, np.int64), shape)
+    lo = np.broadcast_to(np.asarray(lo, np.int64), shape)
+    hi = np.broadcast_to(np.asarray(hi, np.int64), shape)
+    n = int(np.prod(shape))
+    strat = ((rng.permutation(n) + rng.random(n)) / n).reshape(shape)  # (stratified: small shapes cover the window)
+    code = lo + (strat * (hi - lo + 1)).astype(np.int64)
+    mant = rng.integers(0, 1 << M, size=shape)
+    bits = rng.integers(1, M + 1, size=shape)
+    sub = (rng.integers(0, 1 << 30, size=shape) % (1 << bits)) | (1 << (bits - 1))  # bit length `bits`: 1 .. 2^M - 1
+    v = np.where(code == 0, np.ldexp(sub / 2.0 ** M, (1 - bias).astype(np.int32)),
+                 np.ldexp(1.0 + mant / 2.0 ** M, (code - bias).astype(np.int32)))
+    v = v * rng.choice([-1.0, 1.0], size=shape)
+    v[rng.random(shape) < zero_frac] = 0.0
+    return v.astype(np.float32)
+
+
+def operands(E, M, bA, bB, bR, shape, flags, seed=0, zero_frac=0.1, spare=0):
+    """(A [Mr, K], B [K, N]) on the grids of (E, M, bA) and (E, M, bB[n]), drawn inside windows()."""
+    Mr, K, N = shape
+    bB = np.broadcast_to(np.asarray(bB, np.int64).reshape(-1), (N,))
+    (a_lo, a_hi), (b_lo, b_hi) = windows(E, M, bA, bB, bR, K, flags, spare)
+    rng = np.random.default_rng([SEED + seed, E, M, Mr, K, N])  # (one draw per window: the flag sets share it)
+    if flags & pc.V5:
+        zero_frac = 0.0
+    A = draw(rng, E, M, (Mr, K), bA, a_lo, a_hi, zero_frac)
+    B = draw(rng, E, M, (K, N), bB[None, :], b_lo[None, :], b_hi[None, :], zero_frac)
+    return A, B
+
+
+def per_column_bias(base, N, spread, seed=0):
+    """bB per column: base .. base + spread, every value present where N allows."""
+    rng = np.random.default_rng([seed, N, spread])
+    b = base + rng.integers(0, spread + 1, size=N)
+    b[:min(N, spread + 1)] = base + np.arange(min(N, spread + 1))
+    return b.astype(np.int32)
+
+
+# ------------------------------------------------------------------------------------------ cases
+# Bias triples (bA, first bB, spread of bB over the columns, bR) per format: the ones the kernels' own test
+# files use for sums (E4M3: bA + min bB - bR >= 17, E5M2: >= 33 keep every term inside the scaled fp8 range;
+# E3M4: inside gemm_tt16_kernel's f16 window), E2M5 with bR three higher so that a quarter of the terms is normal.
+BIASES = {(4, 3): (10, 14, 2, 7), (5, 2): (20, 20, 2, 7), (3, 4): (7, 9, 2, 8), (2, 5): (5, 7, 1, 9)}
+FL = pc.flag_word(True, True, True, False)           # the matrix-core / tile-table flag set
+FL_FAST = pc.flag_word(True, False, True, True)      # one fast-kernel flag set with a band (qbma on)
+MAT_SHAPES = [(1, 64, 1), (65, 17, 63), (257, 17, 5), (130, 300, 129)]
+SPLITK_SHAPE = (64, 2304, 64)
+V5_SWITCHES = [(False, False, False), (True, True, False), (True, True, True)]
+V5_TABLE = {(4, 3): "d3", (3, 4): "d4", (2, 5): "d5", (5, 2): "zero"}
+
+
+def one_table_per_mode():
+    """(E, M, table name) per packing mode of pack_table: E4M3 gives the five one-word modes, E2M5 the two
+    two-word ones."""
+    out, seen = [], set()
+    for (E, M) in ((4, 3), (2, 5)):
+        for name, t in pc.tables(E, M).items():
+            mode = pc.table_mode(t, M)
+            if mode not in seen:
+                seen.add(mode)
+                out.append((E, M, name))
+    return out
+
+
+def _mat(fam, E, M, table, flags, shape, **kw):
+    Mr, K, N = shape
+    tag = kw.pop("tag", "")
+    key = f"{fam}-E{E}M{M}-{table}-f{flags}-{Mr}x{K}x{N}" + ("-offgrid" if kw.get("offgrid") else "") + \
+        ("-posA" if kw.get("posA") else "")
+    cid = key + (f"-{tag}" if tag and tag != "offgrid" else "")
+    return dict(kind="mat", id=cid, pkey=key, fam=fam, E=E, M=M, table=table, flags=flags, shape=shape, **kw)
+
+
+def matmul_cases():
+    """Matrix launches: per path of run_gemm the formats and tables the issue lists, at every shape."""
+    out = []
+    for shape in MAT_SHAPES:
+        K = shape[1]
+        out += [_mat("f8mx", 4, 3, "nocomp", FL, shape), _mat("f8mx", 4, 3, "zero", FL, shape),
+                _mat("f8mx", 5, 2, "zero", FL, shape), _mat("tt", 2, 5, "nocomp", FL, shape),
+                _mat("tt" if K < 64 else "tt16", 3, 4, "nocomp", FL, shape), _mat("tt16", 3, 4, "comp3", FL, shape)]
+        for (E, M, name) in one_table_per_mode():
+            for fl in pc.v9_flag_words(False):
+                out.append(_mat("fast", E, M, name, fl, shape))
+            out.append(_mat("fast", E, M, name, pc.flag_word(False, False, True, True), shape))
+        out.append(_mat("v5mx", 5, 2, "zero", pc.v5_flag_word(True, False, False), shape))
+        for (E, M) in ((4, 3), (3, 4), (2, 5)):
+            for sw in V5_SWITCHES:
+                out.append(_mat("v5fast", E, M, V5_TABLE[(E, M)], pc.v5_flag_word(*sw), shape))
+    # one off-grid A value per family: the approx kernels mark its units and the exact kernel recomputes them; the
+    # v5 kernels decode it to a code while staging, like the oracle (no fallback exists there)
+    big = MAT_SHAPES[-1]
+    out += [_mat("f8mx", 4, 3, "nocomp", FL, big, offgrid=True, tag="offgrid"),
+            _mat("f8mx", 5, 2, "zero", FL, big, offgrid=True, tag="offgrid"),
+            _mat("tt", 2, 5, "nocomp", FL, big, offgrid=True, tag="offgrid"),
+            _mat("tt16", 3, 4, "nocomp", FL, big, offgrid=True, tag="offgrid"),
+            _mat("fast", 4, 3, "nocomp", FL_FAST, big, offgrid=True, tag="offgrid"),
+            _mat("v5mx", 5, 2, "zero", pc.v5_flag_word(True, False, False), big, offgrid=True, tag="offgrid"),
+            _mat("v5fast", 4, 3, "d3", pc.v5_flag_word(True, True, True), big, offgrid=True, tag="offgrid")]
+    return out
+
+
+def splitk_cases():
+    """(64, 2304, 64) with the split count forced; the in-launch sum (splitk_fixup) exists for gemm_f8mx only."""
+    out = []
+    for fam, E, M, fl in (("f8mx", 4, 3, FL), ("tt", 2, 5, FL), ("fast", 4, 3, FL_FAST)):
+        for S in (2, 3, 6):
+            for fix in ((0, 1) if fam == "f8mx" else (0,)):
+                out.append(_mat(fam, E, M, "nocomp", fl, SPLITK_SHAPE, opts={"splitk": S, "splitk_fixup": fix},
+                                tag=f"s{S}x{fix}", split=True))
+    return out
+
+
+# xm_wave_rows selects between the two 128 x 64 instances, which run only with xm_ncg = 4 (and xm_pipe = 1, the
+# default): both are forced in one launch.  xm_sign_rows builds the positive-sign rows alone only when A holds no
+# negative value: its two values run on the drawn A (both signs: the full build either way) and on |A|.
+SCHEDULES = [{"xm_ncg": 1}, {"xm_ncg": 2}, {"xm_ncg": 4}, {"af32_maxct": 0}, {"af32_maxct": 64}, {"xm_pipe": 0},
+             {"xm_pipe": 1}, {"xm_ncg": 4, "xm_wave_rows": 0}, {"xm_ncg": 4, "xm_wave_rows": 1},
+             {"xm_sign_rows": 0}, {"xm_sign_rows": 1}]
+SCHEDULES_POS = [{"xm_sign_rows": 0}, {"xm_sign_rows": 1}]
+SCHED_CONV = dict(B=2, cin=16, cout=24, k=3, s=1, p=1, d=1, g=1, hw=12)
+SCHED_CONV_1X1 = dict(B=2, cin=32, cout=24, k=1, s=1, p=0, d=1, g=1, hw=12)  # (A staged from fp32 needs a 1 x 1 conv)
+
+
+def _opt_tag(o):
+    return "_".join(f"{k}{v}" for k, v in o.items())
+
+
+def schedule_cases():
+    out = [_mat("f8mx", 4, 3, "nocomp", FL, MAT_SHAPES[-1], opts=o, tag=_opt_tag(o)) for o in SCHEDULES]
+    out += [_mat("f8mx", 4, 3, "nocomp", FL, MAT_SHAPES[-1], opts=o, tag=_opt_tag(o), posA=True) for o in SCHEDULES_POS]
+    out += [_conv("f8mx", 4, 3, "nocomp", FL, SCHED_CONV_1X1 if "af32_maxct" in o else SCHED_CONV, opts=o,
+                  tag=_opt_tag(o)) for o in SCHEDULES]
+    out += [_conv("f8mx", 4, 3, "nocomp", FL, SCHED_CONV, opts=o, tag=_opt_tag(o), posA=True) for o in SCHEDULES_POS]
+    return out
+
+
+def expected_sign_build(c):
+    """fp8a_xm_sign_stats of one gemm_f8mx launch of a case: the half build only with xm_sign_rows on (the default)
+    and no negative A value."""
+    half = bool(c.get("posA")) and (c.get("opts") or {}).get("xm_sign_rows", 1) != 0
+    return dict(half=int(half), full=int(not half))
+
+
+# the geometries of tests/test_gpu_f8mx.py::test_conv_fast_path_matches_oracle with batch <= 2, <= 32 channels
+CONVS = [
+    dict(B=2, cin=3, cout=32, k=7, s=2, p=3, d=1, g=1, hw=30),     # conv1 class, K = 147
+    dict(B=2, cin=16, cout=24, k=3, s=1, p=1, d=1, g=1, hw=13),    # ragged M (338), N (24)
+    dict(B=2, cin=24, cout=32, k=3, s=2, p=2, d=2, g=1, hw=17),    # dilation
+    dict(B=2, cin=32, cout=24, k=1, s=2, p=0, d=1, g=1, hw=15),    # 1x1 downsample class
+    dict(B=2, cin=16, cout=32, k=3, s=1, p=1, d=1, g=2, hw=9),     # groups
+    dict(B=1, cin=32, cout=32, k=3, s=1, p=1, d=1, g=1, hw=7),     # the deepest K (288)
+    dict(B=2, cin=16, cout=24, k=3, s=2, p=1, d=1, g=1, hw=28),    # stride 2, H*W % 4 == 0
+    dict(B=2, cin=24, cout=16, k=1, s=2, p=0, d=1, g=1, hw=16),    # 1x1 stride-2 downsample
+    dict(B=2, cin=8, cout=20, k=3, s=2, p=2, d=2, g=2, hw=14),     # stride 2 + dilation + groups
+    dict(B=2, cin=8, cout=20, k=3, s=2, p=2, d=2, g=2, hw=15),     # the same with H*W % 4 != 0
+]
+
+
+def _conv(fam, E, M, table, flags, cfg, **kw):
+    tag = kw.pop("tag", "")
+    geo = f"c{cfg['cin']}o{cfg['cout']}k{cfg['k']}s{cfg['s']}p{cfg['p']}d{cfg['d']}g{cfg['g']}hw{cfg['hw']}"
+    key = f"conv-{fam}-E{E}M{M}-{table}-f{flags}-{geo}" + ("-posA" if kw.get("posA") else "")
+    cid = key + (f"-{tag}" if tag else "")
+    return dict(kind="conv", id=cid, pkey=key, fam=fam, E=E, M=M, table=table, flags=flags, cfg=cfg, **kw)
+
+
+def conv_cases():
+    out = []
+    for cfg in CONVS:
+        Kg = cfg["cin"] // cfg["g"] * cfg["k"] ** 2
+        out += [_conv("f8mx", 4, 3, "nocomp", FL, cfg), _conv("tt" if Kg < 64 else "tt16", 3, 4, "nocomp", FL, cfg),
+                _conv("tt", 2, 5, "nocomp", FL, cfg), _conv("fast", 4, 3, "nocomp", FL_FAST, cfg)]
+    return out
+
+
+BAND_BIASES = (5, 7)   # E2M5: bA, bB of the constructed wave-tiles
+BAND_SHAPE = (130, 12, 80)
+BAND_SPOT = (70, 5, 37)  # (row, K position, column): second row half, second staged tile, not its first K-step
+
+
+def band_cases():
+    """gemm_tt_kernel's wave-tile forms (E2M5): every operand has exponent code 1 or 2, so every product is
+    below 2^(6 - bA - bB); `band`: bR puts that at the grid's smallest normal 2^(1 - bR) and the one product of
+    the two code-3 operands at BAND_SPOT sits exactly there; `zero`: bR puts it at half the quantum
+    2^(-bR - M) and that product is the tie (`zero`) or one mantissa step above it (`zero1`)."""
+    out = []
+    for regime in ("band", "zero", "zero1"):
+        for tb in (0, 1):
+            for table in ("nocomp", "zero"):
+                key = f"band-{regime}-{table}"
+                out.append(dict(kind="band", id=f"{key}-tt_band{tb}", pkey=key, fam="tt", E=2, M=5, table=table,
+                                flags=FL, regime=regime, opts={"tt_band": tb}, shape=BAND_SHAPE))
+    return out
+
+
+BMM_SHAPES = [(70, 64, 65), (65, 70, 64)]
+BMM_FORMATS = [(4, 3, "nocomp"), (5, 2, "zero"), (3, 4, "nocomp")]   # LUT + conversion (twice), arithmetic
+
+
+def bmm_cases():
+    out = []
+    for (E, M, name) in BMM_FORMATS:
+        for shape in BMM_SHAPES:
+            for off in (False, True):
+                cid = f"bmm-E{E}M{M}-{name}-{'x'.join(map(str, shape))}" + ("-offgrid" if off else "")
+                out.append(dict(kind="bmm", id=cid, pkey=cid, fam="bmm", E=E, M=M, table=name, flags=FL, shape=shape,
+                                offgrid=off, items=3))
+    return out
+
+
+# ------------------------------------------------------------------------------------------ exact product, qamaa
+DENSE_FORMS = {"bf16": (4, 3), "e4m3": (4, 3), "e5m2": (5, 2)}   # operand grid per dense form (tests/test_gpu_dense.py)
+DENSE_SHAPES = [(7, 33, 5), (130, 300, 129)]
+# test_gpu_dense.py's first geometry; one with K = 27 <= 32, N <= 64 (dn_direct_kernel)
+DENSE_CONV = dict(B=2, cin=16, H=15, W=17, cout=24, k=3, stride=(2, 1), pad=(1, 2), dil=(1, 2))
+DENSE_DIRECT = dict(B=2, cin=3, H=12, W=13, cout=32, k=3, stride=(1, 1), pad=(1, 1), dil=(1, 1))
+DENSE_DW = dict(B=2, C=8, hw=9)
+
+
+def dense_cases():
+    """fp8a_dense_matmul / fp8a_dense_conv2d / fp8a_grouped_conv2d: the float64 product of on-grid operands, cast
+    to float32.  The off-grid value 1 + 2^-8 (the fp32 units of dn_fix recompute its row) spends five more bits
+    of the budget, not twenty; that case's windows are narrower by as much."""
+    out = []
+    for form, (E, M) in DENSE_FORMS.items():
+        for shape in DENSE_SHAPES:
+            cid = f"dense-{form}-{'x'.join(map(str, shape))}"
+            out.append(dict(kind="dense", id=cid, pkey=cid, fam="dense", form=form, E=E, M=M, flags=0, shape=shape))
+        cid = f"dense-{form}-130x300x129-offgrid"
+        out.append(dict(kind="dense", id=cid, pkey=cid, fam="dense", form=form, E=E, M=M, flags=0,
+                        shape=DENSE_SHAPES[1], offgrid=True))
+        out.append(dict(kind="dconv", id=f"dense-{form}-conv", pkey=f"dense-{form}-conv", fam="dense", form=form, E=E,
+                        M=M, flags=0, geo=DENSE_CONV, opts={}))
+        for d in (0, 1):
+            out.append(dict(kind="dconv", id=f"dense-{form}-conv-dn_direct{d}", pkey=f"dense-{form}-convk27",
+                            fam="dense", form=form, E=E, M=M, flags=0, geo=DENSE_DIRECT, opts={"dn_direct": d}))
+    for stride in (1, 2):
+        for d in (0, 1, 2):
+            out.append(dict(kind="ddw", id=f"dense-dw3x3-s{stride}-dw3_{d}", pkey=f"dense-dw3x3-s{stride}", fam="dense",
+                            E=4, M=3, flags=0, stride=stride, opts={"dw3": d}))
+    return out
+
+
+QAMAA = dict(id="qamaa-E4M3-65x70x63", pkey="qamaa-E4M3-65x70x63", kind="qamaa", fam="qamaa", E=4, M=3, flags=0,
+             shape=(65, 70, 63), maxval=2.5)
+
+
+def _product_terms(A, B):
+    return A.astype(np.float64)[:, :, None] * B.astype(np.float64)[None, :, :]
+
+
+def _dense_operands(c, shape, seed, spare=0):
+    E, M = c["E"], c["M"]
+    bA, base, _, bR = BIASES[(E, M)]
+    return operands(E, M, bA, np.full(shape[2], base, np.int32), bR, shape, 0, seed=seed, spare=spare) + (bA, base)
+
+
+def _dense_image(c, xshape, wshape, K, seed):
+    """x and w of an exact-product convolution, drawn directly inside the windows of a K-term sum."""
+    E, M = c["E"], c["M"]
+    bA, base, _, bR = BIASES[(E, M)]
+    (a_lo, a_hi), (b_lo, b_hi) = windows(E, M, bA, [base], bR, K, 0)
+    rng = np.random.default_rng([SEED + seed, E, M, K] + list(xshape))
+    return (draw(rng, E, M, xshape, bA, a_lo, a_hi, 0.1), draw(rng, E, M, wshape, base, int(b_lo[0]), int(b_hi[0]), 0.1))
+
+
+def _dense_problem(c):
+    E, M = c["E"], c["M"]
+    if c["kind"] == "dense":
+        A, B, bA, _ = _dense_operands(c, c["shape"], 1, spare=5 if c.get("offgrid") else 0)
+        if c.get("offgrid"):  # 1 + 2^-8: the shortest significand off bf16's grid too, five bits finer than E4M3's
+            A[70, 5] = np.float32(np.ldexp(1.0 + 2.0 ** -8, (1 << E) - 1 - bA))
+        return dict(A=A, B=B, parts=[(A, B, _product_terms(A, B), slice(None))])
+    if c["kind"] == "dconv":
+        g = c["geo"]
+        K = g["cin"] * g["k"] ** 2
+        x, w = _dense_image(c, (g["B"], g["cin"], g["H"], g["W"]), (g["cout"], g["cin"], g["k"], g["k"]), K, 2)
+        import torch
+        cols = torch.nn.functional.unfold(torch.from_numpy(x), (g["k"], g["k"]), dilation=g["dil"], padding=g["pad"],
+                                          stride=g["stride"])
+        cols = cols.transpose(1, 2).reshape(-1, K).numpy()
+        Bm = np.ascontiguousarray(w.reshape(g["cout"], -1).T)
+        return dict(x=x, w=w, parts=[(cols, Bm, _product_terms(cols, Bm), slice(None))])
+    g = DENSE_DW                                         # depthwise 3 x 3, padding 1: one part per channel
+    x, w = _dense_image(c, (g["B"], g["C"], g["hw"], g["hw"]), (g["C"], 1, 3, 3), 9, 3)
+    cfg = dict(k=3, d=1, p=1, s=c["stride"])
+    cols = unfold(x, cfg)                                # [B Ho Wo, C * 9]
+    parts = []
+    for ch in range(g["C"]):
+        Ac = np.ascontiguousarray(cols[:, ch * 9:(ch + 1) * 9])
+        Bc = np.ascontiguousarray(w[ch].reshape(1, 9).T)
+        parts.append((Ac, Bc, _product_terms(Ac, Bc), slice(ch, ch + 1)))
+    return dict(x=x, w=w, parts=parts)
+
+
+def _qamaa_problem(c):
+    """fq(sum_k fq(a b)): operands on a power-of-two-scaled 4-bit-significand grid, their products from four
+    binades below the quantizer's subnormal step up to what the budget allows; the inner terms fq(a b) come from
+    the oracle's quantizer (oracle.fp8_fake_quant)."""
+    from oracle import oracle as orc
+    E, M = c["E"], c["M"]
+    Mr, K, N = c["shape"]
+    _, bias = orc.fp8_fake_quant(np.ones(1, np.float32), c["maxval"], E, M)
+    lu = 1 - int(bias[0]) - M                           # log2 of the quantizer's subnormal step
+    lo, hi = lu - 4, lu + BUDGET_LOG2 - 3 - _clog2(K)
+    rng = np.random.default_rng([SEED + 5, Mr, K, N])
+    wa = (hi - lo) - 2
+    A = draw(rng, 5, M, (Mr, K), 0, 8, 8 + wa, 0.1) * np.float32(2.0 ** (lo - 16))
+    B = draw(rng, 5, M, (K, N), 0, 8, 10, 0.1)
+    P = (A[:, :, None] * B[None, :, :]).astype(np.float32)   # exact: two 4-bit significands
+    T, _ = orc.fp8_fake_quant(P.reshape(1, -1), c["maxval"], E, M)
+    return dict(A=A.astype(np.float32), B=B, bR=int(bias[0]), parts=[(A, B, T.reshape(P.shape), slice(None))])
+
+
+# ------------------------------------------------------------------------------------------ tensor-bias depthwise
+FL_TB_DIRECT = pc.flag_word(True, False, True, False)   # s2n off: conv_tb_direct_kernel alone
+TB_PLANES = [7, 9, 14]
+
+
+def _tbdw(form, E, M, table, flags, hw, stride, opts):
+    key = f"tbdw-E{E}M{M}-{table}-f{flags}-hw{hw}s{stride}"
+    return dict(kind="tbdw", id=key + (f"-{_opt_tag(opts)}" if opts else ""), pkey=key, fam=form, E=E, M=M, table=table,
+                flags=flags, hw=hw, stride=stride, opts=opts, C=8, B=2)
+
+
+def tbdw_cases():
+    """Depthwise 3 x 3 (single-output-channel groups: tensor-bias semantics), padding 1, all nine taps nonzero,
+    8 channels with their own bW, planes whose width is and is not a multiple of 4.  The v5 form runs with the
+    adder wrap and with_UF_opt: the padding's zeros are operands too, and without the underflow option their
+    wrapped terms alone spend the budget (2^32 u)."""
+    out = []
+    for hw in TB_PLANES:
+        for stride in (1, 2):
+            for tbs in (0, 1, 2):
+                for rw in (1, 2):
+                    out.append(_tbdw("tbx", 4, 3, "nocomp", FL, hw, stride, {"tbs": tbs, "tbx_rw": rw}))
+            out += [_tbdw("tb_fast", 3, 4, "nocomp", FL, hw, stride, {}),
+                    _tbdw("tb_fast", 2, 5, "nocomp", FL, hw, stride, {}),
+                    _tbdw("tb_direct", 4, 3, "nocomp", FL_TB_DIRECT, hw, stride, {})]
+            for v in (0, 1):
+                out.append(_tbdw("v5dw", 5, 2, "zero", pc.v5_flag_word(True, False, True), hw, stride, {"v5ds": v}))
+    return out
+
+
+def _tbdw_problem(c):
+    from oracle import oracle as orc
+    E, M, fl, C, hw = c["E"], c["M"], c["flags"], c["C"], c["hw"]
+    bA, bW, bR = case_biases(c, C)
+    tfl = fl if fl & pc.V5 else fl | pc.TB
+    (a_lo, a_hi), (b_lo, b_hi) = windows(E, M, bA, bW, bR, 9, tfl)
+    rng = np.random.default_rng([SEED + 13, E, M, hw, c["stride"], int(fl)])
+    x = draw(rng, E, M, (c["B"], C, hw, hw), bA, a_lo, a_hi, 0.0 if fl & pc.V5 else 0.1)
+    sh = (C, 1, 1, 1)
+    w = draw(rng, E, M, (C, 1, 3, 3), bW.reshape(sh), b_lo.reshape(sh), b_hi.reshape(sh), 0.0)
+    cols = unfold(x, dict(k=3, d=1, p=1, s=c["stride"]))
+    tab = case_table(c)
+    parts = []
+    for ch in range(C):
+        Ac = np.ascontiguousarray(cols[:, ch * 9:(ch + 1) * 9])
+        Bc = np.ascontiguousarray(w[ch].reshape(1, 9).T)
+        parts.append((Ac, Bc, orc.terms(Ac, Bc, E, M, bA, bW[ch:ch + 1], bR, tab, tfl), slice(ch, ch + 1)))
+    return dict(x=x, w=w, bA=bA, bB=bW, bR=bR, table=tab, parts=parts, flags=tfl)
+
+
+def all_cases():
+    return matmul_cases() + splitk_cases() + schedule_cases() + band_cases() + conv_cases() + bmm_cases() + \
+        dense_cases() + [QAMAA] + tbdw_cases()
+
+
+# ------------------------------------------------------------------------------------------ problems
+def case_table(c):
+    return (pc.v5_tables if c["flags"] & pc.V5 else pc.tables)(c["E"], c["M"])[c["table"]]
+
+
+def case_biases(c, N):
+    """(bA, bB[N], bR); the v5 model has one bias."""
+    E, M = c["E"], c["M"]
+    if c["flags"] & pc.V5:
+        b = pc.v5_biases(E)[1]
+        return b, np.full(N, b, np.int32), b
+    bA, base, spread, bR = BIASES[(E, M)]
+    return bA, per_column_bias(base, N, spread), bR
+
+
+def off_grid_value(bA, window):
+    """A value with 24 significant bits, on no (E, M) grid, in the middle binade of A's exponent window."""
+    return np.float32(np.ldexp(np.float32(1.2001), (window[0] + window[1]) // 2 - int(bA)))
+
+
+def _mat_problem(c):
+    E, M = c["E"], c["M"]
+    Mr, K, N = c["shape"]
+    bA, bB, bR = case_biases(c, N)
+    A, B = operands(E, M, bA, bB, bR, c["shape"], c["flags"])
+    spot = None
+    if c.get("offgrid"):
+        spot = (Mr // 2, K - 1)
+        A[spot] = off_grid_value(bA, windows(E, M, bA, bB, bR, K, c["flags"])[0])
+    if c.get("posA"):
+        A = np.abs(A)
+    return dict(A=A, B=B, bA=bA, bB=bB, bR=bR, spot=spot)
+
+
+def _band_problem(c):
+    E, M = c["E"], c["M"]
+    Mr, K, N = c["shape"]
+    bA, b = BAND_BIASES
+    bB = np.full(N, b, np.int32)
+    top = 6 - bA - b                                  # every product of two codes <= 2 is below 2^top
+    bR = 1 - top if c["regime"] == "band" else -top - M
+    rng = np.random.default_rng([7, Mr, K, N])
+    A = draw(rng, E, M, (Mr, K), bA, 1, 2, 0.1)
+    B = draw(rng, E, M, (K, N), b, 1, 2, 0.1)
+    r, k, n = BAND_SPOT
+    A[r, k] = np.ldexp(1.0 + (1 / 32 if c["regime"] == "zero1" else 0.0), 3 - bA)
+    B[k, n] = np.ldexp(1.0, 3 - b)
+    row = draw(rng, E, M, (N,), b, 1, 1, 0.0)         # the K-step's other columns: code 1, no zero
+    row[n] = B[k, n]
+    B[k] = row
+    A[A[:, k] == 0, k] = np.ldexp(1.0, 1 - bA)
+    return dict(A=A, B=B, bA=bA, bB=bB, bR=bR, spot=None)
+
+
+def conv_out_hw(cfg):
+    return (cfg["hw"] + 2 * cfg["p"] - cfg["d"] * (cfg["k"] - 1) - 1) // cfg["s"] + 1
+
+
+def unfold(x, cfg):
+    """im2col of x [B, C, H, W] as rows [B * Ho * Wo, C * k * k] (torch.nn.functional.unfold's order)."""
+    import torch
+    cols = torch.nn.functional.unfold(torch.from_numpy(np.ascontiguousarray(x)), (cfg["k"], cfg["k"]),
+                                      dilation=cfg["d"], padding=cfg["p"], stride=cfg["s"])
+    return cols.transpose(1, 2).reshape(-1, cols.shape[1]).numpy()
+
+
+def _conv_problem(c):
+    E, M, cfg = c["E"], c["M"], c["cfg"]
+    cig, cout = cfg["cin"] // cfg["g"], cfg["cout"]
+    K = cig * cfg["k"] ** 2
+    bA, bW, bR = case_biases(c, cout)
+    (a_lo, a_hi), (b_lo, b_hi) = windows(E, M, bA, bW, bR, K, c["flags"])
+    rng = np.random.default_rng([11, E, M, cfg["cin"], cout, cfg["hw"], cfg["k"], int(c["flags"])])
+    x = draw(rng, E, M, (cfg["B"], cfg["cin"], cfg["hw"], cfg["hw"]), bA, a_lo, a_hi, 0.1)
+    sh = (cout, 1, 1, 1)
+    w = draw(rng, E, M, (cout, cig, cfg["k"], cfg["k"]), bW.reshape(sh), b_lo.reshape(sh), b_hi.reshape(sh), 0.1)
+    if c.get("posA"):
+        x = np.abs(x)
+    return dict(x=x, w=w, bA=bA, bB=bW, bR=bR)
+
+
+def _bmm_problem(c):
+    E, M = c["E"], c["M"]
+    Mr, K, N = c["shape"]
+    bA, base, _, bR = BIASES[(E, M)]
+    bB = np.full(N, base, np.int32)
+    items = [operands(E, M, bA, bB, bR, c["shape"], c["flags"], seed=100 + z) for z in range(c["items"])]
+    A = np.stack([a for a, _ in items])
+    B = np.stack([b for _, b in items])
+    spot = None
+    if c["offgrid"]:
+        spot = (1, 5, 3)
+        A[spot] = off_grid_value(bA, windows(E, M, bA, bB, bR, K, c["flags"])[0])
+    return dict(A=A, B=B, bA=bA, bB=bB, bR=bR, spot=spot)
+
+
+def problem(cid):
+    """problem_of(pkey) of a case: cases that differ only in options share one problem."""
+    return problem_of(CASES[cid]["pkey"])
+
+
+@functools.lru_cache(maxsize=6)
+def problem_of(pkey):
+    """The operands of a case (by id) with the oracle's terms: dict with bA, bB, bR, table and `parts`, a list of
+    (A [Mr, K], B [K, N], T [Mr, K, N], output slice) -- one part per group of a convolution or batch item --
+    plus the launch's own arrays (A / B, or x / w)."""
+    from oracle import oracle as orc
+    c = next(v for v in CASES.values() if v["pkey"] == pkey)
+    if c["kind"] in ("dense", "dconv", "ddw"):
+        return _dense_problem(c)
+    if c["kind"] == "qamaa":
+        return _qamaa_problem(c)
+    if c["kind"] == "tbdw":
+        return _tbdw_problem(c)
+    E, M, tab, fl = c["E"], c["M"], case_table(c), c["flags"]
+    if c["kind"] == "conv":
+        p = _conv_problem(c)
+        cfg = c["cfg"]
+        cols = unfold(p["x"], cfg)
+        g, cog = cfg["g"], cfg["cout"] // cfg["g"]
+        Kg = cols.shape[1] // g
+        p["parts"] = []
+        for i in range(g):
+            Ag = np.ascontiguousarray(cols[:, i * Kg:(i + 1) * Kg])
+            Bg = np.ascontiguousarray(p["w"][i * cog:(i + 1) * cog].reshape(cog, -1).T)
+            T = orc.terms(Ag, Bg, E, M, p["bA"], p["bB"][i * cog:(i + 1) * cog], p["bR"], tab, fl)
+            p["parts"].append((Ag, Bg, T, slice(i * cog, (i + 1) * cog)))
+    elif c["kind"] == "bmm":
+        p = _bmm_problem(c)
+        p["parts"] = [(a, b, orc.terms(a, b, E, M, p["bA"], p["bB"], p["bR"], tab, fl), z)
+                      for z, (a, b) in enumerate(zip(p["A"], p["B"]))]
+    else:
+        p = _band_problem(c) if c["kind"] == "band" else _mat_problem(c)
+        T = orc.terms(p["A"], p["B"], E, M, p["bA"], p["bB"], p["bR"], tab, fl)
+        p["parts"] = [(p["A"], p["B"], T, slice(None))]
+    p["table"] = tab
+    return p
+
+
+def case_terms(p):
+    """All terms of a problem as one [outputs, K] view per part, for unit() and the budget: the unit is taken
+    over the whole case."""
+    return [T for (_, _, T, _) in p["parts"]]
+
+
+def case_unit(p):
+    us = [unit(T) for T in case_terms(p)]
+    us = [u for u in us if u]
+    return min(us) if us else 0.0
+
+
+def case_budget_log2(p):
+    u = case_unit(p)
+    if not u:
+        return -math.inf
+    return math.log2(max(float(abs_sum(T).max()) for T in case_terms(p)) / u)
+
+
+def case_old_bar(p):
+    """(median, max) of the old tolerance 1e-5 sum|T| over the case's outputs, in units of u."""
+    u = case_unit(p)
+    bars = np.concatenate([(1e-5 * abs_sum(T) / u).ravel() for T in case_terms(p)]) if u else np.zeros(1)
+    return float(np.median(bars)), float(bars.max())
+
+
+def case_K(c):
+    if c["kind"] == "conv":
+        return c["cfg"]["cin"] // c["cfg"]["g"] * c["cfg"]["k"] ** 2
+    if c["kind"] == "dconv":
+        return c["geo"]["cin"] * c["geo"]["k"] ** 2
+    if c["kind"] in ("ddw", "tbdw"):
+        return 9
+    return c["shape"][1]
+
+
+CASES = {c["id"]: c for c in all_cases()}
+assert len(CASES) == len(all_cases()), "case ids are not unique"
