@@ -28,7 +28,8 @@ SYMBOLS = ("fp8a_version", "fp8a_last_error", "fp8a_fallback_stats", "fp8a_path_
            "fp8a_flag_arena_slot_bytes",
            "fp8a_check_workspace_size", "fp8a_matmul_check", "fp8a_conv2d_check_workspace_size", "fp8a_conv2d_check",
            "fp8a_fp8_mse_workspace_size", "fp8a_fp8_mse_search", "fp8a_fq_selfcheck",
-           "fp8a_bn_train_workspace_size", "fp8a_bn_train", "fp8a_bmm", "fp8a_bmm_stats")
+           "fp8a_bn_train_workspace_size", "fp8a_bn_train", "fp8a_bmm", "fp8a_bmm_stats",
+           "fp8a_bmm_check_workspace_size", "fp8a_bmm_check")
 
 _lib = None
 
@@ -116,6 +117,9 @@ def load():
         "fp8a_bmm": ([P, P, P, I64, I64, I64, I64, I64, I64, I64, I64, I64, I64, I64, I64, I64, I64, I64, I, I, P, P, I64,
                       P, P, U, P], I),
         "fp8a_bmm_stats": ([P, I], I),
+        "fp8a_bmm_check_workspace_size": ([I64, I64, I64, I64, I64], SZ),
+        "fp8a_bmm_check": ([P, P, P, I64, I64, I64, I64, I64, I64, I64, I64, I64, I64, I64, I64, I, I, P, P, I64, P, P, U,
+                            P, P, P, P, SZ, P], I),
     }
     for name, (args, res) in sig.items():
         f = getattr(L, name)

@@ -25,10 +25,10 @@ import torch.nn.functional as F
 from torch import nn
 
 from . import _lib
-from .approx_ops import (_bias_dev, _res_quant_params, approx_bmm, approx_conv2d, approx_conv2d_check, approx_matmul,
-                         approx_matmul_block, approx_matmul_check, bias_epilogue, dense_conv2d, dense_format,
-                         dense_matmul, format_self_check, grouped_conv2d, make_flags, make_flags_v5, qamaa_conv2d,
-                         qamaa_matmul)
+from .approx_ops import (_bias_dev, _res_quant_params, approx_bmm, approx_bmm_check, approx_conv2d,
+                         approx_conv2d_check, approx_matmul, approx_matmul_block, approx_matmul_check, bias_epilogue,
+                         dense_conv2d, dense_format, dense_matmul, format_self_check, grouped_conv2d, make_flags,
+                         make_flags_v5, qamaa_conv2d, qamaa_matmul)
 from .error_tables import get_comp_table_NN_v5, get_error_table_NN, load_error_table
 from .quantization.hijacker import QuantizationHijacker
 from .quantization.quantization_manager import QuantizationManager
@@ -374,8 +374,12 @@ class ApproxMatMulMixin(ApproxOpMixin):
     (``a_quantizer``, ``b_quantizer``: bA, bB), the calibration / original_quantize_res product through
     ``res_quantizer`` (which gives the product its bR), the approx result returned unquantized.
 
-    Not supported here: quantize_after_mult_and_add and approx_version 5 (NotImplementedError);
-    self_check_mode is ignored (no error_report rows for these products)."""
+    custom_approx_params['self_check_mode'] follows the production launch (unchanged, ``out=`` included) with
+    the batched check kernel on the same quantized operands and biases (approx_bmm_check, prod = that result):
+    ``last_self_check`` keeps its CheckStats over all batch items, the reference's block is printed once per
+    forward, and error_report gives the product a ``matmul`` row.
+
+    Not supported here: quantize_after_mult_and_add and approx_version 5 (NotImplementedError)."""
 
     def _init_matmul_quantizers(self):
         mk = dict(qmethod=self.act_method, init=self.act_range_method, qparams=self.act_qparams,
@@ -409,9 +413,12 @@ class ApproxMatMulMixin(ApproxOpMixin):
         if self.res_quantizer_flag and self.approx_flag:
             E, M, table, flags = self._approx_config()
             dev = a.device
-            res = approx_bmm(a.detach(), b.detach(), E, M, self._default_bias(self.a_quantizer.get_fp_bias(), E, dev),
-                             self._default_bias(self.b_quantizer.get_fp_bias(), E, dev),
-                             self._default_bias(self.res_quantizer.get_fp_bias(), E, dev), table, flags=flags, out=out)
+            biases = (self._default_bias(self.a_quantizer.get_fp_bias(), E, dev),
+                      self._default_bias(self.b_quantizer.get_fp_bias(), E, dev),
+                      self._default_bias(self.res_quantizer.get_fp_bias(), E, dev))
+            res = approx_bmm(a.detach(), b.detach(), E, M, *biases, table, flags=flags, out=out)
+            if self._self_check_on():
+                self._self_check(approx_bmm_check, flags, res, a.detach(), b.detach(), E, M, *biases, table)
         self._check_res_flag()
         if res is None:  # (as the hijacker: fixed ranges with no product selected)
             raise UnboundLocalError("local variable 'res' referenced before assignment")

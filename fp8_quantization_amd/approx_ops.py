@@ -24,7 +24,7 @@ from .error_tables import get_error_table_NN  # noqa: F401  (re-exported, v9:555
 __all__ = ["custom_matmul_vectorize", "approx_matmul", "approx_bmm", "approx_matmul_block", "approx_terms", "approx_conv2d", "qamaa_matmul", "qamaa_conv2d",
            "quant_to_fp_any_vectorize_torch", "float_to_fpany_absint_torch", "get_error_table_NN",
            "make_flags", "make_flags_v5", "fp8_fake_quantize", "bn_act_epilogue", "dense_format", "dense_matmul",
-           "dense_conv2d", "grouped_conv2d", "dense_conv2d_fused", "approx_matmul_check", "approx_conv2d_check",
+           "dense_conv2d", "grouped_conv2d", "dense_conv2d_fused", "approx_matmul_check", "approx_conv2d_check", "approx_bmm_check",
            "CheckStats", "format_self_check", "SELF_CHECK_LABELS", "fp8_mse_losses", "bn_train"]
 
 
@@ -529,6 +529,44 @@ def approx_conv2d_check(x, w, E, M, bA, bW, bR, table=None, flags=None, stride=(
     _lib.check(rc, "fp8a_conv2d_check")
     S = ws[:y.numel() * 4].view(torch.float32).view(y.shape)
     return y, G, CheckStats.from_bytes(stats.cpu().numpy().tobytes(), S=S)
+
+
+def approx_bmm_check(A, B, E, M, bA, bB, bR, table=None, flags=None, prod=None, **flag_kwargs):
+    """The fused self-check of one batched product (fp8a_bmm_check): ``(C, G, CheckStats)`` with C, G and
+    ``CheckStats.S`` dense in the product's shape [..., M, N], the statistics over all batch items (every
+    item's A and B counted once).  Operands and biases as approx_bmm: one or two equal leading batch dims,
+    views consumed in place as long as A's k stride is 1.  prod: approx_bmm's result (any float32 tensor of
+    C's shape; made contiguous) to compare C against.  Reads the struct back with one synchronising copy."""
+    if A.dim() not in (3, 4) or A.dim() != B.dim() or A.shape[:-2] != B.shape[:-2] or A.shape[-1] != B.shape[-2]:
+        raise AssertionError(f"approx_bmm_check: shape mismatch {tuple(A.shape)} @ {tuple(B.shape)}")  # v9:20
+    if flags is None:
+        flags = make_flags(**flag_kwargs)
+    L = _lib.load()
+    A, B = _as_f32(A), _as_f32(B)
+    if A.stride(-1) != 1 and A.shape[-1] > 1:
+        A = A.contiguous()
+    dev = A.device
+    nb0, nb1, sa0, sa1 = _bmm_view(A, "A")
+    _, _, sb0, sb1 = _bmm_view(B, "B")
+    Mr, K = A.shape[-2:]
+    N = B.shape[-1]
+    tab = _table_host(table, M, _uses_table(flags))
+    bA_, bB_, bR_ = _bias_dev(bA, dev), _bias_dev(bB, dev), _bias_dev(bR, dev)
+    if bB_.numel() not in (1, N):
+        raise AssertionError(f"approx_bmm_check: {bB_.numel()} column biases for {N} columns")
+    C = torch.empty(tuple(A.shape[:-1]) + (N,), dtype=torch.float32, device=dev)
+    G = torch.empty_like(C)
+    prod = _check_prod(prod, C)
+    stats = torch.empty(CHECK_STATS_BYTES, dtype=torch.uint8, device=dev)
+    ws = _aligned_workspace(dev, L.fp8a_bmm_check_workspace_size(nb0, nb1, Mr, N, K))
+    rc = L.fp8a_bmm_check(_lib.dev_ptr(A), _lib.dev_ptr(B), _lib.dev_ptr(C), nb0, nb1, Mr, N, K,
+                          A.stride(-2), sa0, sa1, B.stride(-2), B.stride(-1), sb0, sb1, int(E), int(M),
+                          _lib.dev_ptr(bA_), _lib.dev_ptr(bB_), 0 if bB_.numel() == 1 else 1, _lib.dev_ptr(bR_),
+                          _lib.host_ptr(tab), int(flags), _lib.dev_ptr(G), _lib.dev_ptr(prod), _lib.dev_ptr(stats),
+                          _lib.dev_ptr(ws), ws.numel(), _lib.stream_ptr(dev))
+    _lib.check(rc, "fp8a_bmm_check")
+    S = ws[:C.numel() * 4].view(torch.float32).view(C.shape)
+    return C, G, CheckStats.from_bytes(stats.cpu().numpy().tobytes(), S=S)
 
 
 def custom_matmul_vectorize(A, B, expo_width, mant_width, custom_bias_A, custom_bias_B, custom_bias_R,

@@ -2076,6 +2076,77 @@ int fp8a_matmul_check(const float *A, int64_t lda, const float *B, int64_t sbk, 
     return run_check(a, c, M * N, table, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
+// fp8a_bmm_check (gemm_bmm_check_kernel): the S image of all items, then one CheckPart per (item, tile).
+// Sizes saturate instead of wrapping, so an absurd extent fails the workspace test, not the arithmetic.
+static size_t bmm_check_ws_bytes(int64_t nb0, int64_t nb1, int64_t M, int64_t N) {
+    int64_t nb, outs, parts;  // (positive extents; 2^56: far above any device, far below a wrap of the sums)
+    if (__builtin_mul_overflow(nb0, nb1, &nb) || __builtin_mul_overflow(nb, M, &outs) ||
+        __builtin_mul_overflow(outs, N, &outs) || outs > (1ll << 56) || M > (1ll << 40) || N > (1ll << 40) ||
+        __builtin_mul_overflow(nb, check_tiles(M, N), &parts) || parts > (1ll << 50))
+        return SIZE_MAX;
+    return align256((size_t)outs * 4) + align256(check_part_bytes(parts));
+}
+
+size_t fp8a_bmm_check_workspace_size(int64_t nb0, int64_t nb1, int64_t M, int64_t N, int64_t K) {
+    if (nb0 <= 0 || nb1 <= 0 || M <= 0 || N <= 0 || K <= 0) return 0;
+    const size_t b = bmm_check_ws_bytes(nb0, nb1, M, N);
+    return b == SIZE_MAX ? 0 : b;
+}
+
+int fp8a_bmm_check(const float *A, const float *B, float *C, int64_t nb0, int64_t nb1, int64_t M, int64_t N, int64_t K,
+                   int64_t lda, int64_t sa0, int64_t sa1, int64_t sbk, int64_t sbn, int64_t sb0, int64_t sb1, int E,
+                   int Mw, const int32_t *bA, const int32_t *bB, int64_t bB_stride, const int32_t *bR,
+                   const int32_t *table, uint32_t flags, float *G, const float *Cprod, fp8a_check_stats *stats,
+                   void *workspace, size_t workspace_bytes, fp8a_stream_t stream) {
+    int rc = check_format(E, Mw);
+    if (rc) return rc;
+    if (nb0 < 0 || nb1 < 0 || M < 0 || N < 0 || K < 0) return fail(FP8A_EINVAL, "fp8a_bmm_check: negative extent");
+    if (lda < 0 || sa0 < 0 || sa1 < 0 || sbk < 0 || sbn < 0 || sb0 < 0 || sb1 < 0)
+        return fail(FP8A_EINVAL, "fp8a_bmm_check: negative stride");
+    if (flags & F_TB)
+        return fail(FP8A_EINVAL, "fp8a_bmm: no tensor-bias semantics (FP8A_TB) for a batched product");
+    if (flags & (F_V5 | F_OFUF | F_OF | F_UF))
+        return fail(FP8A_EINVAL, "fp8a_bmm: the v5 model is not implemented for a batched product");
+    if (flags & ~(F_APPROX | F_S2N | F_QBMA | F_GCLIP)) return fail(FP8A_EINVAL, "fp8a_bmm_check: unknown flag bits");
+    if (bB_stride != 0 && bB_stride != 1) return fail(FP8A_EINVAL, "fp8a_bmm_check: bB_stride must be 0 or 1");
+    if (M > 1 && lda < K) return fail(FP8A_EINVAL, "leading dimension smaller than extent");
+    if (nb0 <= 0 || nb1 <= 0 || M <= 0 || N <= 0 || K <= 0)
+        return fail(FP8A_EINVAL, "self-check extents must be positive");
+    if (!A || !B || !C || !bA || !bB || !bR || !stats) return fail(FP8A_EINVAL, "null pointer");
+    if (workspace == nullptr || (((uintptr_t)workspace) & 255) != 0 ||
+        workspace_bytes < bmm_check_ws_bytes(nb0, nb1, M, N))
+        return fail(FP8A_EINVAL, "self-check workspace missing, misaligned or too small");
+    if ((((uintptr_t)stats) & 7) != 0) return fail(FP8A_EINVAL, "stats must be 8-byte aligned");
+    // (the workspace test bounds nb0 nb1 M N: no product below wraps)
+    const int64_t nb = nb0 * nb1, tiles = check_tiles(M, N);
+    if (tiles > 0x7FFFFFFFll / nb) return fail(FP8A_EINVAL, "self-check grid too large");
+    BmmCheckArgs a;
+    memset(&a, 0, sizeof(a));
+    int mode;
+    rc = pack_table(table, Mw, (flags & F_APPROX) != 0, a.tab, mode);
+    if (rc) return rc;
+    // a diagnostic, not for graphs; a query that fails is an error of its own (never FP8A_OK)
+    hipStream_t s = (hipStream_t)stream;
+    const int cap = stream_capturing(s);
+    if (cap < 0) {
+        rc = hip_check("fp8a self-check: stream capture query");
+        return rc ? rc : fail(FP8A_EHIP, "fp8a self-check: the stream capture query failed");
+    }
+    if (cap) return fail(FP8A_EINVAL, "the self-check does not run on a capturing stream");
+    a.A = A; a.B = B; a.C = C; a.G = G; a.Cprod = Cprod;
+    a.S = (float *)workspace;
+    a.part = (CheckPart *)((char *)workspace + align256((size_t)(nb * M * N) * 4));
+    a.nb1 = nb1; a.M = M; a.N = N; a.K = K;
+    a.lda = lda; a.sa0 = sa0; a.sa1 = sa1; a.sbk = sbk; a.sbn = sbn; a.sb0 = sb0; a.sb1 = sb1;
+    a.tiles_n = (N + CK_BN - 1) / CK_BN;
+    a.tiles = tiles;
+    a.E = E; a.Mw = Mw; a.bA = bA; a.bB = bB; a.bBs = bB_stride; a.bR = bR; a.flags = flags;
+    CheckArgs c{};
+    c.Cprod = Cprod; c.stats = stats; c.part = a.part; c.groups = (int)nb;
+    launch_bmm_check(a, c, nb, s);
+    return hip_check("fp8a self-check launch");
+}
+
 size_t fp8a_conv2d_check_workspace_size(int64_t Bn, int64_t Cin, int64_t H, int64_t W, int64_t Cout, int kh, int kw,
                                         int sh, int sw, int ph, int pw, int dh, int dw, int groups) {
     ConvShape c{Bn, Cin, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, groups};

@@ -42,6 +42,7 @@ void launch_v5mx(const GemmArgs &a, hipStream_t s);
 
 // k_check.hip: the fused self-check (gemm_check.h) -- gemm_check_kernel over (64 x 64 tiles, groups)
 // and its one-workgroup stats reduction; check_part_bytes = the workspace bytes of `parts` workgroups.
+// (The batched form's launcher, launch_bmm_check, is declared with its arguments in gemm_check.h.)
 struct CheckArgs;
 void launch_check(const GemmArgs &a, const CheckArgs &c, hipStream_t s);
 size_t check_part_bytes(int64_t parts);

@@ -3,16 +3,19 @@
 ``layer_error_report(model, x)`` switches custom_approx_params['self_check_mode'] on for every
 approx layer of a calibrated (fixed-range) model, runs one eager forward -- every layer then runs
 unfused and follows its production launch with the fused check kernel on the same quantized
-operands (approx_ops.approx_matmul_check / approx_conv2d_check) -- and returns one row per layer:
+operands (approx_ops.approx_matmul_check / approx_conv2d_check, approx_bmm_check for QCustomMatMul's
+batched products) -- and returns one row per layer:
 the max / mean / RMSE of |golden - approx| (approx_matmul_whole_v9.py:145-157), the SQNR of the
 approx sum against the golden one, the shares of normal values in A, B and the product tensor, and
 the production kernel's distance from the literal check kernel in units of the project's 1e-5 S bar.
 
     python -m fp8_quantization_amd.error_report --arch resnet18 --batch 16 [--size 224] [--json]
-                                                [--error-table FILE]
+                                                [--error-table FILE] [--approx-attention]
 
 builds the synthetic calibrated workload of the benchmark's workload modules (random weights, BN
 statistics estimated on synthetic batches, one calibration batch, fixed ranges) and prints the table.
+--approx-attention (--arch vit_b16 only) also sends attention's QK^T and PV through the multiplier: two
+``matmul`` rows per encoder layer.
 """
 import argparse
 import contextlib
@@ -22,7 +25,7 @@ import math
 
 import torch
 
-from .approx_calculation import ApproxConv2dMixin, ApproxOpMixin
+from .approx_calculation import ApproxConv2dMixin, ApproxMatMulMixin, ApproxOpMixin
 
 __all__ = ["layer_error_report", "format_report", "build_workload", "main"]
 
@@ -37,7 +40,14 @@ def approx_layers(model):
 
 
 def _row(name, mod, st):
-    if isinstance(mod, ApproxConv2dMixin):
+    batch = None
+    if isinstance(mod, ApproxMatMulMixin):
+        # a batched activation x activation product: the (M, N, K) of one item, `batch` items (S: [..., M, N])
+        kind, groups = "matmul", 1
+        M, N = st.S.shape[-2:]
+        batch = st.n_out // (M * N)
+        K = st.a_total // (batch * M)
+    elif isinstance(mod, ApproxConv2dMixin):
         kind = "conv"
         N = mod.out_channels // mod.groups
         K = (mod.in_channels // mod.groups) * mod.kernel_size[0] * mod.kernel_size[1]
@@ -48,17 +58,21 @@ def _row(name, mod, st):
         N, K, groups = mod.out_features, mod.in_features, 1
         M = st.n_out // N
     pct = lambda v: None if v is None else float(v)  # noqa: E731
-    return dict(name=name, kind=kind, shape=(int(M), int(N), int(K)), groups=int(groups), macs=int(st.n_out) * int(K),
-                max=float(st.max_err), mean=float(st.mean), rmse=float(st.rmse), sqnr_db=float(st.sqnr_db),
-                a_norm_pct=pct(st.a_norm_pct), b_norm_pct=pct(st.b_norm_pct), r_norm_pct=pct(st.r_norm_pct),
-                prod_max_rel=float(st.prod_max_rel) / BAR)
+    row = dict(name=name, kind=kind, shape=(int(M), int(N), int(K)), groups=int(groups), macs=int(st.n_out) * int(K),
+               max=float(st.max_err), mean=float(st.mean), rmse=float(st.rmse), sqnr_db=float(st.sqnr_db),
+               a_norm_pct=pct(st.a_norm_pct), b_norm_pct=pct(st.b_norm_pct), r_norm_pct=pct(st.r_norm_pct),
+               prod_max_rel=float(st.prod_max_rel) / BAR)
+    if batch is not None:
+        row["batch"] = int(batch)
+    return row
 
 
 def layer_error_report(model, x, quiet=True):
     """One eager forward of ``model`` on ``x`` with the self-check on in every approx layer; returns
     the rows (dicts: name, kind, shape (M, N, K), groups, macs, max, mean, rmse, sqnr_db,
     a_norm_pct, b_norm_pct, r_norm_pct -- None with with_s2nn2s_opt --, prod_max_rel in units of
-    1e-5).  Every layer's self_check_mode is restored afterwards.  quiet: swallow the per-launch
+    1e-5; a ``matmul`` row -- QCustomMatMul -- has the shape of one batch item and a ``batch`` key
+    with the number of items).  Every layer's self_check_mode is restored afterwards.  quiet: swallow the per-launch
     blocks the layers print.  A diagnostic, not for HIP graphs: raises RuntimeError on a capturing
     stream."""
     if x.is_cuda and torch.cuda.is_current_stream_capturing():
@@ -97,10 +111,13 @@ def format_report(rows):
     return "\n".join(out)
 
 
-def build_workload(arch, size, cfg, bn_stats_batches=4, cal_batch=64, device="cuda"):
+def build_workload(arch, size, cfg, bn_stats_batches=4, cal_batch=64, device="cuda", approx_attention=False):
     """The benchmark's synthetic calibrated workload: the arch's workload module (random weights, BN
     statistics estimated on the CPU from synthetic batches), one synthetic calibration batch, fixed
-    ranges.  Returns the model on ``device`` in eval mode."""
+    ranges.  approx_attention (vit_b16 only): QK^T and PV through the multiplier as well.  Returns the
+    model on ``device`` in eval mode."""
+    if approx_attention and arch != "vit_b16":
+        raise ValueError(f"approx_attention needs arch 'vit_b16', got {arch!r}")
     from . import resnet_workload as rw
     bn = dict(bn_stats_batches=bn_stats_batches, device=torch.device("cpu"))
     if arch in ("resnet18", "resnet50"):
@@ -113,7 +130,7 @@ def build_workload(arch, size, cfg, bn_stats_batches=4, cal_batch=64, device="cu
         model = mobilenet_v2_approx(input_size=size, **bn, **cfg)
     elif arch == "vit_b16":
         from .vit_workload import vit_b16_approx
-        model = vit_b16_approx(image_size=size, **cfg)
+        model = vit_b16_approx(image_size=size, approx_attention=approx_attention, **cfg)
     else:
         raise ValueError(f"unknown arch {arch!r}")
     model = model.to(device).eval()
@@ -141,7 +158,11 @@ def main(argv=None):
     ap.add_argument("--bn-stats-batches", type=int, default=4)
     ap.add_argument("--error-table", default=None, metavar="FILE",
                     help="a custom error table (.npy or text rows) in place of the built-in one")
+    ap.add_argument("--approx-attention", action="store_true",
+                    help="--arch vit_b16: QK^T and PV through the multiplier too (two matmul rows per layer)")
     args = ap.parse_args(argv)
+    if args.approx_attention and args.arch != "vit_b16":
+        ap.error("--approx-attention needs --arch vit_b16")
     cfg = dict(expo_width=args.expo_width, mant_width=args.mant_width, dnsmp_factor=3, withComp=args.with_comp,
                with_approx=True, with_s2nn2s_opt=not args.no_s2n, quant_btw_mult_accu=True)
     digest = None
@@ -149,7 +170,8 @@ def main(argv=None):
         from .error_tables import load_error_table, table_digest
         cfg["error_table"] = load_error_table(args.error_table, args.mant_width)
         digest = table_digest(cfg["error_table"])
-    model = build_workload(args.arch, args.size, cfg, args.bn_stats_batches, args.cal_batch)
+    model = build_workload(args.arch, args.size, cfg, args.bn_stats_batches, args.cal_batch,
+                           approx_attention=args.approx_attention)
     g = torch.Generator(device="cpu").manual_seed(10)
     x = torch.randn((args.batch, 3, args.size, args.size), generator=g).to("cuda")
     rows = layer_error_report(model, x)

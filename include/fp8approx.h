@@ -380,6 +380,40 @@ int fp8a_conv2d_check(const float *x, const float *w, float *y, int64_t Bn, int6
                       size_t workspace_bytes, fp8a_stream_t stream);
 
 /*
+ * fp8a_bmm_check: the fused self-check of the batched product.  A and B are addressed as fp8a_bmm
+ * addresses them (two batch strides per operand: head views of [B, S, H*d] buffers and a transposed
+ * K are read in place); C, G (NULL, or C's layout), Cprod (NULL, or a production result) and S are
+ * dense [nb0][nb1][M][N].  Per output the three fp32 sums of fp8a_matmul_check in the same k order,
+ * the K tail not padded; the v9 term with int biases -- bA, bR device int32 [1], bB device int32
+ * with bB_stride 0 (shared) or 1 (per column n), the same for every item; every format, table
+ * (custom ones included) and APPROX / S2N / QBMA / GCLIP combination.  *stats (DEVICE memory) is
+ * over the whole call: n_out = nb M N, a_total = nb M K, b_total = nb K N, r_total = nb M K N
+ * (nb = nb0 nb1; r_norm = r_total = 0 with FP8A_S2N), every item's A and B counted once.  One part
+ * per workgroup (64 x 64 tile of one item), summed by one workgroup in a fixed order, no
+ * floating-point atomics: two calls give identical bytes.
+ * workspace: at least fp8a_bmm_check_workspace_size(nb0, nb1, M, N, K) bytes =
+ * align256(4 nb M N) + align256(64 nb tiles), tiles = ceil(M / 64) ceil(N / 64), 256-byte aligned;
+ * S sits at its head.  The size query is host-only and returns 0 for any non-positive extent.
+ * Checked in this order, all before any HIP call: the format (FP8A_EFORMAT); then, FP8A_EINVAL
+ * each: negative extents or strides; FP8A_TB and the v5 flags (as fp8a_bmm); unknown flag bits;
+ * bB_stride not 0 or 1; lda < K with M > 1; non-positive extents (the self-check has no
+ * empty-extent form); null A, B, C, bA, bB, bR or stats; workspace null, not 256-byte aligned or
+ * too small; stats not 8-byte aligned; more than 2^31 - 1 workgroups.  A diagnostic, not for HIP
+ * graphs: on a capturing stream it returns FP8A_EINVAL before launching anything, and a failed
+ * capture query is FP8A_EHIP, never FP8A_OK.  Asynchronous, allocates nothing and never
+ * synchronises the host.
+ */
+size_t fp8a_bmm_check_workspace_size(int64_t nb0, int64_t nb1, int64_t M, int64_t N, int64_t K);
+int fp8a_bmm_check(const float *A, const float *B, float *C,
+                   int64_t nb0, int64_t nb1, int64_t M, int64_t N, int64_t K,
+                   int64_t lda, int64_t sa0, int64_t sa1,
+                   int64_t sbk, int64_t sbn, int64_t sb0, int64_t sb1,
+                   int E, int Mw, const int32_t *bA, const int32_t *bB, int64_t bB_stride,
+                   const int32_t *bR, const int32_t *table, uint32_t flags,
+                   float *G, const float *Cprod, fp8a_check_stats *stats,
+                   void *workspace, size_t workspace_bytes, fp8a_stream_t stream);
+
+/*
  * Replaces QCustomBNConv2dTorch.run_forward (approx_calculation.py:822-917) minus the conv
  * bias: x NCHW [Bn, Cin, H, W], w [Cout, Cin/groups, kh, kw], y NCHW [Bn, Cout, Ho, Wo].
  * bW: device int32 per output channel (weight_quantizer.custom_bias).  Groups whose output

@@ -32,15 +32,20 @@ def resources(lib):
             t.write(co)
             t.flush()
             notes = subprocess.run([READOBJ, "--notes", t.name], capture_output=True, text=True).stdout
-        cur = None
+        # a kernel's entry opens with "  - " and lists its keys in alphabetical order: the ones before
+        # .name wait in `pend` (an argument's own "- " sits deeper)
+        cur, pend = None, {}
         for line in notes.splitlines():
+            if re.match(r"\s{1,3}-\s", line):
+                cur, pend = None, {}
             m = re.match(r"\s*-?\s*\.name:\s+(\S+)", line)
-            if m:
+            if m and line.startswith("    ."):
                 cur = out.setdefault(m.group(1), {})
+                cur.update(pend)
                 continue
             m = re.match(r"\s*-?\s*(\.\w+):\s+(\d+)\s*$", line)
-            if m and cur is not None and m.group(1) in KEYS:
-                cur[m.group(1)] = int(m.group(2))
+            if m and m.group(1) in KEYS:
+                (pend if cur is None else cur)[m.group(1)] = int(m.group(2))
     return out
 
 
