@@ -29,7 +29,7 @@ SYMBOLS = ("fp8a_version", "fp8a_last_error", "fp8a_fallback_stats", "fp8a_path_
            "fp8a_check_workspace_size", "fp8a_matmul_check", "fp8a_conv2d_check_workspace_size", "fp8a_conv2d_check",
            "fp8a_fp8_mse_workspace_size", "fp8a_fp8_mse_search", "fp8a_fq_selfcheck",
            "fp8a_bn_train_workspace_size", "fp8a_bn_train", "fp8a_bmm", "fp8a_bmm_stats",
-           "fp8a_bmm_check_workspace_size", "fp8a_bmm_check")
+           "fp8a_bmm_check_workspace_size", "fp8a_bmm_check", "fp8a_grad_bmm", "fp8a_grad_stats")
 
 _lib = None
 
@@ -120,6 +120,8 @@ def load():
         "fp8a_bmm_check_workspace_size": ([I64, I64, I64, I64, I64], SZ),
         "fp8a_bmm_check": ([P, P, P, I64, I64, I64, I64, I64, I64, I64, I64, I64, I64, I64, I64, I, I, P, P, I64, P, P, U,
                             P, P, P, P, SZ, P], I),
+        "fp8a_grad_bmm": ([P, P, P] + [I64] * 16 + [P], I),
+        "fp8a_grad_stats": ([P, I], I),
     }
     for name, (args, res) in sig.items():
         f = getattr(L, name)
@@ -267,6 +269,15 @@ def bmm_stats(reset=False):
     L = load()
     out = (ctypes.c_uint64 * 3)()
     check(L.fp8a_bmm_stats(ctypes.cast(out, ctypes.c_void_p), 1 if reset else 0), "fp8a_bmm_stats")
+    return dict(launches=int(out[0]), tiles=int(out[1]), recomputed=int(out[2]))
+
+
+def grad_stats(reset=False):
+    """fp8a_grad_stats: dict(launches, tiles, recomputed) -- fp8a_grad_bmm launches and their 64 x 64 output
+    tiles (host-side counters) and the tiles recomputed in fp32 (synchronises the device)."""
+    L = load()
+    out = (ctypes.c_uint64 * 3)()
+    check(L.fp8a_grad_stats(ctypes.cast(out, ctypes.c_void_p), 1 if reset else 0), "fp8a_grad_stats")
     return dict(launches=int(out[0]), tiles=int(out[1]), recomputed=int(out[2]))
 
 

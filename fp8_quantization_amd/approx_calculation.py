@@ -28,11 +28,11 @@ from . import _lib
 from .approx_ops import (_bias_dev, _res_quant_params, approx_bmm, approx_bmm_check, approx_conv2d,
                          approx_conv2d_check, approx_matmul, approx_matmul_block, approx_matmul_check, bias_epilogue,
                          dense_conv2d, dense_format, dense_matmul, format_self_check, grouped_conv2d, make_flags,
-                         make_flags_v5, qamaa_conv2d, qamaa_matmul)
+                         make_flags_v5, qamaa_conv2d, qamaa_matmul, ste_bmm, ste_conv2d, ste_linear)
 from .error_tables import get_comp_table_NN_v5, get_error_table_NN, load_error_table
 from .quantization.hijacker import QuantizationHijacker
 from .quantization.quantization_manager import QuantizationManager
-from .quantization.base_quantized_classes import QuantizedActivation, QuantizedModule
+from .quantization.base_quantized_classes import QuantizedActivation, QuantizedModule, sync_ste
 from .quantization.hijacker import activations_set
 from .quantization.quantized_folded_bn import BNFusedHijacker
 from .chain import ChainConsumerMixin
@@ -123,6 +123,13 @@ class ApproxOpMixin:
         self.last_self_check = stats
         print(format_self_check(stats, flags))
 
+    def _ste_on(self):
+        """custom_approx_params['ste_backward'] (opt-in, default off) with autograd recording: the layer then
+        runs unfused, as under the self-check -- quantizer Functions, the product as a Function whose
+        backward is the exact product's on the gradient GEMM (approx_ops.ste_*), BN / activation / tail in
+        torch.  approx_version 5 and quantize_after_mult_and_add raise NotImplementedError with the switch."""
+        return sync_ste(self)
+
     def approx_multiply(self, x, y, x_bias, y_bias, res_bias):
         """x [M, K] @ y [K, N] with the operator's approx configuration."""
         E, M, table, flags = self._approx_config()
@@ -187,11 +194,11 @@ class ApproxConv2dMixin(ApproxOpMixin, ChainConsumerMixin):
     # product before BN / activation / tail)
     @property
     def supports_bn_act_epilogue(self):
-        return not self._self_check_on()
+        return not self._self_check_on() and not self._ste_on()
 
     @property
     def supports_input_quant_fusion(self):
-        return not self._self_check_on()
+        return not self._self_check_on() and not self._ste_on()
 
     def run_forward(self, x, weight, bias, offsets=None, epilogue=None, qin=None, post=None, chain=None):
         """qin: the layer's input FPQuantizer when the hijacker fused it (x unquantized; the op
@@ -235,8 +242,13 @@ class ApproxConv2dMixin(ApproxOpMixin, ChainConsumerMixin):
                 if ch is not None:
                     chain.done(ch)
             else:
-                out = approx_conv2d(x.detach(), weight.detach(), E, M, self._default_bias(a_bias, E, x.device),
-                                    w_bias, self._default_bias(r_bias, E, x.device), table, **args)
+                a_b, r_b = self._default_bias(a_bias, E, x.device), self._default_bias(r_bias, E, x.device)
+                if self._ste_on():  # the same launch, recorded with the straight-through backward
+                    out = ste_conv2d(x, weight, lambda xq, wq: approx_conv2d(xq, wq, E, M, a_b, w_bias, r_b, table,
+                                                                             **args),
+                                     self.stride, self.padding, self.dilation, self.groups)
+                else:
+                    out = approx_conv2d(x.detach(), weight.detach(), E, M, a_b, w_bias, r_b, table, **args)
                 if self._self_check_on():
                     self._self_check(approx_conv2d_check, flags, out, x.detach(), weight.detach(), E, M,
                                      self._default_bias(a_bias, E, x.device), w_bias,
@@ -306,7 +318,7 @@ class ApproxLinearMixin(ApproxOpMixin):
         b = getattr(self, "bias", None)
         return (self.fuse_linear_block and self.approx_flag and self.out_features != 1 and not self._self_check_on()
                 and p.get("approx_version", 9) != 5 and self.get_weights_fp_bias() is not None
-                and not (b is not None and b.requires_grad and torch.is_grad_enabled()))
+                and not self._ste_on() and not (b is not None and b.requires_grad and torch.is_grad_enabled()))
 
     def tail_ok(self):
         """Whether forward(x, post=...) fuses a caller's residual tail: the fixed-range eval
@@ -357,8 +369,11 @@ class ApproxLinearMixin(ApproxOpMixin):
         else:
             if qin is not None or post is not None:
                 raise AssertionError("fused input quantization / tail without the fused linear launch")
-            out = self.approx_multiply(x.detach(), weight.detach().t(), self.get_acts_fp_bias(),
-                                       self.get_weights_fp_bias(), self.get_res_fp_bias())
+            biases = (self.get_acts_fp_bias(), self.get_weights_fp_bias(), self.get_res_fp_bias())
+            if self._ste_on() and self.approx_flag:  # the same launch, recorded with the straight-through backward
+                out = ste_linear(x, weight, lambda xq, wq: self.approx_multiply(xq, wq.t(), *biases))
+            else:
+                out = self.approx_multiply(x.detach(), weight.detach().t(), *biases)
             if bias is not None:
                 out += bias
         if lead is not None:
@@ -402,6 +417,7 @@ class ApproxMatMulMixin(ApproxOpMixin):
         """a [..., M, K] @ b [..., K, N] (any views: heads cut from [B, S, H*d], a transposed b); out: None, or
         the view (unit n stride) that receives the product."""
         self._check_supported()
+        self._ste_on()  # (the quantizers below learn the layer's ste_backward switch)
         if self._qa():
             a = self.a_quantizer(a)
             b = self.b_quantizer(b)
@@ -416,7 +432,11 @@ class ApproxMatMulMixin(ApproxOpMixin):
             biases = (self._default_bias(self.a_quantizer.get_fp_bias(), E, dev),
                       self._default_bias(self.b_quantizer.get_fp_bias(), E, dev),
                       self._default_bias(self.res_quantizer.get_fp_bias(), E, dev))
-            res = approx_bmm(a.detach(), b.detach(), E, M, *biases, table, flags=flags, out=out)
+            if self._ste_on():  # the same launch, recorded with the straight-through backward; out is
+                # filled by the (differentiable) copy below
+                res = ste_bmm(a, b, lambda aq, bq: approx_bmm(aq, bq, E, M, *biases, table, flags=flags))
+            else:
+                res = approx_bmm(a.detach(), b.detach(), E, M, *biases, table, flags=flags, out=out)
             if self._self_check_on():
                 self._self_check(approx_bmm_check, flags, res, a.detach(), b.detach(), E, M, *biases, table)
         self._check_res_flag()

@@ -25,7 +25,8 @@ __all__ = ["custom_matmul_vectorize", "approx_matmul", "approx_bmm", "approx_mat
            "quant_to_fp_any_vectorize_torch", "float_to_fpany_absint_torch", "get_error_table_NN",
            "make_flags", "make_flags_v5", "fp8_fake_quantize", "bn_act_epilogue", "dense_format", "dense_matmul",
            "dense_conv2d", "grouped_conv2d", "dense_conv2d_fused", "approx_matmul_check", "approx_conv2d_check", "approx_bmm_check",
-           "CheckStats", "format_self_check", "SELF_CHECK_LABELS", "fp8_mse_losses", "bn_train"]
+           "CheckStats", "format_self_check", "SELF_CHECK_LABELS", "fp8_mse_losses", "bn_train", "grad_bmm",
+           "ste_linear", "ste_bmm", "ste_conv2d"]
 
 
 def make_flags(with_approx=True, with_s2nn2s_opt=False, quant_btw_mult_accu=True, golden_clip_OF=False,
@@ -1300,7 +1301,8 @@ class MaxPool2d(nn.Module):
         return m
 
     def forward(self, x):
-        if x.dtype != torch.float32 or x.dim() != 4 or not x.is_cuda:
+        # (an input that autograd records -- a layer under ste_backward -- pools on torch: the kernel has no backward)
+        if x.dtype != torch.float32 or x.dim() != 4 or not x.is_cuda or (x.requires_grad and torch.is_grad_enabled()):
             return nn.functional.max_pool2d(x, self.kernel_size, self.stride, self.padding)
         return _max_pool2d_op(x, self.kernel_size, self.stride, self.padding)
 
@@ -1340,6 +1342,204 @@ class AvgPool2d(nn.AvgPool2d):
         pair = lambda v: [int(v), int(v)] if isinstance(v, int) else [int(t) for t in v]  # noqa: E731
         k, s = pair(self.kernel_size), pair(self.stride)
         if (x.dtype == torch.float32 and x.dim() == 4 and x.is_cuda and k[0] <= x.shape[2] < k[0] + s[0]
+                and not (x.requires_grad and torch.is_grad_enabled())  # (recorded by autograd: torch's pooling)
                 and k[1] <= x.shape[3] < k[1] + s[1] and x.shape[2] * x.shape[3] <= 4096):
             return _avg_pool2d_plane_op(x, k, s)
         return super().forward(x)
+
+
+# ----------------------------------------------------------------------------------- STE backward
+# finetune.py sets this to a dict to time the backward's parts with HIP events on the current stream:
+# name ("grad_gemm", "im2col", "fold") -> [(start_event, end_event), ...].  None = no instrumentation.
+_STE_PROFILE = None
+
+
+class _ste_timed:
+    def __init__(self, name):
+        self.name = name
+
+    def __enter__(self):
+        self.start = None
+        if _STE_PROFILE is not None:
+            self.start = torch.cuda.Event(enable_timing=True)
+            self.start.record()
+
+    def __exit__(self, *exc):
+        if self.start is not None and _STE_PROFILE is not None:
+            end = torch.cuda.Event(enable_timing=True)
+            end.record()
+            _STE_PROFILE.setdefault(self.name, []).append((self.start, end))
+        return False
+
+
+def _grad_batch(t, nd, what):
+    """(n0, n1, s0, s1) of the leading batch dims of a view with nd trailing matrix dims."""
+    b = t.dim() - nd
+    if b == 0:
+        return 1, 1, 0, 0
+    if b == 1:
+        return 1, t.shape[0], 0, t.stride(0)
+    if b == 2:
+        return t.shape[0], t.shape[1], t.stride(0), t.stride(1)
+    raise AssertionError(f"grad_bmm: {what} has more than two leading batch dims: {tuple(t.shape)}")
+
+
+def _grad_launch(A, B, C, nb, M, N, K0, K1, oa, ob, oc, sa, sb, sc):
+    """One fp8a_grad_bmm launch; oa / ob / oc: element offsets of the first batch item, sa / sb / sc the
+    operands' (batch, ...) element strides."""
+    L = _lib.load()
+    ptr = lambda t, o: ctypes.c_void_p(t.data_ptr() + 4 * o)  # noqa: E731
+    with _ste_timed("grad_gemm"):
+        rc = L.fp8a_grad_bmm(ptr(A, oa), ptr(B, ob), ptr(C, oc), nb, M, N, K0, K1, *sa, *sb, *sc,
+                             _lib.stream_ptr(A.device))
+    _lib.check(rc, "fp8a_grad_bmm")
+
+
+def grad_bmm(A, B, out=None, k2=False):
+    """The gradient GEMM (fp8a_grad_bmm, csrc/gemm_grad.h): C[..., m, n] = sum_k A[..., m, k] B[..., k, n] as an
+    exact fp32 product on the bf16 matrix core -- A any float32 (a gradient), B a bf16-exact operand (a saved
+    FP8-quantized forward operand; anything else is still summed correctly, on the kernel's fp32 path).
+
+    A [..., M, K] and B [..., K, N] float32 device views with the same zero, one or two leading batch dims, or
+    with k2 the two-level reduction A [..., M, K0, K1], B [..., K0, K1, N] (a convolution's weight gradient
+    reduces over (image, pixel) this way).  Views are read in place whatever their strides (expand() gives a
+    broadcast operand its zero stride); out: None, or the float32 view of [..., M, N] that receives C (any
+    positive strides: a transposed view is written through its strides), not overlapping A or B.  Two batch
+    dims that do not collapse into one stride in every operand run one launch per index of the shorter one."""
+    nk = 2 if k2 else 1
+    if A.dim() < 1 + nk or B.dim() != A.dim() or A.shape[:-1 - nk] != B.shape[:-1 - nk] or \
+            A.shape[-nk:] != B.shape[-1 - nk:-1]:
+        raise AssertionError(f"grad_bmm: shape mismatch {tuple(A.shape)} @ {tuple(B.shape)}")
+    A, B = _as_f32(A), _as_f32(B)
+    if not A.is_cuda or B.device != A.device:
+        raise RuntimeError("fp8approx kernels need HIP device tensors (no CPU fallback)")
+    batch = tuple(A.shape[:-1 - nk])
+    M, N = A.shape[-1 - nk], B.shape[-1]
+    K0, K1 = (A.shape[-2], A.shape[-1]) if k2 else (1, A.shape[-1])
+    shape = batch + (M, N)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=A.device)
+    elif tuple(out.shape) != shape or out.dtype != torch.float32 or out.device != A.device:
+        raise AssertionError(f"grad_bmm: out must be a float32 {shape} view on {A.device}")
+    n0, n1, a0, a1 = _grad_batch(A, 1 + nk, "A")
+    _, _, b0, b1 = _grad_batch(B, 1 + nk, "B")
+    _, _, c0, c1 = _grad_batch(out, 2, "out")
+    sa = (A.stride(-1 - nk), A.stride(-2) if k2 else 0, A.stride(-1))
+    sb = (B.stride(-3) if k2 else 0, B.stride(-2), B.stride(-1))
+    sc = (out.stride(-2), out.stride(-1))
+    if n0 == 1 or n1 == 1 or all(s0 == n1 * s1 for s0, s1 in ((a0, a1), (b0, b1), (c0, c1))):
+        # one batch stride per operand
+        one = lambda s0, s1: s0 if n1 == 1 else s1  # noqa: E731
+        _grad_launch(A, B, out, n0 * n1, M, N, K0, K1, 0, 0, 0, (one(a0, a1), *sa), (one(b0, b1), *sb),
+                     (one(c0, c1), *sc))
+    elif n0 <= n1:
+        for i in range(n0):
+            _grad_launch(A, B, out, n1, M, N, K0, K1, i * a0, i * b0, i * c0, (a1, *sa), (b1, *sb), (c1, *sc))
+    else:
+        for i in range(n1):
+            _grad_launch(A, B, out, n0, M, N, K0, K1, i * a1, i * b1, i * c1, (a0, *sa), (b0, *sb), (c0, *sc))
+    return out
+
+
+class _LinearSTE(torch.autograd.Function):
+    """y = launch(xq, wq) (the approx product of xq [R, K] and wq [N, K], unchanged); backward the
+    straight-through estimator: the exact product's gradients dX = dY Wq, dW = dY^T Xq."""
+
+    @staticmethod
+    def forward(ctx, xq, wq, launch):
+        ctx.save_for_backward(xq, wq)
+        return launch(xq, wq)
+
+    @staticmethod
+    def backward(ctx, dy):
+        xq, wq = ctx.saved_tensors
+        dx = grad_bmm(dy, wq) if ctx.needs_input_grad[0] else None
+        dw = grad_bmm(dy.t(), xq) if ctx.needs_input_grad[1] else None
+        return dx, dw, None
+
+
+class _BmmSTE(torch.autograd.Function):
+    """c = launch(aq, bq) (the batched approx product, unchanged); backward dA = dC Bq^T and dB = Aq^T dC, the
+    latter as dB^T = dC^T Aq written through dB's transposed strides, so the gradient is the A operand of
+    both products."""
+
+    @staticmethod
+    def forward(ctx, aq, bq, launch):
+        ctx.save_for_backward(aq, bq)
+        return launch(aq, bq)
+
+    @staticmethod
+    def backward(ctx, dc):
+        aq, bq = ctx.saved_tensors
+        da = db = None
+        if ctx.needs_input_grad[0]:
+            da = grad_bmm(dc, bq.transpose(-1, -2))
+        if ctx.needs_input_grad[1]:
+            db = torch.empty(bq.shape, dtype=torch.float32, device=bq.device)
+            grad_bmm(dc.transpose(-1, -2), aq, out=db.transpose(-1, -2))
+        return da, db, None
+
+
+class _Conv2dSTE(torch.autograd.Function):
+    """y = launch(xq, wq) (the approx convolution, unchanged); backward the exact convolution's gradients on
+    the gradient GEMM.  The saved input goes through fp8a_im2col once ([Bn L, Cin kh kw], L = Ho Wo);
+    dW[g] = sum over (image, pixel) of dY[:, g] cols[:, g] is one launch with the groups as the batch index and
+    the two-level K = (image, pixel); dXcol[b, g] = Wq[g]^T dY[b, g] is written straight into F.fold's
+    [Bn, Cin kh kw, L] layout (one launch for groups = 1; grouped: one per image or per group, whichever is
+    fewer) and F.fold scatters it back.  Transient memory: the im2col image and dXcol, each kh kw times the
+    input (9x for a 3 x 3 convolution).  Single-output-channel groups get the same exact gradient: the
+    tensor-bias semantics (F5) are a quirk of the forward product only."""
+
+    @staticmethod
+    def forward(ctx, xq, wq, launch, stride, padding, dilation, groups):
+        ctx.save_for_backward(xq, wq)
+        ctx.geo = (tuple(stride), tuple(padding), tuple(dilation), int(groups))
+        return launch(xq, wq)
+
+    @staticmethod
+    def backward(ctx, dy):
+        xq, wq = ctx.saved_tensors
+        stride, padding, dilation, G = ctx.geo
+        Bn, Cin, H, W = xq.shape
+        Cout, Cg, kh, kw = wq.shape
+        dy = _as_f32(dy).contiguous()
+        Ln = dy.shape[2] * dy.shape[3]
+        Og, Kg = Cout // G, Cg * kh * kw
+        dyg = dy.view(Bn, G, Og, Ln)
+        dx = dw = None
+        if ctx.needs_input_grad[1]:
+            L = _lib.load()
+            x = xq.contiguous()
+            cols = torch.empty((Bn, Ln, G, Kg), dtype=torch.float32, device=x.device)
+            with _ste_timed("im2col"):
+                rc = L.fp8a_im2col(_lib.dev_ptr(x), _lib.dev_ptr(cols), Bn, Cin, H, W, kh, kw, stride[0], stride[1],
+                                   padding[0], padding[1], dilation[0], dilation[1], _lib.stream_ptr(x.device))
+            _lib.check(rc, "fp8a_im2col")
+            dw = torch.empty((G, Og, Kg), dtype=torch.float32, device=x.device)
+            # A [G, Og, Bn, L] (the gradient), B [G, Bn, L, Kg] (the im2col image)
+            grad_bmm(dyg.permute(1, 2, 0, 3), cols.permute(2, 0, 1, 3), out=dw, k2=True)
+            del cols
+            dw = dw.view(wq.shape)
+        if ctx.needs_input_grad[0]:
+            w = wq.contiguous().view(G, Og, Kg)
+            dxcol = torch.empty((Bn, G, Kg, Ln), dtype=torch.float32, device=dy.device)
+            # C^T [Bn, G, L, Kg] = A [Bn, G, L, Og] (the gradient, pixels as rows) @ B [G, Og, Kg]
+            grad_bmm(dyg.transpose(-1, -2), w.unsqueeze(0).expand(Bn, G, Og, Kg), out=dxcol.transpose(-1, -2))
+            with _ste_timed("fold"):
+                dx = torch.nn.functional.fold(dxcol.view(Bn, G * Kg, Ln), (H, W), (kh, kw), dilation, padding, stride)
+        return dx, dw, None, None, None, None, None
+
+
+def ste_linear(xq, wq, launch):
+    """launch(xq, wq) -> [R, N] with the straight-through backward (xq [R, K], wq [N, K] quantized operands)."""
+    return _LinearSTE.apply(xq, wq, launch)
+
+
+def ste_bmm(aq, bq, launch):
+    """launch(aq, bq) -> [..., M, N] with the straight-through backward (quantized batched operands)."""
+    return _BmmSTE.apply(aq, bq, launch)
+
+
+def ste_conv2d(xq, wq, launch, stride=(1, 1), padding=(0, 0), dilation=(1, 1), groups=1):
+    """launch(xq, wq) -> NCHW y with the straight-through backward (quantized NCHW input and weights)."""
+    return _Conv2dSTE.apply(xq, wq, launch, stride, padding, dilation, groups)

@@ -32,6 +32,7 @@
 #include "fq_mse.h"
 #include "bn_train.h"
 #include "gemm_bmm.h"
+#include "gemm_grad.h"
 
 // (defined with C linkage below; run_gemm launches it too)
 extern "C" __global__ void fq_bias_kernel(fp8a::FqIn fq, float *bias_out, int32_t *ibias_out);
@@ -2002,6 +2003,66 @@ int fp8a_bmm_stats(uint64_t out[3], int reset) {
     if (reset) {
         g_bmm_launches = 0;
         g_bmm_tiles = 0;
+    }
+    return FP8A_OK;
+}
+
+// ------------------------------------------------------------------------- gradient GEMM
+// fp8a_grad_bmm (gemm_grad.h): one launch of gemm_grad_kernel over (64 x 64 tiles, batch items), nothing else
+// on the stream, as fp8a_bmm.
+static std::atomic<uint64_t> g_grad_launches, g_grad_tiles;  // host-side (a replayed graph adds nothing)
+
+int fp8a_grad_bmm(const float *A, const float *B, float *C, int64_t nb, int64_t M, int64_t N, int64_t K0, int64_t K1,
+                  int64_t sa_i, int64_t sa_m, int64_t sa_k0, int64_t sa_k1, int64_t sb_i, int64_t sb_k0, int64_t sb_k1,
+                  int64_t sb_n, int64_t sc_i, int64_t sc_m, int64_t sc_n, fp8a_stream_t stream) {
+    if (nb < 0 || M < 0 || N < 0 || K0 < 0 || K1 < 0) return fail(FP8A_EINVAL, "fp8a_grad_bmm: negative extent");
+    if (sa_i < 0 || sa_m < 0 || sa_k0 < 0 || sa_k1 < 0 || sb_i < 0 || sb_k0 < 0 || sb_k1 < 0 || sb_n < 0 || sc_i < 0 ||
+        sc_m < 0 || sc_n < 0)
+        return fail(FP8A_EINVAL, "fp8a_grad_bmm: negative stride");
+    if (K0 > 0 && K1 > 0x7FFFFFFFll / K0) return fail(FP8A_EINVAL, "fp8a_grad_bmm: K0 * K1 exceeds 2^31 - 1");
+    const int64_t K = K0 * K1;
+    if (nb == 0 || M == 0 || N == 0) return FP8A_OK;
+    if (!C || (K > 0 && (!A || !B))) return fail(FP8A_EINVAL, "fp8a_grad_bmm: null pointer");
+    if ((sc_m == 0 && M > 1) || (sc_n == 0 && N > 1) || (sc_i == 0 && nb > 1))
+        return fail(FP8A_EINVAL, "fp8a_grad_bmm: a zero stride of C over an extent above 1");
+    if (K > 0) {  // C over an operand, where that is cheap to see: the same base, or two dense spans that meet
+        const int64_t ea = (nb - 1) * sa_i + (M - 1) * sa_m + (K0 - 1) * sa_k0 + (K1 - 1) * sa_k1 + 1,
+                      eb = (nb - 1) * sb_i + (K0 - 1) * sb_k0 + (K1 - 1) * sb_k1 + (N - 1) * sb_n + 1,
+                      ec = (nb - 1) * sc_i + (M - 1) * sc_m + (N - 1) * sc_n + 1;
+        const bool dc = ec == nb * M * N;
+        const bool oa = C == A || (dc && ea == nb * M * K && C < A + ea && A < C + ec);
+        const bool ob = C == B || (dc && eb == nb * K * N && C < B + eb && B < C + ec);
+        if (oa || ob) return fail(FP8A_EINVAL, "fp8a_grad_bmm: C overlaps an operand");
+    }
+    GradArgs a;
+    memset(&a, 0, sizeof(a));
+    a.A = A; a.B = B; a.C = C; a.M = M; a.N = N;
+    a.K0 = (uint32_t)K0; a.K1 = (uint32_t)K1; a.K = (uint32_t)K;
+    a.sa_i = sa_i; a.sa_m = sa_m; a.sa_k0 = sa_k0; a.sa_k1 = sa_k1;
+    a.sb_i = sb_i; a.sb_k0 = sb_k0; a.sb_k1 = sb_k1; a.sb_n = sb_n;
+    a.sc_i = sc_i; a.sc_m = sc_m; a.sc_n = sc_n;
+    a.num_mt = (M + GR_T - 1) / GR_T;
+    a.tiles = a.num_mt * ((N + GR_T - 1) / GR_T);
+    if (a.tiles > 0x7FFFFFFFll / nb) return fail(FP8A_EINVAL, "fp8a_grad_bmm: more than 2^31 - 1 tiles");
+    a.recount = grad_recount_ptr();
+    if (a.recount == nullptr) return fail(FP8A_EHIP, "fp8a_grad_bmm: the recomputed-tile counter's address");
+    launch_grad(a, dim3((unsigned)(a.tiles * nb)), (hipStream_t)stream);
+    ++g_grad_launches;
+    g_grad_tiles += (uint64_t)(a.tiles * nb);
+    return hip_check("fp8a_grad_bmm launch");
+}
+
+int fp8a_grad_stats(uint64_t out[3], int reset) {
+    if (out == nullptr) return fail(FP8A_EINVAL, "null pointer");
+    unsigned long long r = 0;
+    if (hipDeviceSynchronize() != hipSuccess || grad_recount_read(&r, reset != 0) != 0)
+        return hip_check("fp8a_grad_stats");
+    out[0] = g_grad_launches.load();
+    out[1] = g_grad_tiles.load();
+    out[2] = r;
+    if (reset) {
+        g_grad_launches = 0;
+        g_grad_tiles = 0;
     }
     return FP8A_OK;
 }

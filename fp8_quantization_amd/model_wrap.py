@@ -27,7 +27,7 @@ from torch.nn.modules.pooling import _AdaptiveAvgPoolNd, _AvgPoolNd
 from . import chain
 from .approx_calculation import QCustomBNConv2dTorch, QCustomConv2dTorch, QCustomLinearTorch
 from .quantization.base_quantized_classes import (QuantizedActivation, QuantizedModule, _set_layer_approx_calculation,
-                                                  _set_layer_estimate_ranges, _set_layer_fix_ranges)
+                                                  _set_layer_estimate_ranges, _set_layer_fix_ranges, sync_ste)
 from .quantization.hijacker import QuantizationHijacker, activations_set
 from .quantization.quantization_manager import QuantizationManager
 
@@ -121,6 +121,7 @@ class QuantizedActivationWrapper(QuantizedActivation):
         self.layer = layer
 
     def quantize_activations_no_range_update(self, x):
+        sync_ste(self)
         return self.activation_quantizer.quantizer(x) if self._qa() else x
 
     def forward(self, x):

@@ -33,6 +33,36 @@ def _set_layer_approx_calculation(layer):
         layer.approx_flag = True
 
 
+def ste_switch(module):
+    """custom_approx_params['ste_backward'] of a layer (opt-in, default off): with it and autograd recording,
+    the layer runs unfused and its quantizers and approx product carry a straight-through backward."""
+    p = getattr(module, "custom_approx_params", None)
+    return bool(p) and bool(p.get("ste_backward", False))
+
+
+def sync_ste(module):
+    """Hand the layer's ste_backward switch to the FP8 quantizers it owns (they cannot see
+    custom_approx_params); one dict lookup per forward while the switch keeps its value.  Returns whether
+    this forward records a backward: the switch, and autograd enabled."""
+    on = ste_switch(module)
+    if on != module.__dict__.get("_ste_synced", False):
+        for m in module.children():
+            q = getattr(m, "quantizer", None) if isinstance(m, QuantizationManager) else None
+            if isinstance(q, FPQuantizer):
+                q.ste_backward = on
+        module.__dict__["_ste_synced"] = on
+    if not on:
+        return False
+    if _version5(module) or getattr(module, "quantize_after_mult_and_add", False):
+        raise NotImplementedError(f"{type(module).__name__}: ste_backward has no backward for approx_version 5 or "
+                                  "quantize_after_mult_and_add")
+    return torch.is_grad_enabled()
+
+
+def _version5(module):
+    return (getattr(module, "custom_approx_params", None) or {}).get("approx_version", 9) == 5
+
+
 _DEFAULT_RUN_METHOD = dict(approx_flag=False, quantize_after_mult_and_add=False, res_quantizer_flag=False,
                            original_quantize_res=False)
 
@@ -126,6 +156,7 @@ class QuantizedActivation(QuantizedModule):
                                                         range_estim_params=self.act_range_options)
 
     def quantize_activations(self, x):
+        sync_ste(self)
         return self.activation_quantizer(x) if self._qa() else x
 
     def forward(self, x):

@@ -22,8 +22,37 @@ def quantize_to_fp8_ste_MM(x_float, n_bits, maxval, num_mantissa_bits, sign_bits
     return fp8_fake_quantize(x_float, maxval, n_bits, M, sign_bits=sign_bits, per_row=per_row)
 
 
+class _FakeQuantSTE(torch.autograd.Function):
+    """The quantizer's forward kernel, unchanged, with the reference's backward: quantize_to_fp8_ste_MM
+    (fp8_quantizer.py:97-173) is differentiable torch whose gradient with respect to x at fixed maxval is that
+    of the clamp min(max(x, minval), maxval) -- the rounding is straight-through and its power-of-two scales
+    are detached, so (g s) / s = g exactly.  The gradient passes inside the clamp, is zero outside, and -- as
+    ATen's maximum / minimum split a tie -- half at x == minval or x == maxval.  Saved: one byte per element."""
+
+    @staticmethod
+    def forward(ctx, x, q):
+        res, q.custom_bias = quantize_to_fp8_ste_MM(x, q.n_bits, q.maxval, q._mbits_int, q.sign_bits)
+        mx = q.maxval
+        if mx.numel() != 1 and mx.dim() != x.dim():
+            mx = mx.view([-1] + [1] * (x.dim() - 1))
+        lo = -mx if q.sign_bits == 1 else torch.zeros_like(mx)
+        # twice the clamp's derivative: 2 inside, 1 on a bound, 0 outside (NaN: 0)
+        ctx.save_for_backward(((x > lo) & (x < mx)).to(torch.uint8) + ((x >= lo) & (x <= mx)).to(torch.uint8))
+        return res
+
+    @staticmethod
+    def backward(ctx, g):
+        (twice,) = ctx.saved_tensors
+        return g * (twice.to(g.dtype) * 0.5), None
+
+
 class FPQuantizer(nn.Module):
-    """8-bit floating-point quantizer with a learnable-free custom exponent bias."""
+    """8-bit floating-point quantizer with a learnable-free custom exponent bias.
+
+    ``ste_backward`` (default off; set by the owning layer from custom_approx_params['ste_backward']): a
+    forward that autograd records goes through _FakeQuantSTE, the same kernel with the reference's gradient
+    with respect to x.  The ranges stay fixed: make_range_trainable keeps raising."""
+    ste_backward = False
 
     def __init__(self, n_bits=8, per_channel=False, scale_domain=None, mantissa_bits=4, maxval=3,
                  set_maxval=False, learn_maxval=False, learn_mantissa_bits=False, mse_include_mantissa_bits=True,
@@ -72,6 +101,8 @@ class FPQuantizer(nn.Module):
     def forward(self, x_float):
         if self.maxval.device != x_float.device:
             self.maxval = self.maxval.to(x_float.device)
+        if self.ste_backward and torch.is_grad_enabled() and x_float.requires_grad:
+            return _FakeQuantSTE.apply(x_float, self)
         res, self.custom_bias = quantize_to_fp8_ste_MM(x_float, self.n_bits, self.maxval, self._mbits_int,
                                                        self.sign_bits)
         return res

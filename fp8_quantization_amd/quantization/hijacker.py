@@ -10,7 +10,7 @@ import os
 
 from torch import nn
 
-from .base_quantized_classes import QuantizedModule
+from .base_quantized_classes import QuantizedModule, sync_ste
 from .fp8_quantizer import FPQuantizer
 from .quantization_manager import QuantizationManager, Qstates
 from .range_estimators import CurrentMinMaxEstimator
@@ -66,6 +66,7 @@ class QuantizationHijacker(QuantizedModule):
         (BNFusedHijacker's fused BN + activation) goes to the approx product only; the caller
         guarantees that product is the only one this forward runs."""
         qa = self._qa()
+        sync_ste(self)  # (the quantizers below learn the layer's ste_backward switch)
         fq = self._fused_input_quantizer(qa)
         if self.quantize_input and qa and fq is None:
             x = self.activation_quantizer(x)

@@ -25,7 +25,7 @@ def approx_qparams(expo_width=4, mant_width=3, dnsmp_factor=3, withComp=False, w
                    zero_table_ext=None, approx_version=9, sim_hw_add_OFUF=False, with_OF_opt=False,
                    with_UF_opt=False, weight_range_method="current_minmax", weight_range_options=None,
                    act_range_method="allminmax", act_range_options=None, mse_include_mantissa_bits=False,
-                   error_table=None):
+                   error_table=None, ste_backward=False):
     """qparams exactly as the reference scripts build them (utils/click_options.py:544-606,
     scripts/generated_scripts.py): per-channel current_minmax weights, allminmax activations,
     quantize_input, FP8 quantizer with set_maxval, approx + res_quantizer run method.
@@ -34,7 +34,9 @@ def approx_qparams(expo_width=4, mant_width=3, dnsmp_factor=3, withComp=False, w
     reference has no error table for, E5M2: error_tables.get_error_table_NN) and approx_version 5
     (the v5 integer-adder model with live sim_hw_add_OFUF / with_OF_opt / with_UF_opt); error_table, a
     user's own multiplier as anything error_tables.load_error_table accepts -- it replaces the built-in
-    table selection (withComp / dnsmp_factor / zero_table_ext) for the v9 model, for any format.
+    table selection (withComp / dnsmp_factor / zero_table_ext) for the v9 model, for any format;
+    ste_backward (opt-in, custom_approx_params["ste_backward"]): forwards that autograd records run unfused
+    with a straight-through backward on the gradient GEMM, nothing else changes.
 
     weight_range_method / act_range_method: a RangeEstimators name (current_minmax, allminmax,
     running_minmax, MSE: the reference's --weight-quant-method / --act-quant-method) or an estimator
@@ -59,6 +61,7 @@ def approx_qparams(expo_width=4, mant_width=3, dnsmp_factor=3, withComp=False, w
                                   debug_mode=False, self_check_mode=False,
                                   **({"zero_table_ext": True} if zero_table_ext else {}),
                                   **({"error_table": error_table} if error_table is not None else {}),
+                                  **({"ste_backward": True} if ste_backward else {}),
                                   **({"approx_version": 5} if approx_version == 5 else {})),
         run_method=dict(run_method) if run_method else dict(
             approx_flag=True, quantize_after_mult_and_add=False, res_quantizer_flag=True, original_quantize_res=False))

@@ -306,6 +306,36 @@ int fp8a_bmm(const float *A, const float *B, float *C,
 int fp8a_bmm_stats(uint64_t out[3], int reset);
 
 /*
+ * The gradient GEMM of the straight-through backward: an exact fp32 batched product of an ARBITRARY fp32
+ * operand A (the incoming gradient) with a bf16-exact operand B (a saved forward operand on its FP8 grid:
+ * at most 8 significant bits), on the bf16 matrix core.  K is addressed on two levels in both operands, so
+ * a convolution's weight gradient reduces over (image, pixel) in one launch:
+ *   C(i,m,n) = sum_{k0 < K0, k1 < K1} A(i,m,k0,k1) * B(i,k0,k1,n),   i < nb
+ *   A(i,m,k0,k1) = A[i*sa_i + m*sa_m + k0*sa_k0 + k1*sa_k1]
+ *   B(i,k0,k1,n) = B[i*sb_i + k0*sb_k0 + k1*sb_k1 + n*sb_n]
+ *   C(i,m,n)     = C[i*sc_i + m*sc_m + n*sc_n]
+ * Every A element is split into three bf16 pieces (8 + 8 + 8 significand bits, each the truncation of what
+ * the previous ones left) while it is staged, B is truncated to bf16, and three
+ * v_mfma_f32_16x16x32_bf16 per K-step accumulate the piece products -- each exact in fp32 -- in fp32: the
+ * fp32 product up to summation order, for any input.  A 64 x 64 output tile whose staging saw a B element
+ * that is not bf16-exact (bf16 subnormals included) or an A element the pieces lose (|a| below 2^-103, inf,
+ * NaN) is recomputed with fp32 FMAs in the same k order inside the same launch.  Deterministic: a fixed k
+ * order per output, no float atomics, no split along K.
+ * Strides are in elements and non-negative (C's are positive over any extent above 1); K0 * K1 < 2^31; C
+ * must not overlap A or B.  Asynchronous, no workspace, no allocation, no host synchronisation.  Empty
+ * extents as fp8a_bmm: nb == 0, M == 0 or N == 0 write nothing; K0 * K1 == 0 writes zeros.  Every argument
+ * check runs before any HIP call and returns FP8A_EINVAL with a message.
+ * fp8a_grad_stats, out[3]: launches and output tiles since load or the last reset (host-side counters) and
+ * tiles recomputed in fp32 (one device counter; synchronises the device).
+ */
+int fp8a_grad_bmm(const float *A, const float *B, float *C,
+                  int64_t nb, int64_t M, int64_t N, int64_t K0, int64_t K1,
+                  int64_t sa_i, int64_t sa_m, int64_t sa_k0, int64_t sa_k1,
+                  int64_t sb_i, int64_t sb_k0, int64_t sb_k1, int64_t sb_n,
+                  int64_t sc_i, int64_t sc_m, int64_t sc_n, fp8a_stream_t stream);
+int fp8a_grad_stats(uint64_t out[3], int reset);
+
+/*
  * Per-product terms (debug / parity): T[m, k, n] = the value the reference sums at v9:113.
  * Same arguments as fp8a_matmul; T is dense [M][K][N].
  */
