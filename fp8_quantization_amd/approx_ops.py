@@ -172,18 +172,35 @@ def _bmm_view(t, what):
     raise AssertionError(f"approx_bmm: {what} needs one or two leading batch dims, got {tuple(t.shape)}")
 
 
+def _bmm_geometry(A, B):
+    """fp8a_bmm's and fp8a_bmm_check's (nb0, nb1, M, N, K, lda, sa0, sa1, sbk, sbn, sb0, sb1)."""
+    nb0, nb1, sa0, sa1 = _bmm_view(A, "A")
+    _, _, sb0, sb1 = _bmm_view(B, "B")
+    return (nb0, nb1, A.shape[-2], B.shape[-1], A.shape[-1], A.stride(-2), sa0, sa1, B.stride(-2), B.stride(-1),
+            sb0, sb1)
+
+
+def _bmm_operands(who, A, B, M, bA, bB, bR, table, flags):
+    """approx_bmm's and approx_bmm_check's operands: float32, A with a unit k stride, the host table and the device
+    biases.  Returns (A, B, bA, bB, bR, table)."""
+    A, B = _as_f32(A), _as_f32(B)
+    if A.stride(-1) != 1 and A.shape[-1] > 1:
+        A = A.contiguous()
+    dev = A.device
+    tab = _table_host(table, M, _uses_table(flags))
+    bB_ = _bias_dev(bB, dev)
+    if bB_.numel() not in (1, B.shape[-1]):
+        raise AssertionError(f"{who}: {bB_.numel()} column biases for {B.shape[-1]} columns")
+    return A, B, _bias_dev(bA, dev), bB_, _bias_dev(bR, dev), tab
+
+
 @torch.library.custom_op("fp8approx::bmm", mutates_args=("out",))
 def _bmm_op(A: torch.Tensor, B: torch.Tensor, out: torch.Tensor, bA: torch.Tensor, bB: torch.Tensor,
             bR: torch.Tensor, table: torch.Tensor, E: int, M: int, flags: int) -> None:
     L = _lib.load()
-    nb0, nb1, sa0, sa1 = _bmm_view(A, "A")
-    _, _, sb0, sb1 = _bmm_view(B, "B")
     _, _, sc0, sc1 = _bmm_view(out, "out")
-    Mr, K = A.shape[-2:]
-    N = B.shape[-1]
     bBs = 0 if bB.numel() == 1 else 1
-    rc = L.fp8a_bmm(_lib.dev_ptr(A), _lib.dev_ptr(B), _lib.dev_ptr(out), nb0, nb1, Mr, N, K,
-                    A.stride(-2), sa0, sa1, B.stride(-2), B.stride(-1), sb0, sb1, out.stride(-2), sc0, sc1,
+    rc = L.fp8a_bmm(_lib.dev_ptr(A), _lib.dev_ptr(B), _lib.dev_ptr(out), *_bmm_geometry(A, B), out.stride(-2), sc0, sc1,
                     E, M, _lib.dev_ptr(bA), _lib.dev_ptr(bB), bBs, _lib.dev_ptr(bR), _lib.host_ptr(table), flags,
                     _lib.stream_ptr(A.device))
     _lib.check(rc, "fp8a_bmm")
@@ -207,9 +224,6 @@ def approx_bmm(A, B, E, M, bA, bB, bR, table=None, flags=None, out=None, **flag_
         raise AssertionError(f"approx_bmm: shape mismatch {tuple(A.shape)} @ {tuple(B.shape)}")  # v9:20
     if flags is None:
         flags = make_flags(**flag_kwargs)
-    A, B = _as_f32(A), _as_f32(B)
-    if A.stride(-1) != 1 and A.shape[-1] > 1:
-        A = A.contiguous()
     shape = tuple(A.shape[:-1]) + (B.shape[-1],)
     dev = A.device
     if out is None:
@@ -217,12 +231,9 @@ def approx_bmm(A, B, E, M, bA, bB, bR, table=None, flags=None, out=None, **flag_
     elif tuple(out.shape) != shape or out.dtype != torch.float32 or out.device != dev or \
             (out.stride(-1) != 1 and shape[-1] > 1):
         raise AssertionError(f"approx_bmm: out must be a float32 {shape} view with unit n stride on {dev}")
-    tab = _table_host(table, M, _uses_table(flags))
-    bB_ = _bias_dev(bB, dev)
-    if bB_.numel() not in (1, B.shape[-1]):
-        raise AssertionError(f"approx_bmm: {bB_.numel()} column biases for {B.shape[-1]} columns")
+    A, B, bA_, bB_, bR_, tab = _bmm_operands("approx_bmm", A, B, M, bA, bB, bR, table, flags)
     ev = _prof_start()
-    _bmm_op(A, B, out, _bias_dev(bA, dev), bB_, _bias_dev(bR, dev), tab, int(E), int(M), int(flags))
+    _bmm_op(A, B, out, bA_, bB_, bR_, tab, int(E), int(M), int(flags))
     _prof_end(ev, A.numel() * B.shape[-1])
     return out
 
@@ -453,6 +464,22 @@ def _check_prod(prod, like):
     return prod
 
 
+def _run_check(entry, call, shape, dev, nbytes, prod):
+    """The approx_*_check functions' tail: C, G, the stats struct and an aligned workspace of nbytes; the C-ABI call
+    ``call(C's pointer, G, Cprod, stats, workspace, workspace_bytes, stream) -> rc``; S as a view of the workspace's
+    head in C's shape; one synchronising read-back of the struct.  Returns ``(C, G, CheckStats)``."""
+    C = torch.empty(shape, dtype=torch.float32, device=dev)
+    G = torch.empty_like(C)
+    prod = _check_prod(prod, C)
+    stats = torch.empty(CHECK_STATS_BYTES, dtype=torch.uint8, device=dev)
+    ws = _aligned_workspace(dev, nbytes)
+    rc = call(_lib.dev_ptr(C), _lib.dev_ptr(G), _lib.dev_ptr(prod), _lib.dev_ptr(stats), _lib.dev_ptr(ws), ws.numel(),
+              _lib.stream_ptr(dev))
+    _lib.check(rc, entry)
+    S = ws[:C.numel() * 4].view(torch.float32).view(C.shape)
+    return C, G, CheckStats.from_bytes(stats.cpu().numpy().tobytes(), S=S)
+
+
 def approx_matmul_check(A, B, E, M, bA, bB, bR, table=None, flags=None, prod=None, **flag_kwargs):
     """The fused self-check of one product (fp8a_matmul_check): returns ``(C, G, CheckStats)`` with
     C the approx sum, G the golden sum (v9:30-36, 145) and the error / normal-value statistics of
@@ -476,19 +503,12 @@ def approx_matmul_check(A, B, E, M, bA, bB, bR, table=None, flags=None, prod=Non
     bA_, bB_, bR_ = _bias_dev(bA, dev), _bias_dev(bB, dev), _bias_dev(bR, dev)
     if bB_.numel() not in (1, N):
         raise AssertionError(f"approx_matmul_check: {bB_.numel()} column biases for {N} columns")
-    C = torch.empty((Mr, N), dtype=torch.float32, device=dev)
-    G = torch.empty_like(C)
-    prod = _check_prod(prod, C)
-    stats = torch.empty(CHECK_STATS_BYTES, dtype=torch.uint8, device=dev)
-    ws = _aligned_workspace(dev, L.fp8a_check_workspace_size(Mr, N, K))
-    rc = L.fp8a_matmul_check(_lib.dev_ptr(A), A.stride(0), _lib.dev_ptr(B), B.stride(0), B.stride(1), _lib.dev_ptr(C),
-                             N, Mr, N, K, int(E), int(M), _lib.dev_ptr(bA_), _lib.dev_ptr(bB_),
-                             0 if bB_.numel() == 1 else 1, _lib.dev_ptr(bR_), _lib.host_ptr(tab), int(flags),
-                             _lib.dev_ptr(G), _lib.dev_ptr(prod), _lib.dev_ptr(stats), _lib.dev_ptr(ws), ws.numel(),
-                             _lib.stream_ptr(dev))
-    _lib.check(rc, "fp8a_matmul_check")
-    S = ws[:Mr * N * 4].view(torch.float32).view(Mr, N)
-    return C, G, CheckStats.from_bytes(stats.cpu().numpy().tobytes(), S=S)
+
+    def call(C, *tail):
+        return L.fp8a_matmul_check(_lib.dev_ptr(A), A.stride(0), _lib.dev_ptr(B), B.stride(0), B.stride(1), C, N, Mr, N,
+                                   K, int(E), int(M), _lib.dev_ptr(bA_), _lib.dev_ptr(bB_),
+                                   0 if bB_.numel() == 1 else 1, _lib.dev_ptr(bR_), _lib.host_ptr(tab), int(flags), *tail)
+    return _run_check("fp8a_matmul_check", call, (Mr, N), dev, L.fp8a_check_workspace_size(Mr, N, K), prod)
 
 
 def approx_conv2d_check(x, w, E, M, bA, bW, bR, table=None, flags=None, stride=(1, 1), padding=(0, 0),
@@ -518,18 +538,11 @@ def approx_conv2d_check(x, w, E, M, bA, bW, bR, table=None, flags=None, stride=(
     nbytes = L.fp8a_conv2d_check_workspace_size(*geo)
     if nbytes == 0:
         raise AssertionError("approx_conv2d_check: empty or inconsistent convolution geometry")
-    y = torch.empty(_conv_out_shape(x, w, stride, padding, dilation), dtype=torch.float32, device=dev)
-    G = torch.empty_like(y)
-    prod = _check_prod(prod, y)
-    stats = torch.empty(CHECK_STATS_BYTES, dtype=torch.uint8, device=dev)
-    ws = _aligned_workspace(dev, nbytes)
-    rc = L.fp8a_conv2d_check(_lib.dev_ptr(x), _lib.dev_ptr(w), _lib.dev_ptr(y), *geo, int(E), int(M),
-                             _lib.dev_ptr(bA_), _lib.dev_ptr(bW_), _lib.dev_ptr(bR_), _lib.host_ptr(tab), int(flags),
-                             _lib.dev_ptr(G), _lib.dev_ptr(prod), _lib.dev_ptr(stats), _lib.dev_ptr(ws), ws.numel(),
-                             _lib.stream_ptr(dev))
-    _lib.check(rc, "fp8a_conv2d_check")
-    S = ws[:y.numel() * 4].view(torch.float32).view(y.shape)
-    return y, G, CheckStats.from_bytes(stats.cpu().numpy().tobytes(), S=S)
+
+    def call(y, *tail):
+        return L.fp8a_conv2d_check(_lib.dev_ptr(x), _lib.dev_ptr(w), y, *geo, int(E), int(M), _lib.dev_ptr(bA_),
+                                   _lib.dev_ptr(bW_), _lib.dev_ptr(bR_), _lib.host_ptr(tab), int(flags), *tail)
+    return _run_check("fp8a_conv2d_check", call, _conv_out_shape(x, w, stride, padding, dilation), dev, nbytes, prod)
 
 
 def approx_bmm_check(A, B, E, M, bA, bB, bR, table=None, flags=None, prod=None, **flag_kwargs):
@@ -543,31 +556,15 @@ def approx_bmm_check(A, B, E, M, bA, bB, bR, table=None, flags=None, prod=None, 
     if flags is None:
         flags = make_flags(**flag_kwargs)
     L = _lib.load()
-    A, B = _as_f32(A), _as_f32(B)
-    if A.stride(-1) != 1 and A.shape[-1] > 1:
-        A = A.contiguous()
-    dev = A.device
-    nb0, nb1, sa0, sa1 = _bmm_view(A, "A")
-    _, _, sb0, sb1 = _bmm_view(B, "B")
-    Mr, K = A.shape[-2:]
-    N = B.shape[-1]
-    tab = _table_host(table, M, _uses_table(flags))
-    bA_, bB_, bR_ = _bias_dev(bA, dev), _bias_dev(bB, dev), _bias_dev(bR, dev)
-    if bB_.numel() not in (1, N):
-        raise AssertionError(f"approx_bmm_check: {bB_.numel()} column biases for {N} columns")
-    C = torch.empty(tuple(A.shape[:-1]) + (N,), dtype=torch.float32, device=dev)
-    G = torch.empty_like(C)
-    prod = _check_prod(prod, C)
-    stats = torch.empty(CHECK_STATS_BYTES, dtype=torch.uint8, device=dev)
-    ws = _aligned_workspace(dev, L.fp8a_bmm_check_workspace_size(nb0, nb1, Mr, N, K))
-    rc = L.fp8a_bmm_check(_lib.dev_ptr(A), _lib.dev_ptr(B), _lib.dev_ptr(C), nb0, nb1, Mr, N, K,
-                          A.stride(-2), sa0, sa1, B.stride(-2), B.stride(-1), sb0, sb1, int(E), int(M),
-                          _lib.dev_ptr(bA_), _lib.dev_ptr(bB_), 0 if bB_.numel() == 1 else 1, _lib.dev_ptr(bR_),
-                          _lib.host_ptr(tab), int(flags), _lib.dev_ptr(G), _lib.dev_ptr(prod), _lib.dev_ptr(stats),
-                          _lib.dev_ptr(ws), ws.numel(), _lib.stream_ptr(dev))
-    _lib.check(rc, "fp8a_bmm_check")
-    S = ws[:C.numel() * 4].view(torch.float32).view(C.shape)
-    return C, G, CheckStats.from_bytes(stats.cpu().numpy().tobytes(), S=S)
+    A, B, bA_, bB_, bR_, tab = _bmm_operands("approx_bmm_check", A, B, M, bA, bB, bR, table, flags)
+    geo = _bmm_geometry(A, B)  # (nb0, nb1, M, N, K, the strides)
+
+    def call(C, *tail):
+        return L.fp8a_bmm_check(_lib.dev_ptr(A), _lib.dev_ptr(B), C, *geo, int(E), int(M), _lib.dev_ptr(bA_),
+                                _lib.dev_ptr(bB_), 0 if bB_.numel() == 1 else 1, _lib.dev_ptr(bR_), _lib.host_ptr(tab),
+                                int(flags), *tail)
+    return _run_check("fp8a_bmm_check", call, tuple(A.shape[:-1]) + (geo[3],), A.device,
+                      L.fp8a_bmm_check_workspace_size(*geo[:5]), prod)
 
 
 def custom_matmul_vectorize(A, B, expo_width, mant_width, custom_bias_A, custom_bias_B, custom_bias_R,

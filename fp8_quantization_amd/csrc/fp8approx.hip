@@ -1014,6 +1014,12 @@ static int stream_capturing(hipStream_t s) {
     if (dbg) fprintf(stderr, "fp8a lease stream=%p capturing=%d\n", (void *)s, (int)st);
     return st == hipStreamCaptureStatusActive ? 1 : 0;
 }
+// stream_capturing returned -1: HIP's recorded error, or an error of our own when it recorded none --
+// never FP8A_OK, the caller has launched nothing.  who: "fp8a", "fp8a self-check:".
+static int capture_query_error(const std::string &who) {
+    const int rc = hip_check((who + " stream capture query").c_str());
+    return rc ? rc : fail(FP8A_EHIP, who + " the stream capture query failed");
+}
 // The lease of a captured launch: `need` bytes at the head of its workspace, zeroed in-stream.
 static bool capture_lease(hipStream_t s, void *ws, size_t ws_bytes, size_t need, ArenaLease &l) {
     if (ws == nullptr || ws_bytes < need) return false;
@@ -1120,7 +1126,7 @@ static int run_gemm(GemmArgs &a, const int32_t *table, void *ws, size_t ws_bytes
     const size_t head = ws_bytes >= head_bytes(a.M, a.N) ? head_bytes(a.M, a.N) : FLAG_BYTES;
     ArenaLease lease;
     const int cap = stream_capturing(s);  // (captured: the words live in the workspace head, flag_arena)
-    if (cap < 0) return hip_check("fp8a stream capture query");
+    if (cap < 0) return capture_query_error("fp8a");
     if (cap ? !capture_lease(s, ws, ws_bytes, head, lease) : !flag_arena(s, head_bytes(a.M, a.N), lease))
         return lease_error();
     a.flag = lease.mine;
@@ -1938,6 +1944,31 @@ static int64_t bmm_span(int64_t n0, int64_t s0, int64_t n1, int64_t s1, int64_t 
     return (n0 - 1) * s0 + (n1 - 1) * s1 + (r - 1) * sr + (c - 1) * sc + 1;
 }
 
+// C over an operand, where that is cheap to see: the same base, or two dense spans that meet.  ea, eb, ec:
+// the views' bmm_span; fp8a_bmm and fp8a_grad_bmm.
+static bool c_overlaps_operand(const float *A, int64_t ea, const float *B, int64_t eb, const float *C, int64_t ec,
+                               int64_t nb, int64_t M, int64_t N, int64_t K) {
+    const bool dc = ec == nb * M * N;
+    const bool oa = C == A || (dc && ea == nb * M * K && C < A + ea && A < C + ec);
+    const bool ob = C == B || (dc && eb == nb * K * N && C < B + eb && B < C + ec);
+    return oa || ob;
+}
+
+// What fp8a_bmm and fp8a_bmm_check refuse alike in a batched view, each in its own order: fp8a_bmm_check
+// looks at the strides first.  who: the entry, for the texts that carry one.
+static int bmm_view_check(const char *who, uint32_t flags, int64_t bB_stride, bool neg_stride, bool strides_first) {
+    const std::string w = std::string(who) + ": ";
+    if (strides_first && neg_stride) return fail(FP8A_EINVAL, w + "negative stride");
+    if (flags & F_TB)
+        return fail(FP8A_EINVAL, "fp8a_bmm: no tensor-bias semantics (FP8A_TB) for a batched product");
+    if (flags & (F_V5 | F_OFUF | F_OF | F_UF))
+        return fail(FP8A_EINVAL, "fp8a_bmm: the v5 model is not implemented for a batched product");
+    if (flags & ~(F_APPROX | F_S2N | F_QBMA | F_GCLIP)) return fail(FP8A_EINVAL, w + "unknown flag bits");
+    if (bB_stride != 0 && bB_stride != 1) return fail(FP8A_EINVAL, w + "bB_stride must be 0 or 1");
+    if (neg_stride) return fail(FP8A_EINVAL, w + "negative stride");
+    return FP8A_OK;
+}
+
 int fp8a_bmm(const float *A, const float *B, float *C, int64_t nb0, int64_t nb1, int64_t M, int64_t N, int64_t K,
              int64_t lda, int64_t sa0, int64_t sa1, int64_t sbk, int64_t sbn, int64_t sb0, int64_t sb1, int64_t ldc,
              int64_t sc0, int64_t sc1, int E, int Mw, const int32_t *bA, const int32_t *bB, int64_t bB_stride,
@@ -1945,14 +1976,10 @@ int fp8a_bmm(const float *A, const float *B, float *C, int64_t nb0, int64_t nb1,
     int rc = check_format(E, Mw);
     if (rc) return rc;
     if (nb0 < 0 || nb1 < 0 || M < 0 || N < 0 || K < 0) return fail(FP8A_EINVAL, "fp8a_bmm: negative extent");
-    if (flags & F_TB)
-        return fail(FP8A_EINVAL, "fp8a_bmm: no tensor-bias semantics (FP8A_TB) for a batched product");
-    if (flags & (F_V5 | F_OFUF | F_OF | F_UF))
-        return fail(FP8A_EINVAL, "fp8a_bmm: the v5 model is not implemented for a batched product");
-    if (flags & ~(F_APPROX | F_S2N | F_QBMA | F_GCLIP)) return fail(FP8A_EINVAL, "fp8a_bmm: unknown flag bits");
-    if (bB_stride != 0 && bB_stride != 1) return fail(FP8A_EINVAL, "fp8a_bmm: bB_stride must be 0 or 1");
-    if (lda < 0 || sa0 < 0 || sa1 < 0 || sbk < 0 || sbn < 0 || sb0 < 0 || sb1 < 0 || ldc < 0 || sc0 < 0 || sc1 < 0)
-        return fail(FP8A_EINVAL, "fp8a_bmm: negative stride");
+    const bool neg_stride = lda < 0 || sa0 < 0 || sa1 < 0 || sbk < 0 || sbn < 0 || sb0 < 0 || sb1 < 0 || ldc < 0 ||
+                            sc0 < 0 || sc1 < 0;
+    rc = bmm_view_check("fp8a_bmm", flags, bB_stride, neg_stride, false);
+    if (rc) return rc;
     if ((M > 1 && lda < K) || (M > 1 && ldc < N)) return fail(FP8A_EINVAL, "leading dimension smaller than extent");
     TablePack tp;
     int mode;
@@ -1961,14 +1988,10 @@ int fp8a_bmm(const float *A, const float *B, float *C, int64_t nb0, int64_t nb1,
     const int64_t nb = nb0 * nb1;
     if (nb == 0 || M == 0 || N == 0) return FP8A_OK;
     if (!C || (K > 0 && (!A || !B || !bA || !bB || !bR))) return fail(FP8A_EINVAL, "fp8a_bmm: null pointer");
-    if (K > 0) {  // C over an operand, where that is cheap to see: the same base, or two dense spans that meet
-        const int64_t ea = bmm_span(nb0, sa0, nb1, sa1, M, lda, K, 1), eb = bmm_span(nb0, sb0, nb1, sb1, K, sbk, N, sbn),
-                      ec = bmm_span(nb0, sc0, nb1, sc1, M, ldc, N, 1);
-        const bool dc = ec == nb * M * N;
-        const bool oa = C == A || (dc && ea == nb * M * K && C < A + ea && A < C + ec);
-        const bool ob = C == B || (dc && eb == nb * K * N && C < B + eb && B < C + ec);
-        if (oa || ob) return fail(FP8A_EINVAL, "fp8a_bmm: C overlaps an operand");
-    }
+    if (K > 0 && c_overlaps_operand(A, bmm_span(nb0, sa0, nb1, sa1, M, lda, K, 1), B,
+                                    bmm_span(nb0, sb0, nb1, sb1, K, sbk, N, sbn), C,
+                                    bmm_span(nb0, sc0, nb1, sc1, M, ldc, N, 1), nb, M, N, K))
+        return fail(FP8A_EINVAL, "fp8a_bmm: C overlaps an operand");
     BmmArgs a;
     memset(&a, 0, sizeof(a));
     a.A = A; a.B = B; a.C = C; a.nb1 = nb1; a.M = M; a.N = N; a.K = K;
@@ -2025,15 +2048,10 @@ int fp8a_grad_bmm(const float *A, const float *B, float *C, int64_t nb, int64_t 
     if (!C || (K > 0 && (!A || !B))) return fail(FP8A_EINVAL, "fp8a_grad_bmm: null pointer");
     if ((sc_m == 0 && M > 1) || (sc_n == 0 && N > 1) || (sc_i == 0 && nb > 1))
         return fail(FP8A_EINVAL, "fp8a_grad_bmm: a zero stride of C over an extent above 1");
-    if (K > 0) {  // C over an operand, where that is cheap to see: the same base, or two dense spans that meet
-        const int64_t ea = (nb - 1) * sa_i + (M - 1) * sa_m + (K0 - 1) * sa_k0 + (K1 - 1) * sa_k1 + 1,
-                      eb = (nb - 1) * sb_i + (K0 - 1) * sb_k0 + (K1 - 1) * sb_k1 + (N - 1) * sb_n + 1,
-                      ec = (nb - 1) * sc_i + (M - 1) * sc_m + (N - 1) * sc_n + 1;
-        const bool dc = ec == nb * M * N;
-        const bool oa = C == A || (dc && ea == nb * M * K && C < A + ea && A < C + ec);
-        const bool ob = C == B || (dc && eb == nb * K * N && C < B + eb && B < C + ec);
-        if (oa || ob) return fail(FP8A_EINVAL, "fp8a_grad_bmm: C overlaps an operand");
-    }
+    if (K > 0 && c_overlaps_operand(A, bmm_span(nb, sa_i, M, sa_m, K0, sa_k0, K1, sa_k1), B,
+                                    bmm_span(nb, sb_i, K0, sb_k0, K1, sb_k1, N, sb_n), C,
+                                    bmm_span(1, 0, nb, sc_i, M, sc_m, N, sc_n), nb, M, N, K))
+        return fail(FP8A_EINVAL, "fp8a_grad_bmm: C overlaps an operand");
     GradArgs a;
     memset(&a, 0, sizeof(a));
     a.A = A; a.B = B; a.C = C; a.M = M; a.N = N;
@@ -2083,46 +2101,75 @@ int fp8a_terms(const float *A, int64_t lda, const float *B, int64_t sbk, int64_t
 }
 
 // ------------------------------------------------------------------------- fused self-check
-// fp8a_matmul_check / fp8a_conv2d_check (gemm_check.h): workspace = the dense S image (one float per
-// output), then one CheckPart per workgroup (64 x 64 tile x group).
+// fp8a_matmul_check / fp8a_bmm_check / fp8a_conv2d_check (gemm_check.h): one kernel over `units` products of
+// M x N x K -- the one matrix product, the nb0 x nb1 batch items, the convolution groups.  Workspace = the
+// dense S image (one float per output, units M N of them), then one CheckPart per workgroup (unit x 64 x 64 tile).
 static int64_t check_tiles(int64_t M, int64_t N) { return ((M + CK_BM - 1) / CK_BM) * ((N + CK_BN - 1) / CK_BN); }
-static size_t check_ws_bytes(int64_t outs, int64_t M, int64_t N, int64_t groups) {
-    return align256((size_t)outs * 4) + align256(check_part_bytes(check_tiles(M, N) * groups));
+// Sizes saturate instead of wrapping, so an absurd extent fails the workspace test, not the arithmetic.
+static size_t check_ws_bytes(int64_t units, int64_t M, int64_t N) {
+    int64_t outs, parts;  // (positive extents; 2^56: far above any device, far below a wrap of the sums)
+    if (__builtin_mul_overflow(units, M, &outs) || __builtin_mul_overflow(outs, N, &outs) || outs > (1ll << 56) ||
+        M > (1ll << 40) || N > (1ll << 40) || __builtin_mul_overflow(units, check_tiles(M, N), &parts) ||
+        parts > (1ll << 50))
+        return SIZE_MAX;
+    return align256((size_t)outs * 4) + align256(check_part_bytes(parts));
+}
+// (the size queries' answer: 0 for what no workspace can hold)
+static size_t check_ws_query(int64_t units, int64_t M, int64_t N) {
+    const size_t b = check_ws_bytes(units, M, N);
+    return b == SIZE_MAX ? 0 : b;
+}
+// nb0 nb1 of non-negative extents, saturating
+static int64_t bmm_units(int64_t nb0, int64_t nb1) {
+    int64_t nb;
+    return __builtin_mul_overflow(nb0, nb1, &nb) ? INT64_MAX : nb;
 }
 
-static int run_check(GemmArgs &a, CheckArgs &c, int64_t outs, const int32_t *table, void *ws, size_t ws_bytes,
-                     hipStream_t s) {
-    int rc = check_format(a.E, a.Mw);
+// The tail of all three entries, from the checks they share to the launch.  c: the operands, extents, units and
+// flags; this fills tiles, S, part and the table.
+static int run_check(CheckArgs &c, const int32_t *table, void *ws, size_t ws_bytes, hipStream_t s) {
+    int rc = check_format(c.E, c.Mw);
     if (rc) return rc;
-    if (a.flags & F_V5) return fail(FP8A_EINVAL, "the self-check covers the v9 model only (no FP8A_V5)");
-    if (a.M <= 0 || a.N <= 0 || a.K <= 0) return fail(FP8A_EINVAL, "self-check extents must be positive");
-    if ((!a.A && !a.conv) || (a.conv && !a.X) || !a.B || !a.C || !a.bA || !a.bB || !a.bR || !c.stats)
-        return fail(FP8A_EINVAL, "null pointer");
-    if (check_tiles(a.M, a.N) >= (1ll << 31) || c.groups > 65535)
-        return fail(FP8A_EINVAL, "self-check grid too large");
-    if (ws == nullptr || (((uintptr_t)ws) & 255) != 0 || ws_bytes < check_ws_bytes(outs, a.M, a.N, c.groups))
+    if (c.flags & F_V5) return fail(FP8A_EINVAL, "the self-check covers the v9 model only (no FP8A_V5)");
+    if (c.units <= 0 || c.M <= 0 || c.N <= 0 || c.K <= 0)
+        return fail(FP8A_EINVAL, "self-check extents must be positive");
+    if (!c.A || !c.B || !c.C || !c.bA || !c.bB || !c.bR || !c.stats) return fail(FP8A_EINVAL, "null pointer");
+    if (ws == nullptr || (((uintptr_t)ws) & 255) != 0 || ws_bytes < check_ws_bytes(c.units, c.M, c.N))
         return fail(FP8A_EINVAL, "self-check workspace missing, misaligned or too small");
     if ((((uintptr_t)c.stats) & 7) != 0) return fail(FP8A_EINVAL, "stats must be 8-byte aligned");
+    // (the workspace test bounds units M N: no product below wraps)
+    c.tiles_n = (c.N + CK_BN - 1) / CK_BN;
+    c.tiles = check_tiles(c.M, c.N);
+    if (c.tiles > 0x7FFFFFFFll / c.units || (c.conv && c.units > 65535))
+        return fail(FP8A_EINVAL, "self-check grid too large");
     int mode;
-    rc = pack_table(table, a.Mw, (a.flags & F_APPROX) != 0, a.tab, mode);
+    rc = pack_table(table, c.Mw, (c.flags & F_APPROX) != 0, c.tab, mode);
     if (rc) return rc;
-    // a diagnostic, not for graphs; a query that fails is an error of its own (never FP8A_OK)
+    // a diagnostic, not for graphs
     const int cap = stream_capturing(s);
-    if (cap < 0) {
-        rc = hip_check("fp8a self-check: stream capture query");
-        return rc ? rc : fail(FP8A_EHIP, "fp8a self-check: the stream capture query failed");
-    }
+    if (cap < 0) return capture_query_error("fp8a self-check:");
     if (cap) return fail(FP8A_EINVAL, "the self-check does not run on a capturing stream");
     c.S = (float *)ws;
-    c.part = (CheckPart *)((char *)ws + align256((size_t)outs * 4));
-    c.tiles_n = (a.N + CK_BN - 1) / CK_BN;
-    launch_check(a, c, s);
+    c.part = (CheckPart *)((char *)ws + align256((size_t)(c.units * c.M * c.N) * 4));
+    launch_check(c, s);
     return hip_check("fp8a self-check launch");
+}
+
+// what all three entries set alike (one unit until the caller says otherwise); the rest stays zero
+static CheckArgs check_args(const float *A, const float *B, float *C, int64_t M, int64_t N, int64_t K, int E, int Mw,
+                            const int32_t *bA, const int32_t *bB, int64_t bBs, const int32_t *bR, uint32_t flags,
+                            float *G, const float *Cprod, fp8a_check_stats *stats) {
+    CheckArgs c{};
+    c.A = A; c.B = B; c.C = C; c.G = G; c.Cprod = Cprod; c.stats = stats;
+    c.M = M; c.N = N; c.K = K; c.E = E; c.Mw = Mw;
+    c.bA = bA; c.bB = bB; c.bBs = bBs; c.bR = bR; c.flags = flags;
+    c.units = 1; c.nb1 = 1;
+    return c;
 }
 
 size_t fp8a_check_workspace_size(int64_t M, int64_t N, int64_t K) {
     if (M <= 0 || N <= 0 || K <= 0) return 0;
-    return check_ws_bytes(M * N, M, N, 1);
+    return check_ws_query(1, M, N);
 }
 
 int fp8a_matmul_check(const float *A, int64_t lda, const float *B, int64_t sbk, int64_t sbn, float *C, int64_t ldc,
@@ -2131,27 +2178,15 @@ int fp8a_matmul_check(const float *A, int64_t lda, const float *B, int64_t sbk, 
                       const float *Cprod, fp8a_check_stats *stats, void *workspace, size_t workspace_bytes,
                       fp8a_stream_t stream) {
     if (lda < K || ldc < N) return fail(FP8A_EINVAL, "leading dimension smaller than extent");
-    GemmArgs a = make_args(A, lda, B, sbk, sbn, C, ldc, M, N, K, E, Mw, bA, bB, bB_stride, bR, flags);
-    CheckArgs c{};
-    c.G = G; c.Cprod = Cprod; c.stats = stats; c.groups = 1;
-    return run_check(a, c, M * N, table, workspace, workspace_bytes, (hipStream_t)stream);
+    CheckArgs c = check_args(A, B, C, M, N, K, E, Mw, bA, bB, bB_stride, bR, flags, G, Cprod, stats);
+    c.lda = lda; c.sbk = sbk; c.sbn = sbn; c.ldc = ldc;
+    return run_check(c, table, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
-// fp8a_bmm_check (gemm_bmm_check_kernel): the S image of all items, then one CheckPart per (item, tile).
-// Sizes saturate instead of wrapping, so an absurd extent fails the workspace test, not the arithmetic.
-static size_t bmm_check_ws_bytes(int64_t nb0, int64_t nb1, int64_t M, int64_t N) {
-    int64_t nb, outs, parts;  // (positive extents; 2^56: far above any device, far below a wrap of the sums)
-    if (__builtin_mul_overflow(nb0, nb1, &nb) || __builtin_mul_overflow(nb, M, &outs) ||
-        __builtin_mul_overflow(outs, N, &outs) || outs > (1ll << 56) || M > (1ll << 40) || N > (1ll << 40) ||
-        __builtin_mul_overflow(nb, check_tiles(M, N), &parts) || parts > (1ll << 50))
-        return SIZE_MAX;
-    return align256((size_t)outs * 4) + align256(check_part_bytes(parts));
-}
-
+// fp8a_bmm_check: the units are the nb0 x nb1 items, C, G, Cprod and S dense [nb0][nb1][M][N].
 size_t fp8a_bmm_check_workspace_size(int64_t nb0, int64_t nb1, int64_t M, int64_t N, int64_t K) {
     if (nb0 <= 0 || nb1 <= 0 || M <= 0 || N <= 0 || K <= 0) return 0;
-    const size_t b = bmm_check_ws_bytes(nb0, nb1, M, N);
-    return b == SIZE_MAX ? 0 : b;
+    return check_ws_query(bmm_units(nb0, nb1), M, N);
 }
 
 int fp8a_bmm_check(const float *A, const float *B, float *C, int64_t nb0, int64_t nb1, int64_t M, int64_t N, int64_t K,
@@ -2162,57 +2197,21 @@ int fp8a_bmm_check(const float *A, const float *B, float *C, int64_t nb0, int64_
     int rc = check_format(E, Mw);
     if (rc) return rc;
     if (nb0 < 0 || nb1 < 0 || M < 0 || N < 0 || K < 0) return fail(FP8A_EINVAL, "fp8a_bmm_check: negative extent");
-    if (lda < 0 || sa0 < 0 || sa1 < 0 || sbk < 0 || sbn < 0 || sb0 < 0 || sb1 < 0)
-        return fail(FP8A_EINVAL, "fp8a_bmm_check: negative stride");
-    if (flags & F_TB)
-        return fail(FP8A_EINVAL, "fp8a_bmm: no tensor-bias semantics (FP8A_TB) for a batched product");
-    if (flags & (F_V5 | F_OFUF | F_OF | F_UF))
-        return fail(FP8A_EINVAL, "fp8a_bmm: the v5 model is not implemented for a batched product");
-    if (flags & ~(F_APPROX | F_S2N | F_QBMA | F_GCLIP)) return fail(FP8A_EINVAL, "fp8a_bmm_check: unknown flag bits");
-    if (bB_stride != 0 && bB_stride != 1) return fail(FP8A_EINVAL, "fp8a_bmm_check: bB_stride must be 0 or 1");
-    if (M > 1 && lda < K) return fail(FP8A_EINVAL, "leading dimension smaller than extent");
-    if (nb0 <= 0 || nb1 <= 0 || M <= 0 || N <= 0 || K <= 0)
-        return fail(FP8A_EINVAL, "self-check extents must be positive");
-    if (!A || !B || !C || !bA || !bB || !bR || !stats) return fail(FP8A_EINVAL, "null pointer");
-    if (workspace == nullptr || (((uintptr_t)workspace) & 255) != 0 ||
-        workspace_bytes < bmm_check_ws_bytes(nb0, nb1, M, N))
-        return fail(FP8A_EINVAL, "self-check workspace missing, misaligned or too small");
-    if ((((uintptr_t)stats) & 7) != 0) return fail(FP8A_EINVAL, "stats must be 8-byte aligned");
-    // (the workspace test bounds nb0 nb1 M N: no product below wraps)
-    const int64_t nb = nb0 * nb1, tiles = check_tiles(M, N);
-    if (tiles > 0x7FFFFFFFll / nb) return fail(FP8A_EINVAL, "self-check grid too large");
-    BmmCheckArgs a;
-    memset(&a, 0, sizeof(a));
-    int mode;
-    rc = pack_table(table, Mw, (flags & F_APPROX) != 0, a.tab, mode);
+    const bool neg_stride = lda < 0 || sa0 < 0 || sa1 < 0 || sbk < 0 || sbn < 0 || sb0 < 0 || sb1 < 0;
+    rc = bmm_view_check("fp8a_bmm_check", flags, bB_stride, neg_stride, true);
     if (rc) return rc;
-    // a diagnostic, not for graphs; a query that fails is an error of its own (never FP8A_OK)
-    hipStream_t s = (hipStream_t)stream;
-    const int cap = stream_capturing(s);
-    if (cap < 0) {
-        rc = hip_check("fp8a self-check: stream capture query");
-        return rc ? rc : fail(FP8A_EHIP, "fp8a self-check: the stream capture query failed");
-    }
-    if (cap) return fail(FP8A_EINVAL, "the self-check does not run on a capturing stream");
-    a.A = A; a.B = B; a.C = C; a.G = G; a.Cprod = Cprod;
-    a.S = (float *)workspace;
-    a.part = (CheckPart *)((char *)workspace + align256((size_t)(nb * M * N) * 4));
-    a.nb1 = nb1; a.M = M; a.N = N; a.K = K;
-    a.lda = lda; a.sa0 = sa0; a.sa1 = sa1; a.sbk = sbk; a.sbn = sbn; a.sb0 = sb0; a.sb1 = sb1;
-    a.tiles_n = (N + CK_BN - 1) / CK_BN;
-    a.tiles = tiles;
-    a.E = E; a.Mw = Mw; a.bA = bA; a.bB = bB; a.bBs = bB_stride; a.bR = bR; a.flags = flags;
-    CheckArgs c{};
-    c.Cprod = Cprod; c.stats = stats; c.part = a.part; c.groups = (int)nb;
-    launch_bmm_check(a, c, nb, s);
-    return hip_check("fp8a self-check launch");
+    if (M > 1 && lda < K) return fail(FP8A_EINVAL, "leading dimension smaller than extent");
+    CheckArgs c = check_args(A, B, C, M, N, K, E, Mw, bA, bB, bB_stride, bR, flags, G, Cprod, stats);
+    c.units = bmm_units(nb0, nb1); c.nb1 = nb1;
+    c.lda = lda; c.sa0 = sa0; c.sa1 = sa1; c.sbk = sbk; c.sbn = sbn; c.sb0 = sb0; c.sb1 = sb1; c.ldc = N;
+    return run_check(c, table, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 size_t fp8a_conv2d_check_workspace_size(int64_t Bn, int64_t Cin, int64_t H, int64_t W, int64_t Cout, int kh, int kw,
                                         int sh, int sw, int ph, int pw, int dh, int dw, int groups) {
     ConvShape c{Bn, Cin, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, groups};
     if (conv_shape(c) || Bn <= 0 || Cout <= 0 || Cin <= 0) return 0;
-    return check_ws_bytes(Cout * c.Mrows, c.Mrows, c.cog, groups);
+    return check_ws_query(groups, c.Mrows, c.cog);
 }
 
 int fp8a_conv2d_check(const float *x, const float *w, float *y, int64_t Bn, int64_t Cin, int64_t H, int64_t W,
@@ -2231,18 +2230,13 @@ int fp8a_conv2d_check(const float *x, const float *w, float *y, int64_t Bn, int6
     const int64_t Ho = g.Ho, Wo = g.Wo, cog = g.cog, cig = g.cig, Kg = g.Kg, Mrows = g.Mrows;
     // single-output-channel groups: the tensor-bias semantics, as fp8a_conv2d (approx_calculation.py:800-809)
     const uint32_t fl = (flags & ~F_TB) | ((cog == 1 && !(flags & F_V5)) ? (uint32_t)F_TB : 0u);
-    GemmArgs a = make_args(nullptr, 0, w, 1, Kg, y, 0, Mrows, cog, Kg, E, Mw, bA, bW, 1, bR, fl);
-    a.nchw = 1;
-    a.hw = Ho * Wo;
-    a.ctot = Cout;
-    a.conv = 1;
-    a.X = x;
-    a.Cin = Cin; a.H = H; a.W = W; a.Ho = Ho; a.Wo = Wo;
-    a.kh = kh; a.kw = kw; a.sh = sh; a.sw = sw; a.ph = ph; a.pw = pw; a.dh = dh; a.dw = dw;
-    CheckArgs c{};
-    c.G = G; c.Cprod = Cprod; c.stats = stats; c.groups = groups;
-    c.b_gs = cog * Kg; c.bb_gs = cog; c.cig = cig; c.cog = cog;
-    return run_check(a, c, Bn * Cout * Ho * Wo, table, workspace, workspace_bytes, (hipStream_t)stream);
+    // the units are the groups: A = x's implicit-im2col rows, B = the group's [cog][Kg] weights
+    CheckArgs c = check_args(x, w, y, Mrows, cog, Kg, E, Mw, bA, bW, 1, bR, fl, G, Cprod, stats);
+    c.units = groups; c.conv = 1; c.sbk = 1; c.sbn = Kg;
+    c.b_gs = cog * Kg; c.bb_gs = cog; c.cig = cig; c.cog = cog; c.ctot = Cout;
+    c.Cin = Cin; c.H = H; c.W = W; c.Ho = Ho; c.Wo = Wo;
+    c.kh = kh; c.kw = kw; c.sh = sh; c.sw = sw; c.ph = ph; c.pw = pw; c.dh = dh; c.dw = dw;
+    return run_check(c, table, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 int fp8a_im2col(const float *x, float *out, int64_t Bn, int64_t Cin, int64_t H, int64_t W, int kh, int kw, int sh,

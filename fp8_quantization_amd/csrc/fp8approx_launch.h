@@ -40,11 +40,11 @@ int tt_rerun_stats(unsigned long long *v, bool reset);
 // k_v5.hip: the v5 matrix-core form (a.wfmt 4), per OF / UF switch pair.
 void launch_v5mx(const GemmArgs &a, hipStream_t s);
 
-// k_check.hip: the fused self-check (gemm_check.h) -- gemm_check_kernel over (64 x 64 tiles, groups)
-// and its one-workgroup stats reduction; check_part_bytes = the workspace bytes of `parts` workgroups.
-// (The batched form's launcher, launch_bmm_check, is declared with its arguments in gemm_check.h.)
+// k_check.hip: the fused self-check (gemm_check.h) -- gemm_check_kernel over c.units * c.tiles workgroups
+// (a unit: the matrix product, a batch item or a convolution group; 64 x 64 tiles) and its
+// one-workgroup stats reduction; check_part_bytes = the workspace bytes of `parts` workgroups.
 struct CheckArgs;
-void launch_check(const GemmArgs &a, const CheckArgs &c, hipStream_t s);
+void launch_check(const CheckArgs &c, hipStream_t s);
 size_t check_part_bytes(int64_t parts);
 
 // k_mse.hip: the FP8 MSE candidate search (fq_mse.h) -- the candidate pre-kernel, the search kernel

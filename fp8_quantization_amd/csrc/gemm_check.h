@@ -6,21 +6,33 @@
 // and reduces the error statistics of fp8a_check_stats (include/fp8approx.h) on the device.
 //
 // A literal kernel on purpose: it shares no code with the production GEMM paths it cross-checks
-// (matrix-core, tile-table, depthwise) beyond the element codecs of fp8approx_device.h, and G comes
-// from its definition -- any fp32 operand, on the FP8 grid or off it.
+// (matrix-core, tile-table, depthwise, batched) beyond the element codecs of fp8approx_device.h, and
+// G comes from its definition -- any fp32 operand, on the FP8 grid or off it.
 //
-// Tiling: a workgroup of 256 threads owns a 64 x 64 output tile (thread = 4 x 4 outputs, three fp32
-// accumulators each) and walks K in steps of 16.  Every step stages 64 x 16 A and 16 x 64 B
-// elements through LDS, decoded ONCE per element -- the value, 1 + mant 2^-M and a packed (expo,
-// subnormal flag, mant) word -- so a product costs the multiply, the table entry, the scale and the
-// two Q_R, not two operand decodes.  A rows are matrix rows or implicit-im2col rows (GemmArgs, as
-// load_A reads them); blockIdx.y is the convolution group.
+// One kernel body, gemm_check_kernel, for all three entries (fp8a_matmul_check, fp8a_bmm_check,
+// fp8a_conv2d_check): the per-product term is stated here once.  What it walks is a list of units -- the
+// one matrix product, the nb0 x nb1 batch items, or the convolution groups -- each an offset into A, B,
+// bB and the output (CheckArgs).  The two forms differ in the rows of this table only, and are the two
+// instances of template <bool CONV> (one kernel branching at run time measured 1 % slower on attention's
+// PV shape than the batched kernel it replaced):
+//                   matrix / batched form                        convolution form
+//   A               A + u0 sa0 + u1 sa1 + m lda + k,             implicit-im2col rows of the NCHW input,
+//                   (u0, u1) = (u / nb1, u % nb1)                input channels from u cig
+//   B               B + u0 sb0 + u1 sb1, by sbk, sbn             B + u b_gs, by sbk, sbn
+//   bB              every unit alike                             bB + u bb_gs
+//   output o        u M N + m ldc + n (items: dense, ldc = N)    (img ctot + u cog + n) hw + pix
+//   S index os      (u M + m) N + n                              o
+//
+// Tiling: a workgroup of 256 threads owns a 64 x 64 output tile of one unit (thread = 4 x 4 outputs,
+// three fp32 accumulators each) and walks K in steps of 16; the grid is flat, workgroup b = (unit
+// b / tiles, tile b % tiles).  Every step stages 64 x 16 A and 16 x 64 B elements through LDS,
+// decoded ONCE per element -- the value, 1 + mant 2^-M and a packed (expo, subnormal flag, mant)
+// word -- so a product costs the multiply, the table entry, the scale and the two Q_R, not two
+// operand decodes.
 //
 // Statistics: every workgroup reduces its threads' partials in LDS in a fixed tree order and
-// writes one CheckPart to the workspace; check_reduce_kernel (one workgroup) sums the parts in a
+// writes CheckPart b to the workspace; check_reduce_kernel (one workgroup) sums the parts in a
 // fixed order.  No floating-point atomics anywhere: two runs give identical bytes.
-//
-// gemm_bmm_check_kernel (below) is the same pass over fp8a_bmm's batched operands.
 #pragma once
 #include <float.h>
 
@@ -38,28 +50,42 @@ struct CheckPart {
     uint32_t pad;
 };
 
+// Everything the check reads (the header's table); fields of the other form stay zero.
 struct CheckArgs {
-    float *G;            // golden sums in C's layout, or nullptr
-    float *S;            // sum_k |v_k|, dense in C's index space (workspace)
+    const float *A, *B;  // A: the matrices, or the convolution's NCHW input
+    float *C, *G, *S;    // G: golden sums in C's layout, or nullptr; S: sum_k |v_k| (the workspace's head)
     const float *Cprod;  // the production result in C's layout, or nullptr
     fp8a_check_stats *stats;
-    CheckPart *part;     // [groups * tiles]
-    int64_t tiles_n;     // column tiles; blockIdx.x = tile_m * tiles_n + tile_n
-    // convolution group g = blockIdx.y: B += g * b_gs, bB += g * bb_gs, input channels from g * cig,
-    // output channels from g * cog
-    int64_t b_gs, bb_gs, cig, cog;
-    int groups;
+    CheckPart *part;     // [units * tiles]
+    int64_t units, tiles, tiles_n;  // tiles per unit / its column tiles: tile = tile_m * tiles_n + tile_n
+    int64_t M, N, K;     // one unit's extents
+    int64_t sbk, sbn;
+    // matrix / batched form
+    int64_t nb1, lda, sa0, sa1, sb0, sb1, ldc;
+    // convolution form
+    int conv;
+    int64_t b_gs, bb_gs, cig, cog, ctot;
+    int64_t Cin, H, W, Ho, Wo;
+    int kh, kw, sh, sw, ph, pw, dh, dw;
+    int E, Mw;
+    const int32_t *bA, *bB;
+    int64_t bBs;
+    const int32_t *bR;
+    uint32_t flags;
+    TablePack tab;
 };
 
 #if FP8A_OWN_CHECK
-__device__ __forceinline__ float check_load_A(const GemmArgs &p, int64_t cbase, int64_t m, int64_t k) {
-    if (!p.conv) return p.A[m * p.lda + k];
+// A(m, k) of one unit: A = the unit's matrix, or the input with the unit's channels from cbase.
+template <bool CONV>
+__device__ __forceinline__ float check_load_A(const CheckArgs &p, const float *A, int64_t cbase, int64_t m, int64_t k) {
+    if (!CONV) return A[m * p.lda + k];
     const int64_t hw = p.Ho * p.Wo, img = m / hw, pix = m - img * hw;
     const int64_t ho = pix / p.Wo, wo = pix - ho * p.Wo;
     const int64_t taps = (int64_t)p.kh * p.kw, c = k / taps, t = k - c * taps, ky = t / p.kw, kx = t - ky * p.kw;
     const int64_t hi = ho * p.sh - p.ph + ky * p.dh, wi = wo * p.sw - p.pw + kx * p.dw;
     if (hi < 0 || hi >= p.H || wi < 0 || wi >= p.W) return 0.0f;
-    return p.X[((img * p.Cin + cbase + c) * p.H + hi) * p.W + wi];
+    return A[((img * p.Cin + cbase + c) * p.H + hi) * p.W + wi];
 }
 
 // The decode of one staged operand element (v9:47-59): the s2n scale-up of a subnormal, then DEC.
@@ -90,19 +116,23 @@ __device__ __forceinline__ T check_block_reduce(T v, T *scratch, Op op) {
     return scratch[0];
 }
 
-__global__ __launch_bounds__(CK_NT) void gemm_check_kernel(const GemmArgs p, const CheckArgs c) {
+template <bool CONV>
+__global__ __launch_bounds__(CK_NT) void gemm_check_kernel(const CheckArgs p) {
     __shared__ float a_val[CK_BK][CK_P], a_fac[CK_BK][CK_P], b_val[CK_BK][CK_P], b_fac[CK_BK][CK_P];
     __shared__ int a_wrd[CK_BK][CK_P], b_wrd[CK_BK][CK_P];
     __shared__ float tabf[1024];  // 2^-M * table entry (the subtrahend of v9:182)
     __shared__ double red[CK_NT];
 
     const int tid = threadIdx.x, ty = tid >> 4, tx = tid & 15;
-    const int64_t grp = blockIdx.y;
-    const int64_t tile_m = blockIdx.x / c.tiles_n, tile_n = blockIdx.x - tile_m * c.tiles_n;
+    const int64_t u = (int64_t)blockIdx.x / p.tiles, tile = (int64_t)blockIdx.x - u * p.tiles;
+    const int64_t tile_m = tile / p.tiles_n, tile_n = tile - tile_m * p.tiles_n;
     const int64_t m0 = tile_m * CK_BM, n0 = tile_n * CK_BN;
-    const float *const Bg = p.B + grp * c.b_gs;
-    const int32_t *const bBg = p.bB + grp * c.bb_gs;
-    const int64_t cbase = grp * c.cig, coff = grp * c.cog;
+    // the unit's operands and output (the header's table)
+    const int64_t u0 = CONV ? 0 : u / p.nb1, u1 = u - u0 * p.nb1;
+    const float *const Au = CONV ? p.A : p.A + u0 * p.sa0 + u1 * p.sa1;
+    const float *const Bg = CONV ? p.B + u * p.b_gs : p.B + u0 * p.sb0 + u1 * p.sb1;
+    const int32_t *const bBg = p.bB + u * p.bb_gs;  // (bb_gs = 0: every matrix unit alike)
+    const int64_t cbase = u * p.cig, coff = u * p.cog, hw = p.Ho * p.Wo;
 
     const uint32_t flags = p.flags;
     const bool tb = flags & F_TB, s2n = flags & F_S2N, qbma = flags & F_QBMA, gclip = flags & F_GCLIP;
@@ -130,7 +160,7 @@ __global__ __launch_bounds__(CK_NT) void gemm_check_kernel(const GemmArgs p, con
     // the operand matrices are counted once: A by the first column tile, B by the first row tile
     const bool count_a = tile_n == 0, count_b = tile_m == 0;
     // staging order: the faster thread index runs along the operand's unit-stride dimension
-    const bool a_mfast = p.conv != 0, b_kfast = p.sbk == 1;
+    const bool a_mfast = CONV, b_kfast = p.sbk == 1;
 
     for (int64_t k0 = 0; k0 < p.K; k0 += CK_BK) {
         __syncthreads();
@@ -141,7 +171,7 @@ __global__ __launch_bounds__(CK_NT) void gemm_check_kernel(const GemmArgs p, con
                 const int mi = a_mfast ? (e & 63) : (e >> 4), ki = a_mfast ? (e >> 6) : (e & 15);
                 const int64_t m = m0 + mi, k = k0 + ki;
                 const bool in = m < p.M && k < p.K;
-                const float v = in ? check_load_A(p, cbase, m, k) : 0.0f;
+                const float v = in ? check_load_A<CONV>(p, Au, cbase, m, k) : 0.0f;
                 float fac;
                 int w;
                 bool normal;
@@ -231,24 +261,24 @@ __global__ __launch_bounds__(CK_NT) void gemm_check_kernel(const GemmArgs p, con
             const int64_t n = n0 + tx * 4 + j;
             if (n >= p.N) continue;
             int64_t o, os;  // index in C's layout / in the dense S image
-            if (!p.nchw) {
-                o = m * p.ldc + n;
-                os = m * p.N + n;
+            if (!CONV) {
+                os = (u * p.M + m) * p.N + n;
+                o = u * p.M * p.N + m * p.ldc + n;  // (ldc = N wherever there is more than one unit)
             } else {
-                const int64_t img = m / p.hw, pix = m - img * p.hw;
-                o = os = (img * p.ctot + coff + n) * p.hw + pix;
+                const int64_t img = m / hw, pix = m - img * hw;
+                o = os = (img * p.ctot + coff + n) * hw + pix;
             }
             const float cv = accC[i][j], gv = accG[i][j];
             p.C[o] = cv;
-            if (c.G) c.G[o] = gv;
-            c.S[os] = accS[i][j];
+            if (p.G) p.G[o] = gv;
+            p.S[os] = accS[i][j];
             const float e = fabsf(gv - cv);  // (fp32, as v9:146)
             me = fmaxf(me, e);
             se += (double)e;
             se2 += (double)e * (double)e;
             sg2 += (double)gv * (double)gv;
-            if (c.Cprod) {
-                const float d = fabsf(c.Cprod[o] - cv);
+            if (p.Cprod) {
+                const float d = fabsf(p.Cprod[o] - cv);
                 pa = fmaxf(pa, d);
                 pr = fmaxf(pr, d / fmaxf(accS[i][j], FLT_MIN));
             }
@@ -270,7 +300,7 @@ __global__ __launch_bounds__(CK_NT) void gemm_check_kernel(const GemmArgs p, con
     out.prod_max_abs = check_block_reduce(pa, redf, maxf);
     out.prod_max_rel = check_block_reduce(pr, redf, maxf);
     out.pad = 0;
-    if (tid == 0) c.part[grp * gridDim.x + blockIdx.x] = out;
+    if (tid == 0) p.part[blockIdx.x] = out;
 }
 
 // Sums the workgroups' parts in a fixed order (thread t takes parts t, t + 256, ...; then the LDS
@@ -308,7 +338,7 @@ __global__ __launch_bounds__(CK_NT) void check_reduce_kernel(const CheckArgs c, 
     pa = check_block_reduce(pa, redf, maxf);
     pr = check_block_reduce(pr, redf, maxf);
     if (threadIdx.x != 0) return;
-    const unsigned long long G = (unsigned long long)c.groups;
+    const unsigned long long G = (unsigned long long)c.units;
     const bool s2n = flags & F_S2N;
     fp8a_check_stats st;
     st.n_out = G * (unsigned long long)M * (unsigned long long)N;
@@ -328,219 +358,6 @@ __global__ __launch_bounds__(CK_NT) void check_reduce_kernel(const CheckArgs c, 
     *c.stats = st;
 }
 
-#endif  // FP8A_OWN_CHECK
-
-// ------------------------------------------------------------------------- batched form
-// gemm_bmm_check_kernel: the same pass over the batched product of fp8a_bmm (gemm_bmm.h) -- nb0 x nb1
-// items with two batch strides per operand, read in place; C, G, Cprod and S dense [nb0][nb1][M][N].  One
-// workgroup owns one 64 x 64 tile of one item; the grid is flat over (tile, item) in blockIdx.x, and
-// part b is workgroup b's, so check_reduce_kernel (groups = items) walks them in the same fixed order.
-// Int biases only (no tensor-bias semantics): bA, bR one value, bB shared or per column, every item alike.
-struct BmmCheckArgs {
-    const float *A, *B;
-    float *C, *G, *S;        // G: nullptr or C's layout; S: the workspace's head
-    const float *Cprod;      // the production result, dense like C, or nullptr
-    CheckPart *part;         // [items * tiles]
-    int64_t nb1;             // the inner batch extent: item z = (z / nb1, z % nb1)
-    int64_t M, N, K;
-    int64_t lda, sa0, sa1;   // A(i0, i1, m, k) = A[i0 sa0 + i1 sa1 + m lda + k]
-    int64_t sbk, sbn, sb0, sb1;
-    int64_t tiles_n, tiles;  // column tiles / tiles per item; block b = (tile b % tiles, item b / tiles)
-    int E, Mw;
-    const int32_t *bA, *bB;
-    int64_t bBs;
-    const int32_t *bR;
-    uint32_t flags;
-    TablePack tab;
-};
-
-// k_check.hip: the kernel over items * a.tiles workgroups, then check_reduce_kernel on c (part, stats, Cprod)
-void launch_bmm_check(const BmmCheckArgs &a, const CheckArgs &c, int64_t items, hipStream_t s);
-
-#if FP8A_OWN_CHECK
-// One product from its staged decodes (gemm_check_kernel's per-product body, operation for operation):
-// the golden term g (v9:30-36) and the approx term v (v9:66-108, before its Q_R).  Returns whether the
-// term counts as normal in R_3d (v9:87; never with s2n).
-__device__ __forceinline__ bool check_product(float a, float b, float fa, float fb, int wa, int wb, int bsum,
-                                              const DFmt &fR, const float *tabf, int nm, float scale, bool approx,
-                                              bool s2n, bool qbma, bool gclip, float &g, float &v) {
-    const int eA = wa >> 8, mA = wa & 0x7F, eB = wb >> 8, mB = wb & 0x7F;
-    const bool as = (wa & 0x80) != 0, bs = (wb & 0x80) != 0;
-    g = a * b;
-    const bool zero = (g == 0.0f);
-    if (qbma) g = exact_q(g, fR, gclip);
-    const int aexp = eA + eB - bsum;
-    const float sgn = (g < 0.0f) ? -1.0f : 1.0f;
-    float mp = fa * fb;
-    if (approx) mp = mp - tabf[mA * nm + mB];
-    bool norm = false;
-    if (s2n) {
-        v = p2(aexp - fR.b) * mp * sgn;
-        if (as) v = v / scale;
-        if (bs) v = v / scale;
-        if (zero) v = 0.0f;
-    } else {
-        norm = (eA > 0) && (eB > 0) && (fabsf(g) >= fR.mn);
-        v = norm ? p2(aexp - fR.b) * mp * sgn : g;
-    }
-    return norm;
-}
-
-__global__ __launch_bounds__(CK_NT) void gemm_bmm_check_kernel(const BmmCheckArgs p) {
-    __shared__ float a_val[CK_BK][CK_P], a_fac[CK_BK][CK_P], b_val[CK_BK][CK_P], b_fac[CK_BK][CK_P];
-    __shared__ int a_wrd[CK_BK][CK_P], b_wrd[CK_BK][CK_P];
-    __shared__ float tabf[1024];  // 2^-M * table entry (the subtrahend of v9:182)
-    __shared__ double red[CK_NT];
-
-    const int tid = threadIdx.x, ty = tid >> 4, tx = tid & 15;
-    const int64_t z = (int64_t)blockIdx.x / p.tiles, bid = (int64_t)blockIdx.x - z * p.tiles;
-    const int64_t tile_m = bid / p.tiles_n, tile_n = bid - tile_m * p.tiles_n;
-    const int64_t m0 = tile_m * CK_BM, n0 = tile_n * CK_BN;
-    const int64_t i0 = z / p.nb1, i1 = z - i0 * p.nb1;
-    const float *const A = p.A + i0 * p.sa0 + i1 * p.sa1;
-    const float *const B = p.B + i0 * p.sb0 + i1 * p.sb1;
-    const int64_t obase = z * p.M * p.N;  // the item's image in C, G, Cprod and S
-
-    const uint32_t flags = p.flags;
-    const bool s2n = flags & F_S2N, qbma = flags & F_QBMA, gclip = flags & F_GCLIP, approx = flags & F_APPROX;
-    const int M = p.Mw, nm = 1 << M;
-    const DFmt fA = dfmt(p.E, M, *p.bA, false), fR = dfmt(p.E, M, *p.bR, false);
-    const float scale = (float)nm, ulp = p2(-M);
-
-    for (int i = tid; i < nm * nm; i += CK_NT) tabf[i] = ulp * (float)p.tab.raw[i];
-
-    // this thread's four columns: the exponent offset bA + bB - bR of each (v9:66)
-    int bsum[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int64_t n = min(n0 + tx * 4 + j, p.N - 1);
-        bsum[j] = fA.b + p.bB[n * p.bBs] - fR.b;
-    }
-
-    float accC[4][4], accG[4][4], accS[4][4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) accC[i][j] = accG[i][j] = accS[i][j] = 0.0f;
-    unsigned long long an = 0, bn = 0, rn = 0;
-    // every item's operands are counted once: A by the first column tile of each of its row tiles, B by
-    // its first row tile
-    const bool count_a = tile_n == 0, count_b = tile_m == 0;
-    const bool b_kfast = p.sbk == 1;  // (a transposed K: lanes along k)
-
-    for (int64_t k0 = 0; k0 < p.K; k0 += CK_BK) {
-        __syncthreads();
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int e = tid + r * CK_NT;  // 0 .. 1023
-            {   // A element (mi, ki): lanes along k
-                const int mi = e >> 4, ki = e & 15;
-                const int64_t m = m0 + mi, k = k0 + ki;
-                const bool in = m < p.M && k < p.K;
-                const float v = in ? A[m * p.lda + k] : 0.0f;
-                float fac;
-                int w;
-                bool normal;
-                check_decode(v, fA, s2n, fac, w, normal);
-                a_val[ki][mi] = v;
-                a_fac[ki][mi] = fac;
-                a_wrd[ki][mi] = w;
-                if (count_a && in && normal) ++an;
-            }
-            {   // B element (ki, ni)
-                const int ni = b_kfast ? (e >> 4) : (e & 63), ki = b_kfast ? (e & 15) : (e >> 6);
-                const int64_t n = n0 + ni, k = k0 + ki;
-                const bool in = n < p.N && k < p.K;
-                const DFmt fB = dfmt(p.E, M, p.bB[min(n, p.N - 1) * p.bBs], false);
-                const float v = in ? B[k * p.sbk + n * p.sbn] : 0.0f;
-                float fac;
-                int w;
-                bool normal;
-                check_decode(v, fB, s2n, fac, w, normal);
-                b_val[ki][ni] = v;
-                b_fac[ki][ni] = fac;
-                b_wrd[ki][ni] = w;
-                if (count_b && in && normal) ++bn;
-            }
-        }
-        __syncthreads();
-        const int kend = (int)min<int64_t>(CK_BK, p.K - k0);  // (the K tail is not padded)
-        uint32_t rn_tile = 0;
-        for (int kk = 0; kk < kend; ++kk) {
-            const float4 av = *reinterpret_cast<const float4 *>(&a_val[kk][ty * 4]);
-            const float4 af = *reinterpret_cast<const float4 *>(&a_fac[kk][ty * 4]);
-            const int4 aw = *reinterpret_cast<const int4 *>(&a_wrd[kk][ty * 4]);
-            const float4 bv = *reinterpret_cast<const float4 *>(&b_val[kk][tx * 4]);
-            const float4 bf = *reinterpret_cast<const float4 *>(&b_fac[kk][tx * 4]);
-            const int4 bw = *reinterpret_cast<const int4 *>(&b_wrd[kk][tx * 4]);
-            const float a4[4] = {av.x, av.y, av.z, av.w}, fa4[4] = {af.x, af.y, af.z, af.w};
-            const float b4[4] = {bv.x, bv.y, bv.z, bv.w}, fb4[4] = {bf.x, bf.y, bf.z, bf.w};
-            const int wa4[4] = {aw.x, aw.y, aw.z, aw.w}, wb4[4] = {bw.x, bw.y, bw.z, bw.w};
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    float g, v;
-                    const bool norm = check_product(a4[i], b4[j], fa4[i], fb4[j], wa4[i], wb4[j], bsum[j], fR, tabf,
-                                                    nm, scale, approx, s2n, qbma, gclip, g, v);
-                    const bool inside = (m0 + ty * 4 + i < p.M) && (n0 + tx * 4 + j < p.N);
-                    rn_tile += (norm && inside) ? 1u : 0u;
-                    if (qbma) v = exact_q(v, fR, gclip);
-                    accC[i][j] += v;
-                    accG[i][j] += g;
-                    accS[i][j] += fabsf(v);
-                }
-            }
-        }
-        rn += rn_tile;
-    }
-
-    // stores and this thread's error partials (outputs in (i, j) order)
-    double se = 0.0, se2 = 0.0, sg2 = 0.0;
-    float me = 0.0f, pa = 0.0f, pr = 0.0f;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int64_t m = m0 + ty * 4 + i;
-        if (m >= p.M) continue;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int64_t n = n0 + tx * 4 + j;
-            if (n >= p.N) continue;
-            const int64_t o = obase + m * p.N + n;
-            const float cv = accC[i][j], gv = accG[i][j];
-            p.C[o] = cv;
-            if (p.G) p.G[o] = gv;
-            p.S[o] = accS[i][j];
-            const float e = fabsf(gv - cv);  // (fp32, as v9:146)
-            me = fmaxf(me, e);
-            se += (double)e;
-            se2 += (double)e * (double)e;
-            sg2 += (double)gv * (double)gv;
-            if (p.Cprod) {
-                const float d = fabsf(p.Cprod[o] - cv);
-                pa = fmaxf(pa, d);
-                pr = fmaxf(pr, d / fmaxf(accS[i][j], FLT_MIN));
-            }
-        }
-    }
-    auto addd = [](double x, double y) { return x + y; };
-    auto addu = [](unsigned long long x, unsigned long long y) { return x + y; };
-    auto maxf = [](float x, float y) { return fmaxf(x, y); };
-    unsigned long long *const redu = reinterpret_cast<unsigned long long *>(red);
-    float *const redf = reinterpret_cast<float *>(red);
-    CheckPart out;
-    out.sum_err = check_block_reduce(se, red, addd);
-    out.sum_err2 = check_block_reduce(se2, red, addd);
-    out.sum_gold2 = check_block_reduce(sg2, red, addd);
-    out.a_norm = check_block_reduce(an, redu, addu);
-    out.b_norm = check_block_reduce(bn, redu, addu);
-    out.r_norm = check_block_reduce(rn, redu, addu);
-    out.max_err = check_block_reduce(me, redf, maxf);
-    out.prod_max_abs = check_block_reduce(pa, redf, maxf);
-    out.prod_max_rel = check_block_reduce(pr, redf, maxf);
-    out.pad = 0;
-    if (tid == 0) p.part[blockIdx.x] = out;
-}
 #endif  // FP8A_OWN_CHECK
 
 }  // namespace fp8a

@@ -1,4 +1,4 @@
-"""The batched self-check on the GPU (fp8a_bmm_check, gemm_bmm_check_kernel): per batch item
+"""The batched self-check on the GPU (fp8a_bmm_check, gemm_check_kernel over batch items): per batch item
 the approx sum C and its scale S against the CPU oracle and the golden sum G against a host golden built from
 its definition (v9:30-36); the counts against numpy + oracle.decompose; the whole call against per-item
 fp8a_matmul_check calls bit for bit; the statistics against a recomputation from the returned tensors; off-grid
