@@ -881,7 +881,11 @@ struct MxPlan {
     int64_t kpad, npad;
     bool any() const { return (f8 || tt || v5mx) && on; }
 };
-static MxPlan mx_plan(int E, int Mw, uint32_t flags, const TablePack &tab, int mode, int64_t N, int64_t K,
+// gemm_f8mx_kernel decomposes blockIdx.x, its tile index and its rows with 32-bit fastdiv (dividends below
+// 2^31).  Rows: M <= a_words < 2^30 (a conv's word image has at least one word per output pixel, a matrix
+// kpad per row; the fp32-staged sources are bounded the same way, xm_af32).  Blocks: tiles x splits, bounded
+// here with the smallest tile of either dimension (128 rows, 16 columns) and the splits run_gemm can choose.
+static MxPlan mx_plan(int E, int Mw, uint32_t flags, const TablePack &tab, int mode, int64_t M, int64_t N, int64_t K,
                       int64_t a_words) {
     MxPlan p;
     p.f8 = f8_form(E, Mw, flags, tab);
@@ -891,6 +895,8 @@ static MxPlan mx_plan(int E, int Mw, uint32_t flags, const TablePack &tab, int m
     p.kpad = (K + BK - 1) / BK * BK;
     p.npad = (N + BN - 1) / BN * BN;
     p.fits32 = a_words < (1ll << 30) && p.kpad * p.npad * 4 < (1ll << 32);
+    if (p.f8 && p.fits32 && M > 0 && N > 0 && K > 0)
+        p.fits32 = M <= a_words && ((M + 127) / 128) * ((N + 15) / 16) * choose_splits(M, N, K) < (1ll << 31);
     return p;
 }
 
@@ -1108,7 +1114,7 @@ static int run_gemm(GemmArgs &a, const int32_t *table, void *ws, size_t ws_bytes
     // E4M3 / E5M2 with a non-negative (or no) table (xm_table_form), s2n and per-product quantization:
     // the LUT + hardware fp8 / bf8 form (FP8A_NO_F8=1 keeps the arithmetic form, for comparison)
     const int64_t a_words = xm_a_words(a);
-    const MxPlan mx = mx_plan(a.E, a.Mw, a.flags, a.tab, mode, a.N, a.K, a_words);
+    const MxPlan mx = mx_plan(a.E, a.Mw, a.flags, a.tab, mode, a.M, a.N, a.K, a_words);
     if (mx.f8) mode = TM_F8;
     const int64_t total = a.M * a.N;
     const unsigned eblocks = (unsigned)std::min<int64_t>((total + 255) / 256, 4096);
@@ -1837,14 +1843,16 @@ static int grouped_conv_impl(const float *x, const float *w, float *y, int64_t B
 int fp8a_clock_stats(uint64_t *out, int reset) {
     if (out == nullptr) return fail(FP8A_EINVAL, "null pointer");
     if (hipDeviceSynchronize() != hipSuccess) return hip_check("fp8a_clock_stats");
-    unsigned long long v[3] = {0, 0, 0};
+    // reset bit 0: zero the sums after reading; bit 1: out = the cycle sum's three phases (before the first
+    // barrier, the K loop, after it: gemm_f8mx.h g_clk[3..5]) instead of {cycles, 100 MHz ticks, workgroups}
+    unsigned long long v[6] = {0, 0, 0, 0, 0, 0};
     int (*parts[3])(unsigned long long *, bool) = {f8mx_clock_xf0, f8mx_clock_xf1, f8mx_clock_xf2};
     for (auto f : parts) {
-        unsigned long long w[3] = {0, 0, 0};
-        if (f(w, reset != 0) != 0) return hip_check("fp8a_clock_stats");
-        for (int i = 0; i < 3; ++i) v[i] += w[i];
+        unsigned long long w[6] = {0, 0, 0, 0, 0, 0};
+        if (f(w, (reset & 1) != 0) != 0) return hip_check("fp8a_clock_stats");
+        for (int i = 0; i < 6; ++i) v[i] += w[i];
     }
-    for (int i = 0; i < 3; ++i) out[i] = v[i];
+    for (int i = 0; i < 3; ++i) out[i] = v[i + ((reset & 2) ? 3 : 0)];
     return FP8A_OK;
 }
 
@@ -2600,7 +2608,7 @@ static int conv2d_impl(const ConvCall &call) {
         if (c.flags & F_V5) mode = TM_V5;  // (as run_gemm)
         const WordImage wi = word_image(g.H, g.W, g.ph, g.pw);
         const int64_t a_words = g.Bn * g.cig * wi.H * wi.W;  // as xm_a_words / run_gemm
-        const MxPlan mx = mx_plan(c.E, c.Mw, c.flags & ~F_TB, tp, mode, g.cog, g.Kg, a_words);
+        const MxPlan mx = mx_plan(c.E, c.Mw, c.flags & ~F_TB, tp, mode, g.Mrows, g.cog, g.Kg, a_words);
         // every matrix-core form applies fq in its A pre-decode (xm_decode_a), so the convolution fuses for all
         // three; the workspace test is the conservative one (the whole size query), where run_gemm's is exact
         const bool fused = mx.any() && mx.fits32 &&
@@ -2726,7 +2734,7 @@ int fp8a_conv2d_wants_image(int64_t Cout, int kh, int kw, int ph, int pw, int gr
         return tbx ? 2 : 0;
     }
     // (the forms only: the shape-dependent part of run_gemm's decision -- offsets, workspace -- is not known here)
-    const MxPlan mx = mx_plan(E, Mw, flags & ~F_TB, tp, (flags & F_V5) ? TM_V5 : mode, Cout, 0, 0);
+    const MxPlan mx = mx_plan(E, Mw, flags & ~F_TB, tp, (flags & F_V5) ? TM_V5 : mode, 0, Cout, 0, 0);
     if (groups != 1 || !mx.on) return 0;
     // the v5 matrix-core form (gemm_v5mx_kernel): its words (v5_word_a) when unpadded (an image's
     // border holds the E4M3 / E5M2 form's zero word, fp8a_word_image_init); emitted by the staged
@@ -2898,7 +2906,7 @@ int fp8a_matmul_block(const float *A, int64_t lda, const float *B, int64_t sbk, 
         rc = check_format(E, Mw);
         if (!rc) rc = pack_table(table, Mw, (flags & F_APPROX) != 0, tp, mode);
         if (rc) return rc;
-        const MxPlan mx = mx_plan(E, Mw, flags, tp, mode, N, K, M * ((K + BK - 1) / BK * BK));
+        const MxPlan mx = mx_plan(E, Mw, flags, tp, mode, M, N, K, M * ((K + BK - 1) / BK * BK));
         // the E4M3 / E5M2 form only (the linear layers' tile-table launches keep the separate fake-quant pass);
         // the conservative workspace test, as conv2d_impl
         const bool fused = mx.f8 && mx.on && mx.fits32 && rest >= gemm_workspace_bytes(M, N, K, 0);

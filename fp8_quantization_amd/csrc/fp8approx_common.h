@@ -233,6 +233,14 @@ struct GemmArgs {
     uint32_t arena_clr16;
     float *post_bout;    // post_fq's bias outputs (its custom_bias), written by gemm_exact_kernel, or nullptr
     int32_t *post_ibout;
+    // gemm_f8mx_kernel's 32-bit tile setup, made once per launch by its launcher (launch_shape, k_f8mx.hip) like
+    // kk_mul / kw_mul above; appended, so every earlier field keeps its offset: the tile counts and the fastdiv
+    // magics of blockIdx.x / tiles, tile / row tiles, row / (Ho * Wo), pixel / Wo (conv) and row / hw (an NCHW
+    // store).  Every dividend is below 2^31 (mx_plan's fits32, fp8approx.hip).  No other kernel reads them.
+    uint32_t xm_tiles, xm_num_mt;
+    uint32_t xt_mul, xt_shift, xmt_mul, xmt_shift;
+    uint32_t ohw_mul, ohw_shift, owo_mul, owo_shift;
+    uint32_t shw_mul, shw_shift;
 };
 
 // Fallback flag word bits: FB_ANY = some output unit needs the exact kernel, FB_ALL = every
@@ -320,11 +328,13 @@ __device__ __forceinline__ float4 post4(const GemmArgs &p, int64_t o, float4 v, 
 
 // y = x * scale + shift with scale = gamma * invstd, shift = beta - mean * scale (ATen's eval
 // batch-norm transform), then the activation clamp; c = output channel
-__device__ __forceinline__ float epi(const float2 *ep, int act, float lo, float hi, int64_t c, float x) {
-    if (ep == nullptr) return x;
-    const float2 e = ep[c];
+__device__ __forceinline__ float epi(float2 e, int act, float lo, float hi, float x) {  // (the channel's pair, loaded)
     const float v = __fmaf_rn(x, e.x, e.y);
     return act ? fminf(fmaxf(v, lo), hi) : v;
+}
+__device__ __forceinline__ float epi(const float2 *ep, int act, float lo, float hi, int64_t c, float x) {
+    if (ep == nullptr) return x;
+    return epi(ep[c], act, lo, hi, x);
 }
 
 // n / d for 0 <= n < 2^31 via one mulhi: q = (mulhi(n, mul) + n) >> shift (Granlund-Montgomery).

@@ -558,7 +558,9 @@ __global__ void xm_decode_b(const GemmArgs p, int64_t kpad);
 #ifndef FP8A_CLOCK_STAMP
 #define FP8A_CLOCK_STAMP 0
 #endif
-__device__ unsigned long long g_clk[3];
+// g_clk[3..5]: the s_memtime delta split three ways -- up to the first barrier (the tile setup), the K loop, after
+// the K loop's last barrier (the NaN test, the store, the split sum): FP8A_CLK_MARK stamps the two boundaries.
+__device__ unsigned long long g_clk[6];
 // Launches (the halved-block reruns apart) whose tile-table build wrote the positive-sign rows only
 // [0] / both halves [1]: thread 0 of block 0 counts; read per translation unit (k_f8mx.hip) by
 // fp8a_xm_sign_stats.
@@ -571,10 +573,15 @@ __device__ unsigned long long g_xm_sign[2];
         atomicAdd(&g_clk[0], (unsigned long long)(clk_t1 - clk_t0));                                   \
         atomicAdd(&g_clk[1], (unsigned long long)(clk_r1 - clk_r0));                                   \
         atomicAdd(&g_clk[2], 1ull);                                                                    \
+        atomicAdd(&g_clk[3], (unsigned long long)(clk_ta - clk_t0));                                   \
+        atomicAdd(&g_clk[4], (unsigned long long)(clk_tb - clk_ta));                                   \
+        atomicAdd(&g_clk[5], (unsigned long long)(clk_t1 - clk_tb));                                   \
     }
+#define FP8A_CLK_MARK(name) const uint64_t name = __builtin_amdgcn_s_memtime();
 #else
 #define FP8A_CLK_BEGIN
 #define FP8A_CLK_END
+#define FP8A_CLK_MARK(name)
 #endif
 #ifndef XM_WAVES
 // register bound: 5 waves / SIMD (<= 96 VGPRs; the 128 x 64 instance needs 82).  At 6 waves (80
@@ -644,6 +651,139 @@ template <bool EMIT> struct XmPipe<1, EMIT, true> { static constexpr int value =
 // per staged tile and lane 2 A pair reads and 4 address ops instead of 8 and 16.  Accumulator dq[4 rb + cg]
 // is (row block 2 w + rb, column group cg); it still takes one MFMA per staged tile, in K order, over the same
 // 128 codes converted from the same table and scale words: the same bits as the mapping by columns.
+// gemm_f8mx_kernel's store (XM_SETUP64 = 0).  What a tile's slabs share, taken once per tile:
+// the uniform tests (a split launch's raw partials, the output mapping, the vector forms' alignment, the BN
+// epilogue), the output base and strides, and the BN parameters of the thread's four channels (nb ..).
+struct XmStoreTile {
+    float *C;
+    bool partial, nchw, ep, rvec, nvec;  // rvec / nvec: the row-major / NCHW 16-byte forms' uniform conditions
+    int64_t ldc, ctot, hw, istep;        // istep = (ctot - 1) hw: from an image's last pixel to the next one's first, less 1
+    int64_t cn;                          // coff + nb
+    uint32_t nb;
+    float2 e[TN];                        // (EPT: tiles of more than one slab; else loaded where the slab uses them)
+};
+template <bool EPT>
+__device__ __forceinline__ XmStoreTile xm_store_tile(const GemmArgs &p, uint32_t split, uint32_t nb) {
+    XmStoreTile t;
+    t.partial = p.splits > 1;
+    t.C = t.partial ? p.part + (int64_t)split * p.M * p.N : p.C;
+    t.nchw = p.nchw != 0;
+    t.ldc = t.partial ? p.N : p.ldc;
+    t.ctot = t.partial ? p.N : p.ctot;
+    t.hw = p.hw;
+    t.istep = (t.ctot - 1) * t.hw;
+    t.cn = (t.partial ? 0 : p.coff) + (int64_t)nb;
+    t.nb = nb;
+    const bool al16 = (((uintptr_t)t.C) & 15) == 0;
+    t.rvec = al16 && (t.ldc & 3) == 0;
+    t.nvec = al16 && (p.hw & 3) == 0;
+    t.ep = !t.partial && p.ep != nullptr;
+#pragma unroll
+    for (int j = 0; j < TN; ++j)
+        t.e[j] = EPT && t.ep ? p.ep[p.coff + (int64_t)min(nb + (uint32_t)j, (uint32_t)p.N - 1u)] : make_float2(0.0f, 0.0f);
+    return t;
+}
+// One thread's TM x TN outputs of a slab (rows mb .. mb + 3, columns t.nb .. + 3): store_tile's values -- epi,
+// post1 / post4, emit1 / emit4 and the header records, the same code in the same order -- with (img, pix) by
+// the launcher's magic in 32-bit arithmetic, one 64-bit multiply per slab for the first output offset and
+// adds from there (the NCHW scalar form steps rows across image ends by t.istep).
+template <bool EMIT, bool GELU, bool EPT>
+__device__ __forceinline__ void store_tile_xm(const GemmArgs &p, const XmStoreTile &t, uint32_t mb,
+                                              float (&acc)[TM][TN], const StoreCtx &sc) {
+    constexpr bool RAW = FP8A_RAW_STORE_DIAG && EMIT;
+    constexpr bool FQF = true;
+    const bool partial = t.partial;
+    float *const C = t.C;
+    const uint32_t M = (uint32_t)p.M, N = (uint32_t)p.N, nb = t.nb;
+    if (!RAW && t.ep) {  // fused BN + activation (split-K applies it in the reduction)
+#pragma unroll
+        for (int j = 0; j < TN; ++j) {
+            const float2 e = EPT ? t.e[j] : p.ep[p.coff + (int64_t)min(nb + (uint32_t)j, N - 1u)];
+#pragma unroll
+            for (int i = 0; i < TM; ++i) acc[i][j] = epi(e, p.ep_act, p.ep_lo, p.ep_hi, acc[i][j]);
+        }
+    }
+    const float pb = sc.pb;
+    const GemmArgs &q = p;
+    const bool emit = EMIT && !RAW && !partial && p.em.w != nullptr;
+    const EmitCtx &ec = sc.ec;
+    const FqFast &pk = sc.pk;
+    uint32_t sehi = 0, neg = 0;
+    auto fin1 = [&](int64_t o, float v) {
+        if (partial || RAW) return v;
+        v = post1<GELU, FQF>(q, o, v, pb, pk);
+        if (emit) emit1<FQF>(q, ec, o, v, sehi, neg);
+        return v;
+    };
+    auto fin4 = [&](int64_t o, float4 v) {
+        if (partial || RAW) return v;
+        v = post4<GELU, FQF>(q, o, v, pb, pk);
+        if (emit) emit4<FQF>(q, ec, o, v, sehi, neg);
+        return v;
+    };
+    if (!t.nchw) {
+        int64_t o = (int64_t)mb * t.ldc + nb;
+        const bool v4 = t.rvec && nb + TN <= N;
+#pragma unroll
+        for (int i = 0; i < TM; ++i) {
+            if (mb + i < M) {
+                if (v4) {
+                    *reinterpret_cast<float4 *>(&C[o]) = fin4(o, make_float4(acc[i][0], acc[i][1], acc[i][2], acc[i][3]));
+                } else {
+#pragma unroll
+                    for (int j = 0; j < TN; ++j)
+                        if (nb + j < N) C[o + j] = fin1(o + j, acc[i][j]);
+                }
+            }
+            o += t.ldc;
+        }
+    } else {
+        // NCHW: the thread's 4 rows are 4 consecutive pixels; when they lie in one image and start 16-B
+        // aligned, each output channel gets one float4 store.
+        const uint32_t hw = (uint32_t)p.hw, img = fastdiv(mb, p.shw_mul, p.shw_shift), pix = mb - img * hw;
+        const bool vec = t.nvec && pix + TM <= hw && mb + TM <= M;
+        int64_t o = ((int64_t)img * t.ctot + t.cn) * t.hw + pix;
+        if (vec) {
+#pragma unroll
+            for (int j = 0; j < TN; ++j) {
+                if (nb + j < N)
+                    *reinterpret_cast<float4 *>(&C[o]) = fin4(o, make_float4(acc[0][j], acc[1][j], acc[2][j], acc[3][j]));
+                o += t.hw;
+            }
+        } else {
+            uint32_t px = pix;
+#pragma unroll
+            for (int i = 0; i < TM; ++i) {
+                if (mb + i < M) {
+                    int64_t oj = o;
+#pragma unroll
+                    for (int j = 0; j < TN; ++j) {
+                        if (nb + j < N) C[oj] = fin1(oj, acc[i][j]);
+                        oj += t.hw;
+                    }
+                }
+                ++o;
+                if (++px == hw) {  // the next row opens the next image
+                    px = 0;
+                    o += t.istep;
+                }
+            }
+        }
+    }
+    if (emit) {
+        wave_max_atomic(p.em.invalid + 5, sehi);
+        wave_sign_record(p.em.invalid + 6, neg);
+    }
+}
+
+// Per-tile setup and store indexing: the block -> tile -> row decompositions run in 32-bit
+// arithmetic with fastdiv magics the launcher made (GemmArgs xm_tiles ..), the prologue's global loads go out
+// ahead of them, and the store (store_tile_xm below) takes its uniform tests and the thread's four channels'
+// BN parameters once per tile and advances output offsets by adds.  -DXM_SETUP64=1 (a build-time switch like
+// XM_PIPE_EMIT64, for A/B builds) restores the 64-bit `/` and `%` per tile, row and slab and store_tile.
+#ifndef XM_SETUP64
+#define XM_SETUP64 0
+#endif
 template <int NCG, int RB, bool AF32, int XF, bool EMIT, bool FIX = false, int PIPE = 0, bool WROWS = false>
 __global__ __launch_bounds__(256, (XmWaves<AF32, EMIT>::value)) void gemm_f8mx_kernel(const GemmArgs p) {
     static_assert(PIPE == 0 || (!AF32 && XF != 2), "PIPE: the word-staged plain forms only");
@@ -659,15 +799,29 @@ __global__ __launch_bounds__(256, (XmWaves<AF32, EMIT>::value)) void gemm_f8mx_k
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int wvu = __builtin_amdgcn_readfirstlane(wv);
     const int wc = wvu % NCG, wr = wvu / NCG;  // the wave's column group and row group
+#if XM_SETUP64
     const int64_t num_mt = (p.M + BMT - 1) / BMT;
     const int64_t tiles = num_mt * ((p.N + BNT - 1) / BNT);
     const int64_t bid = (int64_t)blockIdx.x % tiles, split = (int64_t)blockIdx.x / tiles;
     const int64_t m0 = (bid % num_mt) * BMT;
     const int64_t n0 = (bid / num_mt) * BNT;
+#else
+    // The prologue's dependent global loads first -- this thread's 16 bytes of the table image (below), the
+    // sign words and *p.bR; each is waited for at its first use, behind the index arithmetic.
+    uint4 lutv = make_uint4(0u, 0u, 0u, 0u);
+    if (4 * tid < XM_LUT_WORDS) lutv = *reinterpret_cast<const uint4 *>(&p.lutw[4 * tid]);
+    // blockIdx.x -> (split, tile) -> (row tile, column tile) with the launcher's magics (GemmArgs xt_mul ..;
+    // every dividend < 2^31: mx_plan), on the scalar unit
+    const uint32_t splitu = fastdiv(blockIdx.x, p.xt_mul, p.xt_shift), bidu = blockIdx.x - splitu * p.xm_tiles;
+    const uint32_t ntu = fastdiv(bidu, p.xmt_mul, p.xmt_shift);
+    const uint32_t m0u = (bidu - ntu * p.xm_num_mt) * (uint32_t)BMT, n0u = ntu * (uint32_t)BNT;
+    const int64_t bid = bidu, split = splitu, m0 = m0u, n0 = n0u;  // (the fallback marks and the split sum)
+#endif
     // The build writes the table rows of s_a = 1 (8 + m_a) only when an A word of the launch addresses
     // them: the pre-pass left that in the spread sign words (xm_record_sign), the producer of the
     // word image in flag[3] -- one load per wave, lanes 0-31 a spread word each, the rest flag[3].
     // Wave-uniform, read once.  (AF32 decodes A while staging and cannot know: both halves.)
+#if XM_SETUP64
     bool both = true;
     if (!AF32 && p.xm_signs)
         both = __any(__hip_atomic_load(p.flag + (lane < XM_SIGN_NW ? XM_SIGN_W0 + lane : 3), __ATOMIC_RELAXED,
@@ -675,6 +829,15 @@ __global__ __launch_bounds__(256, (XmWaves<AF32, EMIT>::value)) void gemm_f8mx_k
     if (XF != 2 && blockIdx.x == 0 && tid == 0) atomicAdd(&g_xm_sign[both ? 1 : 0], 1ull);
     if (XF == 2 && !xm_half_gate(p, m0, BMT, n0, BNT)) return;  // (a tile the plain form completed)
     const int kbeg = (int)(split * p.kchunk), kend = (int)min(p.K, (int64_t)kbeg + p.kchunk), K32 = (int)p.K;
+#else
+    // (the load here; the wave's vote on it right before the K loop's first barrier)
+    uint32_t signw = 1u;
+    if (!AF32 && p.xm_signs)
+        signw = __hip_atomic_load(p.flag + (lane < XM_SIGN_NW ? XM_SIGN_W0 + lane : 3), __ATOMIC_RELAXED,
+                                  __HIP_MEMORY_SCOPE_WORKGROUP);  // (written by earlier kernels only)
+    if (XF == 2 && !xm_half_gate(p, m0, BMT, n0, BNT)) return;  // (a tile the plain form completed)
+    const int K32 = (int)p.K, kbeg = (int)splitu * (int)p.kchunk, kend = min(K32, kbeg + (int)p.kchunk);
+#endif
     const int bR = *p.bR;
     // AF32: the A operand's bias (the fused input quantizer's, written once for the gated kernels)
     float fmx = 0.0f, fbias = 0.0f;
@@ -693,8 +856,12 @@ __global__ __launch_bounds__(256, (XmWaves<AF32, EMIT>::value)) void gemm_f8mx_k
     const uint32_t emnA = (uint32_t)(128 - bA) << 23;
 
     // table: copied from the launch's pre-computed image (xm_decode_b), 16-B per thread and step
+#if XM_SETUP64
     for (int e = 4 * tid; e < XM_LUT_WORDS; e += 4 * NT)
         *reinterpret_cast<uint4 *>(&sm.lut[e]) = *reinterpret_cast<const uint4 *>(&p.lutw[e]);
+#else
+    static_assert(XM_LUT_WORDS <= 4 * NT, "one 16-byte step per thread (lutv, loaded at the top)");
+#endif
 
     // tile-table build units e = tid + NT u (NBU per tile): (m_a pair q4, column block btx,
     // K-step bkk[u]); the 8 lanes of a ds_write_b128 group are 4 q4 x an even and an odd K-step
@@ -706,7 +873,11 @@ __global__ __launch_bounds__(256, (XmWaves<AF32, EMIT>::value)) void gemm_f8mx_k
     // K-step + u * BKU -- the per-unit offsets are uniform (soffset / immediates), one VGPR each
     constexpr int BKU = 2 * (NT / (8 * TXN));
     const int bkk0 = 2 * (tid / (8 * TXN)) + ((tid >> 2) & 1);
+#if XM_SETUP64
     const uint32_t boff0 = (uint32_t)(kbeg + bkk0) * hq8 + (uint32_t)(n0 / 2 + 2 * btx) * 8u;  // pair 2 btx: 16-B aligned
+#else
+    const uint32_t boff0 = (uint32_t)(kbeg + bkk0) * hq8 + (n0u / 2u + 2u * (uint32_t)btx) * 8u;  // pair 2 btx: 16-B aligned
+#endif
     const bool build = NBU % NT == 0 || tid < NBU;  // (NCG = 1: half the threads build)
 #if XM_BDMA
     // this thread's DMA chunk (tid < XBK TXN): K-step kbeg + tid / TXN, pairs n0 / 2 + 2 (tid % TXN) + {0, 1}
@@ -725,6 +896,26 @@ __global__ __launch_bounds__(256, (XmWaves<AF32, EMIT>::value)) void gemm_f8mx_k
     const int arow = p.conv ? lane : (tid >> 2), akp = p.conv ? wvu : (tid & 3);
     uint32_t aoff[APR];
     const uint32_t phw = AF32 ? (uint32_t)(p.H * p.W) : (uint32_t)(p.awH * p.awW), uW = (uint32_t)p.awW;
+#if !XM_SETUP64
+    // m -> (img, ho, wo) by the launcher's magics; the byte offset in uint32 arithmetic (the A image lies below
+    // 2^32 bytes, so every partial product does: no 64-bit intermediate), its uniform factors on the scalar unit
+    const uint32_t mlast = (uint32_t)p.M - 1u, ohw = (uint32_t)p.Ho * (uint32_t)p.Wo, uWo = (uint32_t)p.Wo;
+    const uint32_t ai = (AF32 ? (uint32_t)p.Cin : (uint32_t)p.aw_c) * phw;                  // words per image
+    const uint32_t ah = (uint32_t)p.sh * (AF32 ? (uint32_t)p.W : uW), as = (uint32_t)p.sw;  // per output row / pixel
+    const uint32_t a0 = AF32 ? (uint32_t)p.cbase * phw : (uint32_t)(p.awpw - p.pw);
+    const uint32_t ald = (uint32_t)(AF32 ? p.lda : p.awld);
+#pragma unroll
+    for (int i = 0; i < APR; ++i) {
+        const uint32_t m = min(m0u + (uint32_t)(arow + 64 * i), mlast);
+        if (p.conv) {
+            const uint32_t img = fastdiv(m, p.ohw_mul, p.ohw_shift), pix = m - img * ohw;
+            const uint32_t ho = fastdiv(pix, p.owo_mul, p.owo_shift), wo = pix - ho * uWo;
+            aoff[i] = 4u * (img * ai + ho * ah + wo * as + a0);
+        } else {
+            aoff[i] = 4u * (m * ald + 2u * (uint32_t)akp);
+        }
+    }
+#else
 #pragma unroll
     for (int i = 0; i < APR; ++i) {
         const int64_t m = min(m0 + arow + 64 * i, p.M - 1);
@@ -738,6 +929,7 @@ __global__ __launch_bounds__(256, (XmWaves<AF32, EMIT>::value)) void gemm_f8mx_k
             aoff[i] = (uint32_t)(4 * (m * (AF32 ? p.lda : p.awld) + 2 * akp));
         }
     }
+#endif
     const __amdgpu_buffer_rsrc_t arsrc =
         AF32 ? __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(p.conv ? p.X : p.A), (short)0, -1, 0x00020000)
              : __builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t *>(p.aw), (short)0, -1, 0x00020000);
@@ -820,10 +1012,17 @@ __global__ __launch_bounds__(256, (XmWaves<AF32, EMIT>::value)) void gemm_f8mx_k
     const char *lut = reinterpret_cast<const char *>(sm.lut);
     const uint32_t wvo = (uint32_t)wc * 512u;  // the wave's first column block (4 wc) in a K-step of the table
     typedef const volatile __attribute__((address_space(3))) uint64_t xm_lds_u64;
+#if !XM_SETUP64
+    // first uses of the loads the prologue began with: the table image into LDS, the wave's vote on the sign words
+    if (4 * tid < XM_LUT_WORDS) *reinterpret_cast<uint4 *>(&sm.lut[4 * tid]) = lutv;
+    const bool both = __any(signw != 0u) != 0;
+    if (XF != 2 && blockIdx.x == 0 && tid == 0) atomicAdd(&g_xm_sign[both ? 1 : 0], 1ull);
+#endif
 #if XM_BDMA
     __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): this wave's B chunks have landed (then the barrier: everyone's)
 #endif
     __syncthreads();  // the static table is in LDS before the first build reads it
+    FP8A_CLK_MARK(clk_ta)
 
     for (int k0 = kbeg; k0 < kend; k0 += XBK) {
         if (AF32) {  // the staged values become words here (the loads above have landed)
@@ -1136,6 +1335,7 @@ __global__ __launch_bounds__(256, (XmWaves<AF32, EMIT>::value)) void gemm_f8mx_k
 #endif
         __syncthreads();
     }
+    FP8A_CLK_MARK(clk_tb)
 
     // a term beyond the e4m3 range came back NaN (and poisons its column): the exact kernel
     // recomputes the tile; (AF32) an A operand off the grid / outside the window marked its row
@@ -1168,6 +1368,13 @@ __global__ __launch_bounds__(256, (XmWaves<AF32, EMIT>::value)) void gemm_f8mx_k
     float *ct = smu.ct;
     const StoreCtx sc = p.splits == 1 ? store_ctx<EMIT>(p) : StoreCtx{};  // (a split launch stores raw partials)
     const int ety = tid & 15, etx = tid >> 4, cb = etx % (BNT / 4), sub = etx / (BNT / 4);
+#if !XM_SETUP64
+    constexpr bool EPT = BMT / SR > 1;  // the BN parameters once per tile where it has more than one slab
+    // (a single-slab tile takes it where the slab's values are in registers: ahead of the LDS pass it is live
+    // across it for nothing)
+    XmStoreTile stt;
+    if (EPT) stt = xm_store_tile<EPT>(p, splitu, n0u + (uint32_t)(cb * TN));
+#endif
 #pragma unroll
     for (int h = 0; h < BMT / SR; ++h) {
         if (h > 0) __syncthreads();  // the previous slab is read (the K loop's last barrier covers h = 0)
@@ -1190,7 +1397,12 @@ __global__ __launch_bounds__(256, (XmWaves<AF32, EMIT>::value)) void gemm_f8mx_k
             for (int j = 0; j < TN; ++j) acc[i][j] = ct[(64 * sub + ety * TM + i) * CP + cb * TN + j];
         // (GELU tails: run_gemm never emits.)  One copy of the store; sc says, uniformly, whether its
         // quantizers and words take the fast forms (option "fq_fast", every guard passed) or the literal ones
+#if XM_SETUP64
         store_tile<EMIT, !EMIT, true>(p, split, m0 + SR * h + 64 * sub, n0, ety, cb, acc, sc);
+#else
+        if (!EPT) stt = xm_store_tile<EPT>(p, splitu, n0u + (uint32_t)(cb * TN));
+        store_tile_xm<EMIT, !EMIT, EPT>(p, stt, m0u + (uint32_t)(SR * h + 64 * sub + ety * TM), acc, sc);
+#endif
     }
     // In-launch split-K sum (p.skcnt: option "splitk_fixup", E4M3).  Every split block publishes its partial
     // tile -- stores drained, barrier, one agent-scope release by thread 0, one relaxed agent-scope ticket on

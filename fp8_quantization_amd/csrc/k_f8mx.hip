@@ -12,10 +12,21 @@
 namespace fp8a {
 
 template <int NCG, int RB, int XF>
-static void launch_shape(const GemmArgs &a, hipStream_t s) {
+static void launch_shape(const GemmArgs &a0, hipStream_t s) {
     using Cf = XmCfg<NCG, RB>;
-    const int64_t xt = ((a.M + Cf::BMT - 1) / Cf::BMT) * ((a.N + Cf::BNT - 1) / Cf::BNT);
-    const dim3 g((unsigned)(xt * a.splits));
+    const int64_t num_mt = (a0.M + Cf::BMT - 1) / Cf::BMT, xt = num_mt * ((a0.N + Cf::BNT - 1) / Cf::BNT);
+    const dim3 g((unsigned)(xt * a0.splits));
+    // the kernel's 32-bit tile setup: its divisors' magics, once per launch (xt * splits < 2^31: mx_plan)
+    GemmArgs a = a0;
+    a.xm_tiles = (uint32_t)xt;
+    a.xm_num_mt = (uint32_t)num_mt;
+    fastdiv_params(a.xm_tiles, a.xt_mul, a.xt_shift);
+    fastdiv_params(a.xm_num_mt, a.xmt_mul, a.xmt_shift);
+    if (a.conv) {
+        fastdiv_params((uint32_t)(a.Ho * a.Wo), a.ohw_mul, a.ohw_shift);
+        fastdiv_params((uint32_t)a.Wo, a.owo_mul, a.owo_shift);
+    }
+    if (a.nchw) fastdiv_params((uint32_t)a.hw, a.shw_mul, a.shw_shift);
     // (the emitting instances only where this launch writes the next convolution's word image
     // from its own store: unsplit, or split with the in-launch sum -- fp8a_conv2d_chain)
     const bool emit = a.em.w != nullptr && (a.splits == 1 || a.skcnt != nullptr);
@@ -77,9 +88,9 @@ static void launch_xf(const GemmArgs &a, hipStream_t s) {
 }
 
 static int clock_read(unsigned long long *v, bool reset) {
-    if (hipMemcpyFromSymbol(v, HIP_SYMBOL(g_clk), 3 * sizeof(unsigned long long)) != hipSuccess) return -1;
+    if (hipMemcpyFromSymbol(v, HIP_SYMBOL(g_clk), 6 * sizeof(unsigned long long)) != hipSuccess) return -1;
     if (reset) {
-        const unsigned long long z[3] = {0, 0, 0};
+        const unsigned long long z[6] = {0, 0, 0, 0, 0, 0};
         if (hipMemcpyToSymbol(HIP_SYMBOL(g_clk), z, sizeof(z)) != hipSuccess) return -1;
     }
     return 0;

@@ -233,7 +233,9 @@ int fp8a_dense_stats(uint64_t *out, int reset);
 /* Diagnostic: the in-kernel clock of gemm_f8mx_kernel, counted only by a library built with
  * -DFP8A_CLOCK_STAMP=1 (tools/clock_probe.py; zeros otherwise), out[3]: sum over workgroups of
  * the s_memtime delta, of the s_memrealtime (100 MHz) delta, and the workgroup count.
- * Synchronises the device. */
+ * reset bit 0 zeroes the sums after the read; with bit 1 set, out[3] is instead the s_memtime sum
+ * split by phase: before the kernel's first barrier, its K loop, after the K loop's last barrier
+ * (tools/phase_probe.py).  Synchronises the device. */
 int fp8a_clock_stats(uint64_t *out, int reset);
 
 /*
