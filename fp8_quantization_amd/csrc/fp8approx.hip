@@ -706,6 +706,10 @@ constexpr size_t FLAG_BYTES = 256;  // workspace prefix holding the off-grid fla
 enum { PATH_F8MX = 0, PATH_TT = 1, PATH_TT16 = 2, PATH_FAST = 3, PATH_EXACT = 4, PATH_DENSE = 5, PATH_V5MX = 6,
        PATH_N = 7 };
 static std::atomic<uint64_t> g_paths[PATH_N];
+// the path of a launch run_gemm has set up: by its pre-decoded operands (a.aw) and their word format
+static int gemm_path(const GemmArgs &a) {
+    return !a.aw ? PATH_FAST : a.wfmt == 0 ? PATH_F8MX : a.wfmt == 1 ? PATH_TT : a.wfmt == 4 ? PATH_V5MX : PATH_TT16;
+}
 
 // Kernel timing (fp8a_kernel_timing / fp8a_kernel_time): while on, run_gemm brackets the product
 // kernel launch(es) of every GEMM (launch_fast: gemm_f8mx_kernel, gemm_tt*_kernel, gemm_v5mx_kernel
@@ -798,11 +802,21 @@ static size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 // The B image: the E4M3 / E5M2 column pairs ([kpad][npad / 2] uint2) or the v5 form's four table
 // words per column ([kpad][npad] uint2, gemm_v5mx.h) -- sized for the larger.
 static size_t xm_b_bytes(int64_t kpad, int64_t npad) { return align256((size_t)(kpad * npad) * 8); }
-static size_t xm_operand_bytes(int64_t N, int64_t K, int64_t a_words) {
+constexpr size_t XM_TABLE_IMAGE_BYTES = 16384;  // the static table image (largest: the tile-table kernels')
+// The region's layout, as byte offsets from its start: A words, B image, table image, E5M2 B exponent ranges
+struct XmOperandLayout {
+    size_t bqw, lutw, ebr, total;
+};
+static XmOperandLayout xm_operand_layout(int64_t N, int64_t K, int64_t a_words) {
     const int64_t kpad = (K + BK - 1) / BK * BK, npad = (N + BN - 1) / BN * BN;
-    // + table image + the E5M2 B exponent ranges
-    return align256((size_t)a_words * 4) + xm_b_bytes(kpad, npad) + 16384 + align256((size_t)(kpad * npad / 16) * 2);
+    XmOperandLayout l;
+    l.bqw = align256((size_t)a_words * 4);
+    l.lutw = l.bqw + xm_b_bytes(kpad, npad);
+    l.ebr = l.lutw + XM_TABLE_IMAGE_BYTES;
+    l.total = l.ebr + align256((size_t)(kpad * npad / 16) * 2);
+    return l;
 }
+static size_t xm_operand_bytes(int64_t N, int64_t K, int64_t a_words) { return xm_operand_layout(N, K, a_words).total; }
 
 // The per-unit fallback marks after the flag word: urow [nur], ucol [nuc], utile [nur * nuc] bytes.
 static size_t unit_bytes(int64_t M, int64_t N) {
@@ -1161,13 +1175,14 @@ static int run_gemm(GemmArgs &a, const int32_t *table, void *ws, size_t ws_bytes
         a.awH = wi.H; a.awW = wi.W; a.awph = wi.ph; a.awpw = wi.pw;
         // (the exact test: the operands behind this launch's own split-K partials; the callers that fuse
         // an input quantizer test gemm_workspace_bytes, which is never smaller)
-        if (mx.fits32 && ws_bytes >= off + xm_operand_bytes(a.N, a.K, a_words)) {
+        const XmOperandLayout lay = xm_operand_layout(a.N, a.K, a_words);
+        if (mx.fits32 && ws_bytes >= off + lay.total) {
             char *base = (char *)ws + off;
             a.aw = (const uint32_t *)base;
             a.awld = kpad;
-            a.bqw = (const uint2 *)(base + align256((size_t)a_words * 4));
-            a.lutw = (const uint32_t *)(base + align256((size_t)a_words * 4) + xm_b_bytes(kpad, npad));
-            a.ebr = (const uint16_t *)((const char *)a.lutw + 16384);
+            a.bqw = (const uint2 *)(base + lay.bqw);
+            a.lutw = (const uint32_t *)(base + lay.lutw);
+            a.ebr = (const uint16_t *)(base + lay.ebr);
             a.xm_vmin = 0;  // the table's lowest V' binade (the E5M2 halved-block form's `tok` threshold)
             if (mode == TM_F8) (void)xm_table_form(a.tab, a.Mw, &a.xm_vmin);
             a.npad = npad;
@@ -1227,7 +1242,7 @@ static int run_gemm(GemmArgs &a, const int32_t *table, void *ws, size_t ws_bytes
     if (a.fqin.mx && !a.aw)  // the caller (conv2d_impl) only fuses where the pre-decode runs
         return fail(FP8A_EINVAL, "internal: fused input quantization without the matrix-core path");
     if (mode == TM_F8 && a.Mw != 3 && !a.aw) mode = mode0;  // (gemm_fast_kernel's TM_F8 form is E4M3 only)
-    ++g_paths[!a.aw ? PATH_FAST : a.wfmt == 0 ? PATH_F8MX : a.wfmt == 1 ? PATH_TT : a.wfmt == 4 ? PATH_V5MX : PATH_TT16];
+    ++g_paths[gemm_path(a)];
     // word-image emission (fp8a_conv2d_chain): the E4M3 / E5M2 matrix-core kernel and the VALU
     // kernel emit the next convolution's words from their store; the tile-table and v5 matrix-core
     // kernels do not (store_tile<false>: the emission code cost gemm_tt16_kernel 32 SGPR spills and a
@@ -1243,7 +1258,7 @@ static int run_gemm(GemmArgs &a, const int32_t *table, void *ws, size_t ws_bytes
     if (g_ktime && !cap) {  // (no host-side events inside a captured graph)
         kev.a = pool_event();
         kev.b = pool_event();
-        kev.path = !a.aw ? PATH_FAST : a.wfmt == 0 ? PATH_F8MX : a.wfmt == 1 ? PATH_TT : a.wfmt == 4 ? PATH_V5MX : PATH_TT16;
+        kev.path = gemm_path(a);
         // (E5M2: the plain and the halved-block form; E3M4 f16 form: + its gated f32 rerun)
         kev.dispatches = (a.aw && ((a.wfmt == 0 && a.Mw == 2) || a.wfmt == 2)) ? 2 : 1;
         kev.macs = (double)a.M * (double)a.N * (double)a.K;

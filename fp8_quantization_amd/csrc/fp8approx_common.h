@@ -576,9 +576,7 @@ __device__ __forceinline__ bool stage_decode(float x, int M, uint32_t emn, bool 
 // EMIT = false compiles the word-image emission out (gemm_f8mx_kernel's non-emitting instances:
 // the emission code alone pushed that kernel past its 80-VGPR budget).
 // GELU = false: the GELU tail compiled out as well (gemm_f8mx_kernel's emitting instances).
-// FQF = true: the post quantizer and the emission take their fast forms where sc.fqf says so (a uniform
-// choice per value around the literal code: ONE copy of the store, so that no instance of
-// gemm_f8mx_kernel allocates more registers than its literal-only store did); false: no fast code.
+// The quantizers and words here are the literal forms (gemm_f8mx_kernel's store_tile_xm has the fast ones).
 // sc: the block's StoreCtx (unsplit launches; a split launch stores raw partials and reads none of it).
 // -DFP8A_RAW_STORE_DIAG=1 (diagnostic build only, tools/gemm_bench.py --emit: DESIGN.md 3v): the emitting
 // instances store the raw fp32 accumulators and nothing else -- no BN / activation, residual, quantizer, word
@@ -586,7 +584,7 @@ __device__ __forceinline__ bool stage_decode(float x, int M, uint32_t emn, bool 
 #ifndef FP8A_RAW_STORE_DIAG
 #define FP8A_RAW_STORE_DIAG 0
 #endif
-template <bool EMIT = true, bool GELU = true, bool FQF = false>
+template <bool EMIT = true, bool GELU = true>
 __device__ __forceinline__ void store_tile(const GemmArgs &p, int64_t split, int64_t m0, int64_t n0, int ty, int tx,
                                            float (&acc)[TM][TN], const StoreCtx &sc) {
     constexpr bool RAW = FP8A_RAW_STORE_DIAG && EMIT;
@@ -611,14 +609,14 @@ __device__ __forceinline__ void store_tile(const GemmArgs &p, int64_t split, int
     uint32_t sehi = 0, neg = 0;
     auto fin1 = [&](int64_t o, float v) {
         if (partial || RAW) return v;
-        v = post1<GELU, FQF>(q, o, v, pb, pk);
-        if (emit) emit1<FQF>(q, ec, o, v, sehi, neg);
+        v = post1<GELU>(q, o, v, pb, pk);
+        if (emit) emit1(q, ec, o, v, sehi, neg);
         return v;
     };
     auto fin4 = [&](int64_t o, float4 v) {
         if (partial || RAW) return v;
-        v = post4<GELU, FQF>(q, o, v, pb, pk);
-        if (emit) emit4<FQF>(q, ec, o, v, sehi, neg);
+        v = post4<GELU>(q, o, v, pb, pk);
+        if (emit) emit4(q, ec, o, v, sehi, neg);
         return v;
     };
     if (!p.nchw) {
@@ -771,7 +769,8 @@ __device__ __forceinline__ void splitk_finish_tile(const GemmArgs &p, int64_t m0
     }
 }
 
-// (the kernels that keep the literal forms: the context per call, as before)
+// (the context per call.  Kept as a forwarding overload: with the context built inside the function above,
+// gemm_fast_kernel's instances came out with two scalar moves in another order)
 template <bool EMIT = true, bool GELU = true>
 __device__ __forceinline__ void store_tile(const GemmArgs &p, int64_t split, int64_t m0, int64_t n0, int ty, int tx,
                                            float (&acc)[TM][TN]) {
@@ -780,7 +779,7 @@ __device__ __forceinline__ void store_tile(const GemmArgs &p, int64_t split, int
         sc.pb = post_bias(p);
         if (EMIT) sc.ec = emit_ctx(p);
     }
-    store_tile<EMIT, GELU, false>(p, split, m0, n0, ty, tx, acc, sc);
+    store_tile<EMIT, GELU>(p, split, m0, n0, ty, tx, acc, sc);
 }
 
 }  // namespace fp8a

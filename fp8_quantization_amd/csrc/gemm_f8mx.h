@@ -119,14 +119,6 @@ __host__ __device__ constexpr int xm_xbias(int Mw) { return Mw == 2 ? 15 : 7; }
 // A words in LDS: [kk / 2][row][kk % 2] -- one ds_write_b64 stores (and one ds_read_b64 reads) a
 // row's words of a K-step pair; the pair arrays sit 32 banks apart, so the math loop's reads
 // (lane groups of K-step pairs g, g + 1) and the staging's stores are conflict-free.
-// B operand by LDS-DMA (option build, round 6; off): the staged tile's B pair words (XBK x TXN
-// 16-byte chunks, each read by the 4 build units of its column block) go global -> LDS by
-// global_load_lds_dwordx4 instead of through 8 prefetch VGPRs per thread.  The plain 128 x 64
-// instance then fits 6 waves / SIMD (76 VGPRs, no spill) -- and ran 4 % slower: ResNet-18 12,175
-// vs 12,673 images/s, ResNet-50 E4M3 4,671 vs 4,857 (profiles/r06_bdma/)
-#ifndef XM_BDMA
-#define XM_BDMA 0
-#endif
 template <int NCG, int RB>
 struct XmCfg {
     static constexpr int NT = 256;
@@ -147,9 +139,6 @@ struct XmCfg {
         uint32_t tt[XBK][TTK];  // c_b-applied pairs [kk][tx][row][j] (first: its byte offsets are the reads' immediates)
         uint32_t lut[XM_LUT_WORDS];
         uint32_t aw[XBK / 2][AWQ];  // A(m, k)'s word: cvt scale exponent << 23 | row << 3
-#if XM_BDMA
-        uint4 bw[XBK * TXN];        // the staged tile's B pair words [kk][column block], by LDS-DMA
-#endif
     };
     union Smem {
         Stage st;
@@ -590,15 +579,6 @@ __device__ unsigned long long g_xm_sign[2];
 // 28.7 -> 25.5 ms, bench 11835 -> 12454 images/s at 5 waves (round 5)
 #define XM_WAVES 5
 #endif
-// the plain instance (staged words, no emission), with the B operand by LDS-DMA: 76 VGPRs, no spill
-// at 6 waves (the emitting / fp32-staging instances spill 7-28 there and stay at XM_WAVES).  (The
-// bound is a trait: a conditional expression in __launch_bounds__ works too, but the macro splits
-// on a template argument list's comma)
-#ifndef XM_WAVES_PLAIN
-#define XM_WAVES_PLAIN (XM_BDMA ? 6 : XM_WAVES)
-#endif
-template <bool AF32, bool EMIT> struct XmWaves { static constexpr int value = XM_WAVES; };
-template <> struct XmWaves<false, false> { static constexpr int value = XM_WAVES_PLAIN; };
 // The GEMM.  Tile BMT x BNT (XmCfg), 4 waves; wave wv = column group wc = wv % NCG (the 16
 // columns 16 wc .. 16 wc + 15, column blocks tx = 4 wc + c of the tile table) and row group
 // wr = wv / NCG (16 RB rows).  Math mapping: lane = (row r16 of each of the wave's RB 16-row
@@ -651,7 +631,7 @@ template <bool EMIT> struct XmPipe<1, EMIT, true> { static constexpr int value =
 // per staged tile and lane 2 A pair reads and 4 address ops instead of 8 and 16.  Accumulator dq[4 rb + cg]
 // is (row block 2 w + rb, column group cg); it still takes one MFMA per staged tile, in K order, over the same
 // 128 codes converted from the same table and scale words: the same bits as the mapping by columns.
-// gemm_f8mx_kernel's store (XM_SETUP64 = 0).  What a tile's slabs share, taken once per tile:
+// gemm_f8mx_kernel's store.  What a tile's slabs share, taken once per tile:
 // the uniform tests (a split launch's raw partials, the output mapping, the vector forms' alignment, the BN
 // epilogue), the output base and strides, and the BN parameters of the thread's four channels (nb ..).
 struct XmStoreTile {
@@ -776,16 +756,60 @@ __device__ __forceinline__ void store_tile_xm(const GemmArgs &p, const XmStoreTi
     }
 }
 
+// ---- The math loop's steps, one copy each; its three mappings in gemm_f8mx_kernel (by columns, by columns
+// pipelined, by rows) share them.
+// (volatile: a table pair's two halves are used as different types; a plain load is split in two and re-merged
+// into a ds_read2_b32 -- half the LDS rate of ds_read_b64 -- and a volatile one also stays where the source
+// puts it, which the pipelined forms rely on)
+typedef const volatile __attribute__((address_space(3))) uint64_t xm_lds_u64;
+// An A element's table address: row offset (the word's bits 3-6) | base, one v_and_or_b32
+__device__ __forceinline__ uint32_t xm_table_addr(uint32_t aword, uint32_t base) {
+    uint32_t a;
+    asm("v_and_or_b32 %0, %1, %2, %3" : "=v"(a) : "v"(aword), "s"(XM_ROW_MASK), "v"(base));
+    return a;
+}
+// The table fetch of one A element and K-step: four ds_read_b64 (16 columns) at address a from `tt`, the byte
+// address that the reads' immediates start from (the K-step h of the lane's pair, the column group by rows)
+__device__ __forceinline__ void xm_table_fetch(const char *tt, uint32_t a, uint2 (&v)[4]) {
+    __builtin_assume((a & 7u) == 0u);
+    xm_lds_u64 *ttk = (xm_lds_u64 *)tt;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        const uint64_t w = ttk[(a >> 3) + 16 * c];
+        v[c] = make_uint2((uint32_t)w, (uint32_t)(w >> 32));
+    }
+}
+// The eight conversions of one A element and K-step h: the four pairs of pairs v, scaled by the A word's
+// exponent field, into the codes av[4 h .. 4 h + 3] (e4m3, or bf8 for the E5M2 forms XF 1 / 2)
+template <int XF>
+__device__ __forceinline__ void xm_convert(const uint2 (&v)[4], uint32_t aword, int h, xm_v8i &av) {
+    const float sc = __uint_as_float(aword);
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        xm_s2 cv;
+        if (XF) {
+            asm("v_cvt_scalef32_pk_bf8_bf16 %0, %1, %2" : "=v"(cv) : "v"(v[c].x), "v"(sc));
+            cv = __builtin_amdgcn_cvt_scalef32_pk_bf8_bf16(cv, __builtin_bit_cast(xm_b2, v[c].y), sc, true);
+        } else {
+            asm("v_cvt_scalef32_pk_fp8_bf16 %0, %1, %2" : "=v"(cv) : "v"(v[c].x), "v"(sc));
+            cv = __builtin_amdgcn_cvt_scalef32_pk_fp8_bf16(cv, __builtin_bit_cast(xm_b2, v[c].y), sc, true);
+        }
+        av[4 * h + c] = __builtin_bit_cast(int, cv);
+    }
+}
+// A row's word pair of K-steps 2 g, 2 g + 1 (the pipelined forms: one ds_read_b64 that stays where the source
+// puts it)
+__device__ __forceinline__ uint2 xm_a_pair(const uint32_t *aw) {
+    const uint64_t w = *(xm_lds_u64 *)aw;
+    return make_uint2((uint32_t)w, (uint32_t)(w >> 32));
+}
+
 // Per-tile setup and store indexing: the block -> tile -> row decompositions run in 32-bit
 // arithmetic with fastdiv magics the launcher made (GemmArgs xm_tiles ..), the prologue's global loads go out
 // ahead of them, and the store (store_tile_xm below) takes its uniform tests and the thread's four channels'
-// BN parameters once per tile and advances output offsets by adds.  -DXM_SETUP64=1 (a build-time switch like
-// XM_PIPE_EMIT64, for A/B builds) restores the 64-bit `/` and `%` per tile, row and slab and store_tile.
-#ifndef XM_SETUP64
-#define XM_SETUP64 0
-#endif
+// BN parameters once per tile and advances output offsets by adds.
 template <int NCG, int RB, bool AF32, int XF, bool EMIT, bool FIX = false, int PIPE = 0, bool WROWS = false>
-__global__ __launch_bounds__(256, (XmWaves<AF32, EMIT>::value)) void gemm_f8mx_kernel(const GemmArgs p) {
+__global__ __launch_bounds__(256, XM_WAVES) void gemm_f8mx_kernel(const GemmArgs p) {
     static_assert(PIPE == 0 || (!AF32 && XF != 2), "PIPE: the word-staged plain forms only");
     static_assert(!WROWS || (NCG == 4 && RB == 8 && PIPE != 0 && !FIX), "WROWS: the 128 x 64 PIPE instances");
     using Cf = XmCfg<NCG, RB>;
@@ -799,13 +823,6 @@ __global__ __launch_bounds__(256, (XmWaves<AF32, EMIT>::value)) void gemm_f8mx_k
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int wvu = __builtin_amdgcn_readfirstlane(wv);
     const int wc = wvu % NCG, wr = wvu / NCG;  // the wave's column group and row group
-#if XM_SETUP64
-    const int64_t num_mt = (p.M + BMT - 1) / BMT;
-    const int64_t tiles = num_mt * ((p.N + BNT - 1) / BNT);
-    const int64_t bid = (int64_t)blockIdx.x % tiles, split = (int64_t)blockIdx.x / tiles;
-    const int64_t m0 = (bid % num_mt) * BMT;
-    const int64_t n0 = (bid / num_mt) * BNT;
-#else
     // The prologue's dependent global loads first -- this thread's 16 bytes of the table image (below), the
     // sign words and *p.bR; each is waited for at its first use, behind the index arithmetic.
     uint4 lutv = make_uint4(0u, 0u, 0u, 0u);
@@ -815,21 +832,11 @@ __global__ __launch_bounds__(256, (XmWaves<AF32, EMIT>::value)) void gemm_f8mx_k
     const uint32_t splitu = fastdiv(blockIdx.x, p.xt_mul, p.xt_shift), bidu = blockIdx.x - splitu * p.xm_tiles;
     const uint32_t ntu = fastdiv(bidu, p.xmt_mul, p.xmt_shift);
     const uint32_t m0u = (bidu - ntu * p.xm_num_mt) * (uint32_t)BMT, n0u = ntu * (uint32_t)BNT;
-    const int64_t bid = bidu, split = splitu, m0 = m0u, n0 = n0u;  // (the fallback marks and the split sum)
-#endif
+    const int64_t bid = bidu, m0 = m0u, n0 = n0u;  // (the fallback marks and the split sum)
     // The build writes the table rows of s_a = 1 (8 + m_a) only when an A word of the launch addresses
     // them: the pre-pass left that in the spread sign words (xm_record_sign), the producer of the
     // word image in flag[3] -- one load per wave, lanes 0-31 a spread word each, the rest flag[3].
     // Wave-uniform, read once.  (AF32 decodes A while staging and cannot know: both halves.)
-#if XM_SETUP64
-    bool both = true;
-    if (!AF32 && p.xm_signs)
-        both = __any(__hip_atomic_load(p.flag + (lane < XM_SIGN_NW ? XM_SIGN_W0 + lane : 3), __ATOMIC_RELAXED,
-                                       __HIP_MEMORY_SCOPE_WORKGROUP) != 0u) != 0;  // (written by earlier kernels only)
-    if (XF != 2 && blockIdx.x == 0 && tid == 0) atomicAdd(&g_xm_sign[both ? 1 : 0], 1ull);
-    if (XF == 2 && !xm_half_gate(p, m0, BMT, n0, BNT)) return;  // (a tile the plain form completed)
-    const int kbeg = (int)(split * p.kchunk), kend = (int)min(p.K, (int64_t)kbeg + p.kchunk), K32 = (int)p.K;
-#else
     // (the load here; the wave's vote on it right before the K loop's first barrier)
     uint32_t signw = 1u;
     if (!AF32 && p.xm_signs)
@@ -837,7 +844,6 @@ __global__ __launch_bounds__(256, (XmWaves<AF32, EMIT>::value)) void gemm_f8mx_k
                                   __HIP_MEMORY_SCOPE_WORKGROUP);  // (written by earlier kernels only)
     if (XF == 2 && !xm_half_gate(p, m0, BMT, n0, BNT)) return;  // (a tile the plain form completed)
     const int K32 = (int)p.K, kbeg = (int)splitu * (int)p.kchunk, kend = min(K32, kbeg + (int)p.kchunk);
-#endif
     const int bR = *p.bR;
     // AF32: the A operand's bias (the fused input quantizer's, written once for the gated kernels)
     float fmx = 0.0f, fbias = 0.0f;
@@ -856,12 +862,7 @@ __global__ __launch_bounds__(256, (XmWaves<AF32, EMIT>::value)) void gemm_f8mx_k
     const uint32_t emnA = (uint32_t)(128 - bA) << 23;
 
     // table: copied from the launch's pre-computed image (xm_decode_b), 16-B per thread and step
-#if XM_SETUP64
-    for (int e = 4 * tid; e < XM_LUT_WORDS; e += 4 * NT)
-        *reinterpret_cast<uint4 *>(&sm.lut[e]) = *reinterpret_cast<const uint4 *>(&p.lutw[e]);
-#else
     static_assert(XM_LUT_WORDS <= 4 * NT, "one 16-byte step per thread (lutv, loaded at the top)");
-#endif
 
     // tile-table build units e = tid + NT u (NBU per tile): (m_a pair q4, column block btx,
     // K-step bkk[u]); the 8 lanes of a ds_write_b128 group are 4 q4 x an even and an odd K-step
@@ -873,21 +874,10 @@ __global__ __launch_bounds__(256, (XmWaves<AF32, EMIT>::value)) void gemm_f8mx_k
     // K-step + u * BKU -- the per-unit offsets are uniform (soffset / immediates), one VGPR each
     constexpr int BKU = 2 * (NT / (8 * TXN));
     const int bkk0 = 2 * (tid / (8 * TXN)) + ((tid >> 2) & 1);
-#if XM_SETUP64
-    const uint32_t boff0 = (uint32_t)(kbeg + bkk0) * hq8 + (uint32_t)(n0 / 2 + 2 * btx) * 8u;  // pair 2 btx: 16-B aligned
-#else
     const uint32_t boff0 = (uint32_t)(kbeg + bkk0) * hq8 + (n0u / 2u + 2u * (uint32_t)btx) * 8u;  // pair 2 btx: 16-B aligned
-#endif
     const bool build = NBU % NT == 0 || tid < NBU;  // (NCG = 1: half the threads build)
-#if XM_BDMA
-    // this thread's DMA chunk (tid < XBK TXN): K-step kbeg + tid / TXN, pairs n0 / 2 + 2 (tid % TXN) + {0, 1}
-    const float *bsrc = reinterpret_cast<const float *>(p.bqw) +
-                        ((size_t)(kbeg + tid / TXN) * (hq8 / 4) + (size_t)(n0 / 2 + 2 * (tid % TXN)) * 2);
-    (void)boff0;
-#else
     const __amdgpu_buffer_rsrc_t brsrc =
         __builtin_amdgcn_make_buffer_rsrc(const_cast<uint2 *>(p.bqw), (short)0, -1, 0x00020000);
-#endif
 
     // A staging: thread = (rows arow + 64 i, K-step pair akp), K-steps 2 akp + r.  conv: lane =
     // row (consecutive pixels), akp = the wave (wave-uniform: the k -> (c, ky, kx) split and the
@@ -896,7 +886,6 @@ __global__ __launch_bounds__(256, (XmWaves<AF32, EMIT>::value)) void gemm_f8mx_k
     const int arow = p.conv ? lane : (tid >> 2), akp = p.conv ? wvu : (tid & 3);
     uint32_t aoff[APR];
     const uint32_t phw = AF32 ? (uint32_t)(p.H * p.W) : (uint32_t)(p.awH * p.awW), uW = (uint32_t)p.awW;
-#if !XM_SETUP64
     // m -> (img, ho, wo) by the launcher's magics; the byte offset in uint32 arithmetic (the A image lies below
     // 2^32 bytes, so every partial product does: no 64-bit intermediate), its uniform factors on the scalar unit
     const uint32_t mlast = (uint32_t)p.M - 1u, ohw = (uint32_t)p.Ho * (uint32_t)p.Wo, uWo = (uint32_t)p.Wo;
@@ -915,29 +904,12 @@ __global__ __launch_bounds__(256, (XmWaves<AF32, EMIT>::value)) void gemm_f8mx_k
             aoff[i] = 4u * (m * ald + 2u * (uint32_t)akp);
         }
     }
-#else
-#pragma unroll
-    for (int i = 0; i < APR; ++i) {
-        const int64_t m = min(m0 + arow + 64 * i, p.M - 1);
-        if (p.conv) {
-            const int64_t hw = p.Ho * p.Wo, img = m / hw, pix = m - img * hw, ho = pix / p.Wo, wo = pix - ho * p.Wo;
-            if (AF32)  // 1x1, unpadded: x[img][cbase + k][ho sh][wo sw]
-                aoff[i] = (uint32_t)(4 * ((img * p.Cin + p.cbase) * (int64_t)phw + ho * p.sh * p.W + wo * p.sw));
-            else
-                aoff[i] = (uint32_t)(4 * (img * p.aw_c * (int64_t)phw + ho * p.sh * p.awW + wo * p.sw + (p.awpw - p.pw)));
-        } else {
-            aoff[i] = (uint32_t)(4 * (m * (AF32 ? p.lda : p.awld) + 2 * akp));
-        }
-    }
-#endif
     const __amdgpu_buffer_rsrc_t arsrc =
         AF32 ? __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(p.conv ? p.X : p.A), (short)0, -1, 0x00020000)
              : __builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t *>(p.aw), (short)0, -1, 0x00020000);
     const int khw = p.kh * p.kw;
     uint32_t wa[APR][2];
-#if !XM_BDMA
     uint4 wbq[BU];
-#endif
     auto load_tile = [&](int k0) {
 #pragma unroll
         for (int r = 0; r < 2; ++r) {
@@ -973,12 +945,6 @@ __global__ __launch_bounds__(256, (XmWaves<AF32, EMIT>::value)) void gemm_f8mx_k
                 wa[i][r] = __builtin_amdgcn_raw_buffer_load_b32(arsrc, (int)aoff[i], (int)ko, 0);
             }
         }
-#if XM_BDMA
-        // chunk tid = (K-step tid / TXN, column block tid % TXN) -> bw[tid]; a wave's 64 chunks land
-        // contiguously from its LDS base (the last, partial wave: lanes past the chunks stay off)
-        if (tid < XBK * TXN)
-            __builtin_amdgcn_global_load_lds(bsrc + (size_t)(k0 - kbeg) * (hq8 / 4), reinterpret_cast<float *>(&sm.bw[64 * wvu]), 16, 0, 0);  // (a uint4 * here: the host pass drops the kernel stubs)
-#else
         if (build) {
             const uint32_t kb = __builtin_amdgcn_readfirstlane((uint32_t)(k0 - kbeg) * hq8);
 #pragma unroll
@@ -986,7 +952,6 @@ __global__ __launch_bounds__(256, (XmWaves<AF32, EMIT>::value)) void gemm_f8mx_k
                 wbq[u] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(
                                                        brsrc, (int)boff0, (int)(kb + (uint32_t)(u * BKU) * hq8), 0));
         }
-#endif
     };
     load_tile(kbeg);
 
@@ -1011,16 +976,10 @@ __global__ __launch_bounds__(256, (XmWaves<AF32, EMIT>::value)) void gemm_f8mx_k
     xm_v8i av = {0, 0, 0, 0, 0, 0, 0, 0};
     const char *lut = reinterpret_cast<const char *>(sm.lut);
     const uint32_t wvo = (uint32_t)wc * 512u;  // the wave's first column block (4 wc) in a K-step of the table
-    typedef const volatile __attribute__((address_space(3))) uint64_t xm_lds_u64;
-#if !XM_SETUP64
     // first uses of the loads the prologue began with: the table image into LDS, the wave's vote on the sign words
     if (4 * tid < XM_LUT_WORDS) *reinterpret_cast<uint4 *>(&sm.lut[4 * tid]) = lutv;
     const bool both = __any(signw != 0u) != 0;
     if (XF != 2 && blockIdx.x == 0 && tid == 0) atomicAdd(&g_xm_sign[both ? 1 : 0], 1ull);
-#endif
-#if XM_BDMA
-    __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): this wave's B chunks have landed (then the barrier: everyone's)
-#endif
     __syncthreads();  // the static table is in LDS before the first build reads it
     FP8A_CLK_MARK(clk_ta)
 
@@ -1065,17 +1024,10 @@ __global__ __launch_bounds__(256, (XmWaves<AF32, EMIT>::value)) void gemm_f8mx_k
         // spilled in the 128 x 64 instances.)
         if (build) {
             auto pk = [](uint32_t v, xm_u2 ad) { return __builtin_bit_cast(uint32_t, __builtin_bit_cast(xm_u2, v) + ad); };
-            auto unit_b = [&](int u) {
-#if XM_BDMA
-                return sm.bw[(bkk0 + u * BKU) * TXN + btx];
-#else
-                return wbq[u];
-#endif
-            };
             if (both) {
 #pragma unroll
                 for (int u = 0; u < BU; ++u) {
-                    const uint4 b = unit_b(u);
+                    const uint4 b = wbq[u];
                     const uint2 s0 = *reinterpret_cast<const uint2 *>(lut + b.y + 8 * q4);
                     const uint2 s1 = *reinterpret_cast<const uint2 *>(lut + b.w + 8 * q4);
                     const xm_u2 a0 = __builtin_bit_cast(xm_u2, b.x), a1 = __builtin_bit_cast(xm_u2, b.z);
@@ -1087,7 +1039,7 @@ __global__ __launch_bounds__(256, (XmWaves<AF32, EMIT>::value)) void gemm_f8mx_k
             } else {
 #pragma unroll
                 for (int u = 0; u < BU; ++u) {
-                    uint4 b = unit_b(u);
+                    uint4 b = wbq[u];
                     asm volatile("" : "+v"(b.x), "+v"(b.z));
                     const uint2 s0 = *reinterpret_cast<const uint2 *>(lut + b.y + 8 * q4);
                     const uint2 s1 = *reinterpret_cast<const uint2 *>(lut + b.w + 8 * q4);
@@ -1132,40 +1084,11 @@ __global__ __launch_bounds__(256, (XmWaves<AF32, EMIT>::value)) void gemm_f8mx_k
             }
             if constexpr (WROWS) {
                 const uint32_t rbase = (uint32_t)(2 * g) * (uint32_t)(TTK * 4);  // (no wave term)
-                auto addr = [&](uint32_t aword) {
-                    uint32_t a;
-                    asm("v_and_or_b32 %0, %1, %2, %3" : "=v"(a) : "v"(aword), "s"(XM_ROW_MASK), "v"(rbase));
-                    return a;
-                };
+                auto addr = [&](uint32_t aword) { return xm_table_addr(aword, rbase); };
                 // the four table reads of (column group cg, K-step h): immediates (4 cg + c) * 128 + h * TTK * 4
-                auto tread = [&](uint32_t a, int cg, int h, uint2(&v)[4]) {
-                    __builtin_assume((a & 7u) == 0u);
-                    xm_lds_u64 *ttk = (xm_lds_u64 *)(tt0 + h * TTK * 4 + cg * 512);
-#pragma unroll
-                    for (int c = 0; c < 4; ++c) {
-                        const uint64_t w = ttk[(a >> 3) + 16 * c];
-                        v[c] = make_uint2((uint32_t)w, (uint32_t)(w >> 32));
-                    }
-                };
-                auto conv = [&](const uint2(&v)[4], uint32_t aword, int h) {
-                    const float sc = __uint_as_float(aword);
-#pragma unroll
-                    for (int c = 0; c < 4; ++c) {
-                        xm_s2 cv;
-                        if (XF) {
-                            asm("v_cvt_scalef32_pk_bf8_bf16 %0, %1, %2" : "=v"(cv) : "v"(v[c].x), "v"(sc));
-                            cv = __builtin_amdgcn_cvt_scalef32_pk_bf8_bf16(cv, __builtin_bit_cast(xm_b2, v[c].y), sc, true);
-                        } else {
-                            asm("v_cvt_scalef32_pk_fp8_bf16 %0, %1, %2" : "=v"(cv) : "v"(v[c].x), "v"(sc));
-                            cv = __builtin_amdgcn_cvt_scalef32_pk_fp8_bf16(cv, __builtin_bit_cast(xm_b2, v[c].y), sc, true);
-                        }
-                        av[4 * h + c] = __builtin_bit_cast(int, cv);
-                    }
-                };
-                auto aread = [&](int rb) {
-                    const uint64_t w = *(xm_lds_u64 *)&sm.aw[g][2 * (16 * (2 * wvu + rb) + r16)];
-                    return make_uint2((uint32_t)w, (uint32_t)(w >> 32));
-                };
+                auto tread = [&](uint32_t a, int cg, int h, uint2(&v)[4]) { xm_table_fetch(tt0 + h * TTK * 4 + cg * 512, a, v); };
+                auto conv = [&](const uint2(&v)[4], uint32_t aword, int h) { xm_convert<XF>(v, aword, h, av); };
+                auto aread = [&](int rb) { return xm_a_pair(&sm.aw[g][2 * (16 * (2 * wvu + rb) + r16)]); };
                 // The pipeline of PIPE over the steps (row block, column group, K-step h); a row block's two
                 // addresses stay live across its four column groups.  The second block's A pair is read right
                 // after the first block's last table reads are issued, when that block's addresses are dead (read
@@ -1216,37 +1139,10 @@ __global__ __launch_bounds__(256, (XmWaves<AF32, EMIT>::value)) void gemm_f8mx_k
                 }
             } else if constexpr (PIPE != 0) {
                 // one K-step's table reads (one v_and_or_b32, four ds_read_b64) / its eight conversions
-                auto tread = [&](uint32_t aword, int h, uint2(&v)[4]) {
-                    uint32_t a;
-                    asm("v_and_or_b32 %0, %1, %2, %3" : "=v"(a) : "v"(aword), "s"(XM_ROW_MASK), "v"(base));
-                    __builtin_assume((a & 7u) == 0u);
-                    xm_lds_u64 *ttk = (xm_lds_u64 *)(tt0 + h * TTK * 4);
-#pragma unroll
-                    for (int c = 0; c < 4; ++c) {
-                        const uint64_t w = ttk[(a >> 3) + 16 * c];
-                        v[c] = make_uint2((uint32_t)w, (uint32_t)(w >> 32));
-                    }
-                };
-                auto conv = [&](const uint2(&v)[4], uint32_t aword, int h) {
-                    const float sc = __uint_as_float(aword);
-#pragma unroll
-                    for (int c = 0; c < 4; ++c) {
-                        xm_s2 cv;
-                        if (XF) {
-                            asm("v_cvt_scalef32_pk_bf8_bf16 %0, %1, %2" : "=v"(cv) : "v"(v[c].x), "v"(sc));
-                            cv = __builtin_amdgcn_cvt_scalef32_pk_bf8_bf16(cv, __builtin_bit_cast(xm_b2, v[c].y), sc, true);
-                        } else {
-                            asm("v_cvt_scalef32_pk_fp8_bf16 %0, %1, %2" : "=v"(cv) : "v"(v[c].x), "v"(sc));
-                            cv = __builtin_amdgcn_cvt_scalef32_pk_fp8_bf16(cv, __builtin_bit_cast(xm_b2, v[c].y), sc, true);
-                        }
-                        av[4 * h + c] = __builtin_bit_cast(int, cv);
-                    }
-                };
+                auto tread = [&](uint32_t aword, int h, uint2(&v)[4]) { xm_table_fetch(tt0 + h * TTK * 4, xm_table_addr(aword, base), v); };
+                auto conv = [&](const uint2(&v)[4], uint32_t aword, int h) { xm_convert<XF>(v, aword, h, av); };
                 // (a volatile u64 like the table reads: one ds_read_b64 that stays where the source puts it)
-                auto aread = [&](int b) {
-                    const uint64_t w = *(xm_lds_u64 *)&sm.aw[g][2 * (16 * (RB * wr + b) + r16)];
-                    return make_uint2((uint32_t)w, (uint32_t)(w >> 32));
-                };
+                auto aread = [&](int b) { return xm_a_pair(&sm.aw[g][2 * (16 * (RB * wr + b) + r16)]); };
                 // The stages are in source order and pinned (sched_barrier: the scheduler otherwise moves the
                 // asm conversions across the reads); the compiler's own s_waitcnt then count the reads in flight
                 uint2 va[4], vb[4];
@@ -1300,39 +1196,14 @@ __global__ __launch_bounds__(256, (XmWaves<AF32, EMIT>::value)) void gemm_f8mx_k
                 }
 #pragma unroll
                 for (int h = 0; h < 2; ++h) {
-                    uint32_t a;
-                    asm("v_and_or_b32 %0, %1, %2, %3" : "=v"(a) : "v"(awh[h]), "s"(XM_ROW_MASK), "v"(base));
-                    __builtin_assume((a & 7u) == 0u);
-                    // (volatile: otherwise the two halves, used as different types, are split into
-                    // two loads and re-merged into a ds_read2_b32 -- half the LDS rate of ds_read_b64)
-                    xm_lds_u64 *ttk = (xm_lds_u64 *)(tt0 + h * TTK * 4);
                     uint2 v[4];
-#pragma unroll
-                    for (int c = 0; c < 4; ++c) {
-                        const uint64_t w = ttk[(a >> 3) + 16 * c];
-                        v[c] = make_uint2((uint32_t)w, (uint32_t)(w >> 32));
-                    }
-                    const float sc = __uint_as_float(awh[h]);
-#pragma unroll
-                    for (int c = 0; c < 4; ++c) {
-                        xm_s2 cv;
-                        if (XF) {
-                            asm("v_cvt_scalef32_pk_bf8_bf16 %0, %1, %2" : "=v"(cv) : "v"(v[c].x), "v"(sc));
-                            cv = __builtin_amdgcn_cvt_scalef32_pk_bf8_bf16(cv, __builtin_bit_cast(xm_b2, v[c].y), sc, true);
-                        } else {
-                            asm("v_cvt_scalef32_pk_fp8_bf16 %0, %1, %2" : "=v"(cv) : "v"(v[c].x), "v"(sc));
-                            cv = __builtin_amdgcn_cvt_scalef32_pk_fp8_bf16(cv, __builtin_bit_cast(xm_b2, v[c].y), sc, true);
-                        }
-                        av[4 * h + c] = __builtin_bit_cast(int, cv);
-                    }
+                    xm_table_fetch(tt0 + h * TTK * 4, xm_table_addr(awh[h], base), v);
+                    xm_convert<XF>(v, awh[h], h, av);
                 }
                 // A codes e4m3 (cbsz 0) or bf8 (cbsz 1); the selection operand is e4m3 (blgp 0)
                 dq[b] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(av, sel, dq[b], XF ? 1 : 0, 0, 0, sca, 0, 127);
             }
         }
-#if XM_BDMA
-        __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): the next tile's B chunks (read by the next build)
-#endif
         __syncthreads();
     }
     FP8A_CLK_MARK(clk_tb)
@@ -1368,13 +1239,11 @@ __global__ __launch_bounds__(256, (XmWaves<AF32, EMIT>::value)) void gemm_f8mx_k
     float *ct = smu.ct;
     const StoreCtx sc = p.splits == 1 ? store_ctx<EMIT>(p) : StoreCtx{};  // (a split launch stores raw partials)
     const int ety = tid & 15, etx = tid >> 4, cb = etx % (BNT / 4), sub = etx / (BNT / 4);
-#if !XM_SETUP64
     constexpr bool EPT = BMT / SR > 1;  // the BN parameters once per tile where it has more than one slab
     // (a single-slab tile takes it where the slab's values are in registers: ahead of the LDS pass it is live
     // across it for nothing)
     XmStoreTile stt;
     if (EPT) stt = xm_store_tile<EPT>(p, splitu, n0u + (uint32_t)(cb * TN));
-#endif
 #pragma unroll
     for (int h = 0; h < BMT / SR; ++h) {
         if (h > 0) __syncthreads();  // the previous slab is read (the K loop's last barrier covers h = 0)
@@ -1397,12 +1266,8 @@ __global__ __launch_bounds__(256, (XmWaves<AF32, EMIT>::value)) void gemm_f8mx_k
             for (int j = 0; j < TN; ++j) acc[i][j] = ct[(64 * sub + ety * TM + i) * CP + cb * TN + j];
         // (GELU tails: run_gemm never emits.)  One copy of the store; sc says, uniformly, whether its
         // quantizers and words take the fast forms (option "fq_fast", every guard passed) or the literal ones
-#if XM_SETUP64
-        store_tile<EMIT, !EMIT, true>(p, split, m0 + SR * h + 64 * sub, n0, ety, cb, acc, sc);
-#else
         if (!EPT) stt = xm_store_tile<EPT>(p, splitu, n0u + (uint32_t)(cb * TN));
         store_tile_xm<EMIT, !EMIT, EPT>(p, stt, m0u + (uint32_t)(SR * h + 64 * sub + ety * TM), acc, sc);
-#endif
     }
     // In-launch split-K sum (p.skcnt: option "splitk_fixup", E4M3).  Every split block publishes its partial
     // tile -- stores drained, barrier, one agent-scope release by thread 0, one relaxed agent-scope ticket on

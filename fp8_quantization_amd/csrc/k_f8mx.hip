@@ -8,8 +8,19 @@
 #define FP8A_OWN_F8MX_DECODE (FP8A_XF_PART == 0)
 #include "fp8approx_launch.h"
 #include "gemm_f8mx.h"
+#include <type_traits>
 
 namespace fp8a {
+
+// f(std::true_type) where b holds and the build allows the `true` form, else f(std::false_type): a runtime
+// boolean as a template argument
+template <bool ALLOWED, class F>
+static void with_bool(bool b, F &&f) {
+    if constexpr (ALLOWED) {
+        if (b) return f(std::true_type{});
+    }
+    f(std::false_type{});
+}
 
 template <int NCG, int RB, int XF>
 static void launch_shape(const GemmArgs &a0, hipStream_t s) {
@@ -27,52 +38,33 @@ static void launch_shape(const GemmArgs &a0, hipStream_t s) {
         fastdiv_params((uint32_t)a.Wo, a.owo_mul, a.owo_shift);
     }
     if (a.nchw) fastdiv_params((uint32_t)a.hw, a.shw_mul, a.shw_shift);
-    // (the emitting instances only where this launch writes the next convolution's word image
-    // from its own store: unsplit, or split with the in-launch sum -- fp8a_conv2d_chain)
+    // Which instance a launch runs -- the one place that says which of gemm_f8mx_kernel's template arguments go
+    // together (gemm_f8mx.h explains each):
+    //   EMIT  = the launch writes the next convolution's word image from its own store (fp8a_conv2d_chain):
+    //           a.em.w, unsplit or split with the in-launch sum
+    //   AF32  = a.af32, A staged from fp32
+    //   FIX   = the in-launch split-K sum, a.skcnt: E4M3 (XF 0) only
+    //   piped = option "xm_pipe" on a word-staged plain form: XF != 2, not AF32
+    //   PIPE  = piped ? XmPipe<NCG, EMIT, FIX> : 0  (XmPipe 0, the 256 x 16 split-sum tiles: the unpiped instance)
+    //   WROWS = option "xm_wave_rows" on a piped 128 x 64 (NCG 4) instance without FIX
+    // A combination the rule excludes is never instantiated (with_bool<false> compiles the `false` arm alone).
     const bool emit = a.em.w != nullptr && (a.splits == 1 || a.skcnt != nullptr);
-    // option "xm_pipe": the word-staged plain forms run their software-pipelined instances (the fp32-staging
-    // and halved-block instances have none)
-    if constexpr (XF != 2) {
-        if (a.xm_pipe && !a.af32) {
-            if constexpr (XF == 0) {
-                if (a.skcnt != nullptr) {
-                    if (emit) gemm_f8mx_kernel<NCG, RB, false, XF, true, true, XmPipe<NCG, true, true>::value><<<g, Cf::NT, 0, s>>>(a);
-                    else gemm_f8mx_kernel<NCG, RB, false, XF, false, true, XmPipe<NCG, false, true>::value><<<g, Cf::NT, 0, s>>>(a);
-                    return;
-                }
-            }
-            // option "xm_wave_rows": the 128 x 64 instances with the math loop's waves by rows (gemm_f8mx.h WROWS)
-            if constexpr (NCG == 4) {
-                if (a.xm_wave_rows) {
-                    if (emit) gemm_f8mx_kernel<NCG, RB, false, XF, true, false, XmPipe<NCG, true, false>::value, true><<<g, Cf::NT, 0, s>>>(a);
-                    else gemm_f8mx_kernel<NCG, RB, false, XF, false, false, XmPipe<NCG, false, false>::value, true><<<g, Cf::NT, 0, s>>>(a);
-                    return;
-                }
-            }
-            if (emit) gemm_f8mx_kernel<NCG, RB, false, XF, true, false, XmPipe<NCG, true, false>::value><<<g, Cf::NT, 0, s>>>(a);
-            else gemm_f8mx_kernel<NCG, RB, false, XF, false, false, XmPipe<NCG, false, false>::value><<<g, Cf::NT, 0, s>>>(a);
-            return;
-        }
-    }
-    if constexpr (XF == 0) {
-        if (a.skcnt != nullptr) {  // split, summed inside the launch: the FIX instances
-            if (a.af32) {
-                if (emit) gemm_f8mx_kernel<NCG, RB, true, XF, true, true><<<g, Cf::NT, 0, s>>>(a);
-                else gemm_f8mx_kernel<NCG, RB, true, XF, false, true><<<g, Cf::NT, 0, s>>>(a);
-            } else {
-                if (emit) gemm_f8mx_kernel<NCG, RB, false, XF, true, true><<<g, Cf::NT, 0, s>>>(a);
-                else gemm_f8mx_kernel<NCG, RB, false, XF, false, true><<<g, Cf::NT, 0, s>>>(a);
-            }
-            return;
-        }
-    }
-    if (a.af32) {
-        if (emit) gemm_f8mx_kernel<NCG, RB, true, XF, true><<<g, Cf::NT, 0, s>>>(a);
-        else gemm_f8mx_kernel<NCG, RB, true, XF, false><<<g, Cf::NT, 0, s>>>(a);
-    } else {
-        if (emit) gemm_f8mx_kernel<NCG, RB, false, XF, true><<<g, Cf::NT, 0, s>>>(a);
-        else gemm_f8mx_kernel<NCG, RB, false, XF, false><<<g, Cf::NT, 0, s>>>(a);
-    }
+    // (The nesting, `true` arm first, is also the order of the kernels in the code object.)
+    with_bool<XF != 2>(a.xm_pipe && !a.af32, [&](auto piped) {
+        with_bool<XF == 0>(a.skcnt != nullptr, [&](auto fix) {
+            constexpr bool PIPED = decltype(piped)::value, FIX = decltype(fix)::value;
+            with_bool<PIPED && !FIX && NCG == 4>(a.xm_wave_rows != 0, [&](auto wrows) {
+                with_bool<!PIPED>(a.af32 != 0, [&](auto af32) {
+                    with_bool<true>(emit, [&](auto em) {
+                        constexpr bool EMIT = decltype(em)::value;
+                        constexpr int PIPE = PIPED ? XmPipe<NCG, EMIT, FIX>::value : 0;
+                        gemm_f8mx_kernel<NCG, RB, decltype(af32)::value, XF, EMIT, FIX, PIPE, decltype(wrows)::value>
+                            <<<g, Cf::NT, 0, s>>>(a);
+                    });
+                });
+            });
+        });
+    });
 }
 
 template <int XF>
@@ -105,18 +97,11 @@ static int signs_read(unsigned long long *v, bool reset) {
     return 0;
 }
 
-#if FP8A_XF_PART == 0
-void launch_f8mx_xf0(const GemmArgs &a, hipStream_t s) { launch_xf<0>(a, s); }
-int f8mx_clock_xf0(unsigned long long *v, bool reset) { return clock_read(v, reset); }
-int f8mx_signs_xf0(unsigned long long *v, bool reset) { return signs_read(v, reset); }
-#elif FP8A_XF_PART == 1
-void launch_f8mx_xf1(const GemmArgs &a, hipStream_t s) { launch_xf<1>(a, s); }
-int f8mx_clock_xf1(unsigned long long *v, bool reset) { return clock_read(v, reset); }
-int f8mx_signs_xf1(unsigned long long *v, bool reset) { return signs_read(v, reset); }
-#else
-void launch_f8mx_xf2(const GemmArgs &a, hipStream_t s) { launch_xf<2>(a, s); }
-int f8mx_clock_xf2(unsigned long long *v, bool reset) { return clock_read(v, reset); }
-int f8mx_signs_xf2(unsigned long long *v, bool reset) { return signs_read(v, reset); }
-#endif
+// launch_f8mx_xfN / f8mx_clock_xfN / f8mx_signs_xfN of this unit's part N (fp8approx_launch.h)
+#define XF_NAME2(name, part) name##part
+#define XF_NAME(name, part) XF_NAME2(name, part)
+void XF_NAME(launch_f8mx_xf, FP8A_XF_PART)(const GemmArgs &a, hipStream_t s) { launch_xf<FP8A_XF_PART>(a, s); }
+int XF_NAME(f8mx_clock_xf, FP8A_XF_PART)(unsigned long long *v, bool reset) { return clock_read(v, reset); }
+int XF_NAME(f8mx_signs_xf, FP8A_XF_PART)(unsigned long long *v, bool reset) { return signs_read(v, reset); }
 
 }  // namespace fp8a

@@ -186,3 +186,42 @@ def test_every_host_kernel_is_in_the_gfx950_code_object():
     assert len(stubs) > 20, "no kernel stubs found in the host part of the library"
     missing = sorted(stubs - kd)
     assert not missing, f"kernels registered on the host but absent from the gfx950 code objects: {missing[:5]}"
+
+
+def _f8mx_expected_instances(xf):
+    """gemm_f8mx_kernel's instances of result-grid form xf by launch_shape's rule (k_f8mx.hip), over every value
+    of the launch's runtime switches."""
+    import itertools
+
+    def xm_pipe(ncg, emit, fix):  # XmPipe<NCG, EMIT, FIX> (gemm_f8mx.h)
+        if ncg == 1 and fix:
+            return 0
+        return 2 if (ncg == 4 and not emit and not fix) else 1
+
+    shapes = [(1, 4), (2, 4)] + ([(4, 8)] if xf != 2 else [])
+    names = set()
+    for (ncg, rb), af32, emit, skcnt, pipe_opt, wave_rows in itertools.product(shapes, *[(False, True)] * 5):
+        fix = xf == 0 and skcnt
+        piped = xf != 2 and pipe_opt and not af32
+        pipe = xm_pipe(ncg, emit, fix) if piped else 0
+        wrows = piped and not fix and ncg == 4 and wave_rows
+        names.add("_ZN4fp8a16gemm_f8mx_kernelILi%dELi%dELb%dELi%dELb%dELb%dELi%dELb%dEEEvNS_8GemmArgsE"
+                  % (ncg, rb, af32, xf, emit, fix, pipe, wrows))
+    return names
+
+
+def test_f8mx_instances_are_exactly_the_launch_rule():
+    """The gfx950 code objects hold exactly the gemm_f8mx_kernel instances launch_shape's rule yields, no more
+    (compile time: part 0 alone is over 3 MB of code) and no fewer (a launch would abort).  Counts of the commit
+    that wrote the rule down, the same as its parent's: part 0 (E4M3) 36, part 1 (E5M2) 20, part 2 (E5M2
+    halved-block) 8."""
+    with open(_lib.LIB_PATH, "rb") as f:
+        so = f.read()
+    built = set()
+    for co in _gfx950_code_objects(so):
+        built |= {n[:-3] for n, _ in _elf_symbols(co) if n.endswith(".kd") and "gemm_f8mx_kernel" in n}
+    expected = [_f8mx_expected_instances(xf) for xf in range(3)]
+    assert [len(e) for e in expected] == [36, 20, 8]
+    want = set().union(*expected)
+    assert sorted(built - want) == [], "instances the rule does not yield"
+    assert sorted(want - built) == [], "instances the rule yields but the library lacks"

@@ -4,8 +4,8 @@ setup), the K loop, after the K loop's last barrier (the NaN test, the store, th
 
     FP8A_LIB_PATH=<a -DFP8A_CLOCK_STAMP=1 build> python tools/phase_probe.py [--batch 1024] [--layers l1.c,..]
 
-Needs a clock-stamp build (tools/gemm_bench.py --build-diag makes one; add -DXM_SETUP64=1 through
-FP8A_HIPCC_FLAGS for the 64-bit index code).  Each layer runs as a ResNet-18 block runs it -- the stem with
+Needs a clock-stamp build (tools/gemm_bench.py --build-diag makes one; for the 64-bit index code build the
+parent commit of "gemm_f8mx: 32-bit tile setup and store indexing" the same way).  Each layer runs as a ResNet-18 block runs it -- the stem with
 BN + ReLU in the store, the 3 x 3 layers with BN + ReLU and the next convolution's word image emitted, the
 1 x 1 downsampling layers plain -- on non-negative on-grid activations made on the device.  One line per layer:
 workgroups, s_memtime ticks per workgroup and the three shares (fp8a_clock_stats with reset bit 1), and the
