@@ -18,6 +18,10 @@ result quantizer Q_R: with per-product quantization (qbma) the product exponent 
 from three binades below the flush point 2^(-bR - M) (half the subnormal quantum u = 2^(1 - bR - M)) through
 the subnormal band up into the normal range, as far as the budget allows for the case's K; without it the
 terms' unit is the product of the operands' own steps and the windows are a few binades per operand.
+
+The non-square geometry cases (GEO_CONVS, GEO_TBDW, QAMAA_CONV, chain_cases; tests/test_gpu_conv_geometry.py) are
+ordinary cases of this table whose (h, w) pairs differ; exchanged() / conv_output() serve the CPU file's proof that
+each of them tells an exchanged pair.
 """
 import functools
 import math
@@ -323,7 +327,10 @@ CONVS = [
 
 def _conv(fam, E, M, table, flags, cfg, **kw):
     tag = kw.pop("tag", "")
-    geo = f"c{cfg['cin']}o{cfg['cout']}k{cfg['k']}s{cfg['s']}p{cfg['p']}d{cfg['d']}g{cfg['g']}hw{cfg['hw']}"
+    geo = f"c{cfg['cin']}o{cfg['cout']}k{geo_tag(cfg['k'])}s{geo_tag(cfg['s'])}p{geo_tag(cfg['p'])}" \
+          f"d{geo_tag(cfg['d'])}g{cfg['g']}hw{geo_tag(cfg['hw'])}"
+    if "name" in cfg:                                   # (the geometry cases go by their names)
+        geo = cfg["name"]
     key = f"conv-{fam}-E{E}M{M}-{table}-f{flags}-{geo}" + ("-posA" if kw.get("posA") else "")
     cid = key + (f"-{tag}" if tag else "")
     return dict(kind="conv", id=cid, pkey=key, fam=fam, E=E, M=M, table=table, flags=flags, cfg=cfg, **kw)
@@ -335,6 +342,52 @@ def conv_cases():
         Kg = cfg["cin"] // cfg["g"] * cfg["k"] ** 2
         out += [_conv("f8mx", 4, 3, "nocomp", FL, cfg), _conv("tt" if Kg < 64 else "tt16", 3, 4, "nocomp", FL, cfg),
                 _conv("tt", 2, 5, "nocomp", FL, cfg), _conv("fast", 4, 3, "nocomp", FL_FAST, cfg)]
+    return out
+
+
+# ------------------------------------------------------------------------------------------ non-square geometry
+# Every other convolution case gives the approximate product one number per (h, w) pair.  Here no pair that can
+# differ is equal by accident: H != W throughout, and per case the kernel, stride, padding or dilation differ in
+# the direction the name says.  K <= 288 (the deepest case above), so the windows are those of the cases above.
+def _geo(name, B, cin, H, W, cout, k, s, p, d, g):
+    return dict(name=name, B=B, cin=cin, cout=cout, k=k, s=s, p=p, d=d, g=g, hw=(H, W))
+
+
+GEO_CONVS = [
+    _geo("h9w16", 2, 8, 9, 16, 24, (3, 3), (1, 1), (1, 1), (1, 1), 1),        # Ho != Wo, W % 4 == 0: widened left border
+    _geo("h16w9", 2, 8, 16, 9, 24, (3, 3), (1, 1), (1, 1), (1, 1), 1),        # transposed: W % 4 != 0, H W % 4 == 0
+    _geo("k1x7", 2, 6, 10, 12, 20, (1, 7), (1, 1), (0, 3), (1, 1), 1),        # ph = 0, pw = 3 widened
+    _geo("k7x1", 2, 6, 12, 10, 20, (7, 1), (1, 1), (3, 0), (1, 1), 1),        # pw = 0, ph = 3
+    _geo("dense-geo", 2, 16, 15, 17, 24, (3, 3), (2, 1), (1, 2), (1, 2), 1),  # the exact product's rectangular case
+    _geo("dense-geo-t", 2, 16, 17, 15, 24, (3, 3), (1, 2), (2, 1), (2, 1), 1),
+    _geo("k3x2-g2", 2, 8, 11, 13, 20, (3, 2), (1, 1), (1, 0), (1, 1), 2),     # even kw, groups, kh != kw
+    _geo("pad-wide", 1, 4, 6, 12, 16, (3, 3), (1, 1), (3, 5), (1, 1), 1),     # pw > 4, W % 4 == 0; all-padding outputs
+    _geo("k1-s2x1", 2, 32, 12, 15, 16, (1, 1), (2, 1), (0, 0), (1, 1), 1),    # the fp32-staged A form, sh != sw
+    _geo("k1-padded", 2, 16, 7, 10, 24, (1, 1), (1, 1), (1, 0), (1, 1), 1),   # 1 x 1 that is not fp32-staged
+    _geo("k2x4-s2x3", 2, 8, 13, 14, 24, (2, 4), (2, 3), (0, 1), (1, 1), 1),   # K = 64: E3M4 on gemm_tt16
+]
+GEO_WIDE = ("h9w16", "h16w9", "dense-geo", "dense-geo-t")  # the widest M (288, 288, 272, 272): the 128 x 64 store
+GEO_WIDE_OPTS = [{"xm_ncg": 4, "xm_wave_rows": 0}, {"xm_ncg": 4, "xm_wave_rows": 1}]
+# the v5 model on a padded convolution: with_UF_opt, as tbdw_cases (the padding's zeros are operands too)
+FL_V5_GEO = pc.v5_flag_word(True, False, True)
+
+
+def geo_conv_cases():
+    """Per geometry one case per product family; gemm_f8mx's 128 x 64 instances on the widest M; the 1 x 1
+    strided case a second time with the fp32 staging off (the pre-pass)."""
+    out = []
+    for cfg in GEO_CONVS:
+        kh, kw = cfg["k"]
+        Kg = cfg["cin"] // cfg["g"] * kh * kw
+        out += [_conv("f8mx", 4, 3, "nocomp", FL, cfg), _conv("f8mx", 5, 2, "zero", FL, cfg),
+                _conv("tt", 2, 5, "nocomp", FL, cfg), _conv("tt" if Kg < 64 else "tt16", 3, 4, "nocomp", FL, cfg),
+                _conv("fast", 4, 3, "nocomp", FL_FAST, cfg), _conv("v5mx", 5, 2, "zero", FL_V5_GEO, cfg),
+                _conv("v5fast", 4, 3, "d3", FL_V5_GEO, cfg)]
+        if cfg["name"] in GEO_WIDE:
+            out += [_conv("f8mx", 4, 3, "nocomp", FL, cfg, opts=o, tag=_opt_tag(o)) for o in GEO_WIDE_OPTS]
+        if cfg["name"] == "k1-s2x1":
+            out += [_conv("f8mx", 4, 3, "nocomp", FL, cfg, opts={"af32_maxct": 0}, tag="af32_maxct0"),
+                    _conv("f8mx", 5, 2, "zero", FL, cfg, opts={"af32_maxct": 0}, tag="af32_maxct0")]
     return out
 
 
@@ -410,6 +463,11 @@ QAMAA = dict(id="qamaa-E4M3-65x70x63", pkey="qamaa-E4M3-65x70x63", kind="qamaa",
              shape=(65, 70, 63), maxval=2.5)
 
 
+# fp8a_conv2d_qamaa on the k3x2-g2 geometry (even kw, groups, kh != kw): K = 24 per group
+QAMAA_CONV = dict(id="qamaa-E4M3-conv-k3x2-g2", pkey="qamaa-E4M3-conv-k3x2-g2", kind="qconv", fam="qamaa", E=4, M=3,
+                  flags=0, maxval=2.5, geo=_geo("k3x2-g2", 2, 8, 11, 13, 20, (3, 2), (1, 1), (1, 0), (1, 1), 2))
+
+
 def _product_terms(A, B):
     return A.astype(np.float64)[:, :, None] * B.astype(np.float64)[None, :, :]
 
@@ -477,6 +535,36 @@ def _qamaa_problem(c):
     return dict(A=A.astype(np.float32), B=B, bR=int(bias[0]), parts=[(A, B, T.reshape(P.shape), slice(None))])
 
 
+def _qamaa_operands(rng, M, lo, hi, xshape, wshape):
+    """_qamaa_problem's operands: A over all but two binades of the window, B over three."""
+    wa = (hi - lo) - 2
+    A = draw(rng, 5, M, xshape, 0, 8, 8 + wa, 0.1) * np.float32(2.0 ** (lo - 16))
+    return A.astype(np.float32), draw(rng, 5, M, wshape, 0, 8, 10, 0.1)
+
+
+def _qconv_problem(c):
+    """_qamaa_problem for the convolution entry point: x and w drawn as its A and B, one part per group."""
+    from oracle import oracle as orc
+    E, M, g = c["E"], c["M"], c["geo"]
+    (H, W), (kh, kw) = g["hw"], g["k"]
+    cig, cog = g["cin"] // g["g"], g["cout"] // g["g"]
+    K = cig * kh * kw
+    _, bias = orc.fp8_fake_quant(np.ones(1, np.float32), c["maxval"], E, M)
+    lu = 1 - int(bias[0]) - M
+    rng = np.random.default_rng([SEED + 19, g["cin"], g["cout"], H, W, kh, kw])
+    x, w = _qamaa_operands(rng, M, lu - 4, lu + BUDGET_LOG2 - 3 - _clog2(K), (g["B"], g["cin"], H, W),
+                           (g["cout"], cig, kh, kw))
+    cols = unfold(x, g)
+    parts = []
+    for i in range(g["g"]):
+        Ag = np.ascontiguousarray(cols[:, i * K:(i + 1) * K])
+        Bg = np.ascontiguousarray(w[i * cog:(i + 1) * cog].reshape(cog, -1).T)
+        P = (Ag[:, :, None] * Bg[None, :, :]).astype(np.float32)   # exact: two 4-bit significands
+        T, _ = orc.fp8_fake_quant(P.reshape(1, -1), c["maxval"], E, M)
+        parts.append((Ag, Bg, T.reshape(P.shape), slice(i * cog, (i + 1) * cog)))
+    return dict(x=x, w=w, bR=int(bias[0]), parts=parts)
+
+
 # ------------------------------------------------------------------------------------------ tensor-bias depthwise
 FL_TB_DIRECT = pc.flag_word(True, False, True, False)   # s2n off: conv_tb_direct_kernel alone
 TB_PLANES = [7, 9, 14]
@@ -507,29 +595,190 @@ def tbdw_cases():
     return out
 
 
+def _tbgeo(name, B, cin, H, W, cout, g, k, s, p, d):
+    return dict(name=name, B=B, cin=cin, cout=cout, g=g, hw=(H, W), k=k, s=s, p=p, d=d)
+
+
+# Groups with one output channel (cout == groups) on non-square geometry: the branches of the tensor-bias kernels
+# that the 3 x 3, padding-1, one-input-channel layers above never reach.
+GEO_TBDW = [
+    _tbgeo("dw-p0x1", 2, 12, 9, 14, 12, 12, (3, 3), 1, (0, 1), 1),        # ph != pw in all staged forms
+    _tbgeo("dw-p1x0-s2", 2, 12, 14, 9, 12, 12, (3, 3), 2, (1, 0), 1),     # the same at stride 2, transposed
+    _tbgeo("dw-p2x2", 2, 8, 7, 12, 8, 8, (3, 3), 1, (2, 2), 1),           # border wider than the kernel's reach
+    _tbgeo("dw-p1x5", 1, 8, 6, 12, 8, 8, (3, 3), 1, (1, 5), 1),           # pw > 4: the staged forms' column guards
+    _tbgeo("kh1", 2, 8, 8, 11, 8, 8, (1, 3), 1, (0, 1), 1),               # the general kh loop
+    _tbgeo("kh5-s2", 2, 8, 13, 10, 8, 8, (5, 3), 2, (2, 1), 1),           # kh = 5; the two-row form's 2 + 5 rows
+    _tbgeo("kh2-dh2", 2, 8, 10, 9, 8, 8, (2, 3), 1, (1, 1), (2, 1)),      # r * dh stepping; tbx_rw = 2 gives way
+    _tbgeo("cig3-s1", 2, 12, 9, 10, 4, 4, (3, 3), 1, (1, 1), 1),          # the cpg loop, K = 27
+    _tbgeo("cig3-s2", 2, 12, 9, 10, 4, 4, (3, 3), 2, (1, 1), 1),
+    _tbgeo("kw2", 2, 8, 9, 11, 8, 8, (3, 2), 1, (1, 0), 1),               # no table form: conv_tb_fast_kernel
+    _tbgeo("s2x1", 2, 8, 11, 9, 8, 8, (3, 3), (2, 1), (1, 1), 1),         # sh != sw: conv_tb_fast_kernel
+]
+TBX_OPTS = [{"tbs": tbs, "tbx_rw": rw} for tbs in (0, 1, 2) for rw in (1, 2)]
+
+
+def _tbdw_geo(form, E, M, table, flags, geo, opts):
+    key = f"tbdw-E{E}M{M}-{table}-f{flags}-{geo['name']}"
+    return dict(kind="tbdw", id=key + (f"-{_opt_tag(opts)}" if opts else ""), pkey=key, fam=form, E=E, M=M, table=table,
+                flags=flags, geo=geo, opts=opts, C=geo["cout"], B=geo["B"])
+
+
+def geo_tbdw_cases():
+    """Per geometry the option sets tbdw_cases sweeps, the table forms on E5M2 too."""
+    out = []
+    for geo in GEO_TBDW:
+        out += [_tbdw_geo("tbx", 4, 3, "nocomp", FL, geo, o) for o in TBX_OPTS]
+        out += [_tbdw_geo("tbx", 5, 2, "zero", FL, geo, o) for o in TBX_OPTS]
+        out += [_tbdw_geo("tb_fast", 3, 4, "nocomp", FL, geo, {}), _tbdw_geo("tb_fast", 2, 5, "nocomp", FL, geo, {}),
+                _tbdw_geo("tb_direct", 4, 3, "nocomp", FL_TB_DIRECT, geo, {})]
+        out += [_tbdw_geo("v5dw", 5, 2, "zero", FL_V5_GEO, geo, {"v5ds": v}) for v in (0, 1)]
+    return out
+
+
+def v5dw_word_form(geo):
+    """conv_v5_depthwise's rule for its word forms (else the literal kernel alone, counted as `exact`)."""
+    (kh, kw), (sh, sw), (_, dw) = pair(geo["k"]), pair(geo["s"]), pair(geo["d"])
+    return geo["cin"] == geo["g"] and kw == 3 and kh <= 5 and dw == 1 and sh == sw and sw in (1, 2)
+
+
+def tbdw_geo(c):
+    """The geometry of a tensor-bias case: its own (the geometry cases), or the depthwise 3 x 3, padding 1, on a
+    square plane."""
+    return c.get("geo") or dict(B=c["B"], cin=c["C"], cout=c["C"], g=c["C"], hw=c["hw"], k=3, s=c["stride"], p=1, d=1)
+
+
 def _tbdw_problem(c):
     from oracle import oracle as orc
-    E, M, fl, C, hw = c["E"], c["M"], c["flags"], c["C"], c["hw"]
+    E, M, fl, g = c["E"], c["M"], c["flags"], tbdw_geo(c)
+    C, cig = g["cout"], g["cin"] // g["g"]
+    (H, W), (kh, kw) = pair(g["hw"]), pair(g["k"])
+    Kg = cig * kh * kw
     bA, bW, bR = case_biases(c, C)
     tfl = fl if fl & pc.V5 else fl | pc.TB
-    (a_lo, a_hi), (b_lo, b_hi) = windows(E, M, bA, bW, bR, 9, tfl)
-    rng = np.random.default_rng([SEED + 13, E, M, hw, c["stride"], int(fl)])
-    x = draw(rng, E, M, (c["B"], C, hw, hw), bA, a_lo, a_hi, 0.0 if fl & pc.V5 else 0.1)
+    (a_lo, a_hi), (b_lo, b_hi) = windows(E, M, bA, bW, bR, Kg, tfl)
+    seed = [SEED + 13, E, M, c["hw"], c["stride"], int(fl)] if "geo" not in c else \
+        [SEED + 17, E, M, g["cin"], C, H, W, kh, kw, *pair(g["s"]), *pair(g["p"]), *pair(g["d"]), int(fl)]
+    rng = np.random.default_rng(seed)
+    x = draw(rng, E, M, (g["B"], g["cin"], H, W), bA, a_lo, a_hi, 0.0 if fl & pc.V5 else 0.1)
     sh = (C, 1, 1, 1)
-    w = draw(rng, E, M, (C, 1, 3, 3), bW.reshape(sh), b_lo.reshape(sh), b_hi.reshape(sh), 0.0)
-    cols = unfold(x, dict(k=3, d=1, p=1, s=c["stride"]))
+    w = draw(rng, E, M, (C, cig, kh, kw), bW.reshape(sh), b_lo.reshape(sh), b_hi.reshape(sh), 0.0)
+    cols = unfold(x, g)
     tab = case_table(c)
     parts = []
-    for ch in range(C):
-        Ac = np.ascontiguousarray(cols[:, ch * 9:(ch + 1) * 9])
-        Bc = np.ascontiguousarray(w[ch].reshape(1, 9).T)
+    for ch in range(C):                                  # (one output channel per group: group ch)
+        Ac = np.ascontiguousarray(cols[:, ch * Kg:(ch + 1) * Kg])
+        Bc = np.ascontiguousarray(w[ch].reshape(1, Kg).T)
         parts.append((Ac, Bc, orc.terms(Ac, Bc, E, M, bA, bW[ch:ch + 1], bR, tab, tfl), slice(ch, ch + 1)))
     return dict(x=x, w=w, bA=bA, bB=bW, bR=bR, table=tab, parts=parts, flags=tfl)
 
 
 def all_cases():
     return matmul_cases() + splitk_cases() + schedule_cases() + band_cases() + conv_cases() + bmm_cases() + \
-        dense_cases() + [QAMAA] + tbdw_cases()
+        dense_cases() + [QAMAA] + tbdw_cases() + geo_conv_cases() + geo_tbdw_cases() + [QAMAA_CONV]
+
+
+def geo_cases():
+    return geo_conv_cases() + geo_tbdw_cases()
+
+
+# ------------------------------------------------------------------------------------------ chained pairs
+# fp8a_conv2d_chain on non-square geometry: the producer is one of the geometry cases above, so its output y is known
+# by bits on the CPU; the consumer quantizes y itself (fused input quantizer, maxval `mx`) and its own terms are
+# drawn inside the budget too (its weights' codes `wcodes`, its result bias `bR`), so that its output is compared by
+# bits as well.  form: the words the producer emits (0 matrix core, 1 tensor-bias table form, 2 v5).
+def _chain(name, E, M, producer, form, cout, k, p, g, mx, bW, bR, wcodes, flags=None):
+    return dict(id=f"chain-{name}-E{E}M{M}", kind="chain", E=E, M=M, producer=producer, form=form, cout=cout, k=k, p=p,
+                g=g, mx=mx, bW=bW, bR=bR, wcodes=wcodes, flags=FL if flags is None else flags)
+
+
+def _geo_id(cases, name, E, M, fam):
+    return next(c["id"] for c in cases if (c.get("cfg") or c["geo"])["name"] == name and (c["E"], c["M"]) == (E, M) and
+                c["fam"] == fam and (c.get("opts") or {}) in ({}, {"tbs": 2, "tbx_rw": 2}, {"v5ds": 1}))
+
+
+def chain_cases():
+    conv, tb = geo_conv_cases(), geo_tbdw_cases()
+    out = []
+    for (E, M, bW, bR, wc) in ((4, 3, 14, 8, (4, 12)), (5, 2, 22, 10, (13, 21))):
+        h9w16, dw = _geo_id(conv, "h9w16", E, M, "f8mx"), _geo_id(tb, "dw-p0x1", E, M, "tbx")
+        out += [_chain("a-1x7", E, M, h9w16, 0, 20, (1, 7), (0, 3), 1, 5.5, bW, bR, wc),        # matrix-core consumer
+                _chain("b-dw3x3", E, M, h9w16, 1, 24, (3, 3), (0, 1), 24, 5.5, bW, bR, (10, 12)),  # table-form consumer
+                _chain("c-dw-1x1", E, M, dw, 0, 16, (1, 1), (0, 0), 1, 5.5, bW, bR, wc)]        # staged depthwise producer
+    out.append(_chain("d-v5-1x1", 5, 2, _geo_id(tb, "dw-p0x1", 5, 2, "v5dw"), 2, 16, (1, 1), (0, 0), 1, 3.5, 20, 12,
+                      (16, 24), flags=FL_V5_GEO))
+    return out
+
+
+def chain_problem(c):
+    """The producer's problem and NCHW output, the consumer's geometry, weights, biases and its oracle terms on the
+    oracle's quantizer of y."""
+    from oracle import oracle as orc
+    pc_ = CASES[c["producer"]]
+    pp = problem_of.__wrapped__(pc_["pkey"])
+    pg = pc_.get("cfg") or pc_["geo"]
+    Ho, Wo = conv_out_hw(dict(pg, hw=pair(pg["hw"])))
+    y = np.concatenate([expected(T) for (_, _, T, _) in pp["parts"]], axis=1)
+    y = np.ascontiguousarray(y.reshape(pg["B"], Ho, Wo, pg["cout"]).transpose(0, 3, 1, 2))
+    E, M = c["E"], c["M"]
+    q, bias = orc.fp8_fake_quant(y, c["mx"], E, M)
+    geo = dict(name=c["id"], B=pg["B"], cin=pg["cout"], cout=c["cout"], g=c["g"], hw=(Ho, Wo), k=c["k"], s=1, p=c["p"], d=1)
+    cig, cog = geo["cin"] // geo["g"], geo["cout"] // geo["g"]
+    rng = np.random.default_rng([SEED + 23, E, M, c["form"], c["cout"], *c["k"]])
+    w = draw(rng, E, M, (c["cout"], cig) + tuple(c["k"]), c["bW"], c["wcodes"][0], c["wcodes"][1], 0.0)
+    bW = np.full(c["cout"], c["bW"], np.int32)
+    fl = c["flags"] | (pc.TB if cog == 1 and not c["flags"] & pc.V5 else 0)
+    tab = case_table(pc_)
+    cols = unfold(q, geo)
+    Kg = cig * c["k"][0] * c["k"][1]
+    parts = []
+    for i in range(geo["g"]):
+        sl = slice(i * cog, (i + 1) * cog)
+        Ag = np.ascontiguousarray(cols[:, i * Kg:(i + 1) * Kg])
+        Bg = np.ascontiguousarray(w[sl].reshape(cog, -1).T)
+        parts.append((Ag, Bg, orc.terms(Ag, Bg, E, M, int(bias[0]), bW[sl], c["bR"], tab, fl), sl))
+    return dict(producer=pp, pcase=pc_, pgeo=pg, y=y, q=q, geo=geo, w=w, bA=int(bias[0]), bB=bW, bR=c["bR"], table=tab,
+                parts=parts, flags=fl)
+
+
+def word_image_bytes(Bn, C, H, W, ph, pw):
+    """The size the layout comment of csrc/fp8approx.hip gives: a 256-byte header, then [Bn][C][H + 2 ph][W'] words
+    rounded up to 256 bytes; W' = W + 2 pw, or with 0 < pw <= 4 and W % 4 == 0 the left border widened to 4 and the row
+    rounded up to a multiple of 4."""
+    Wp = (W + 4 + pw + 3) // 4 * 4 if 0 < pw <= 4 and W % 4 == 0 else W + 2 * pw
+    return 256 + (Bn * C * (H + 2 * ph) * Wp * 4 + 255) // 256 * 256
+
+
+# ------------------------------------------------------------------------------------------ exchanged pairs
+EXCHANGES = ("p", "s", "d", "k", "hw")   # ph <-> pw, sh <-> sw, dh <-> dw, transposed taps, transposed planes
+
+
+def exchanged(geo, x, w, which):
+    """(geometry, x, w) of the problem a kernel would compute if it took one (h, w) pair the wrong way round:
+    the pair `which` of the geometry exchanged; for `k` the taps transposed with it, for `hw` the planes.  None if
+    that is the same problem."""
+    g = dict(geo)
+    g[which] = pair(geo[which])[::-1]
+    x2 = np.ascontiguousarray(np.swapaxes(x, 2, 3)) if which == "hw" else x
+    w2 = np.ascontiguousarray(np.swapaxes(w, 2, 3)) if which == "k" else w
+    same = g[which] == pair(geo[which]) and x2.shape == x.shape and w2.shape == w.shape and \
+        np.array_equal(x2, x) and np.array_equal(w2, w)
+    return None if same else (g, x2, w2)
+
+
+def conv_output(geo, x, w, mm):
+    """A convolution [B, Ho, Wo, cout] from the unfolded rows: mm(A [M, Kg], B [Kg, cog], channel slice) per group."""
+    cols = unfold(x, geo)
+    ng, cog = geo["g"], geo["cout"] // geo["g"]
+    Kg = cols.shape[1] // ng
+    out = np.empty((cols.shape[0], geo["cout"]), np.float32)
+    for i in range(ng):
+        sl = slice(i * cog, (i + 1) * cog)
+        out[:, sl] = mm(np.ascontiguousarray(cols[:, i * Kg:(i + 1) * Kg]),
+                        np.ascontiguousarray(w[sl].reshape(cog, -1).T), sl)
+    (kh, kw), (sh, sw), (ph, pw), (dh, dw) = (pair(geo[f]) for f in ("k", "s", "p", "d"))
+    H, W = x.shape[2], x.shape[3]
+    Ho, Wo = (H + 2 * ph - dh * (kh - 1) - 1) // sh + 1, (W + 2 * pw - dw * (kw - 1) - 1) // sw + 1
+    return out.reshape(x.shape[0], Ho, Wo, geo["cout"])
 
 
 # ------------------------------------------------------------------------------------------ problems
@@ -586,28 +835,47 @@ def _band_problem(c):
     return dict(A=A, B=B, bA=bA, bB=bB, bR=bR, spot=None)
 
 
+def pair(v):
+    """A geometry field as its (h, w) pair: an int stands for both."""
+    return (int(v), int(v)) if np.ndim(v) == 0 else (int(v[0]), int(v[1]))
+
+
+def geo_tag(v):
+    """A geometry field in a case id: 3 for an int (or an equal pair given as an int), 1x7 for a pair."""
+    return str(v) if np.ndim(v) == 0 else f"{v[0]}x{v[1]}"
+
+
 def conv_out_hw(cfg):
-    return (cfg["hw"] + 2 * cfg["p"] - cfg["d"] * (cfg["k"] - 1) - 1) // cfg["s"] + 1
+    """(Ho, Wo) of a convolution case; one int where every field of the case is one."""
+    (H, W), (kh, kw), (sh, sw), (ph, pw), (dh, dw) = (pair(cfg[f]) for f in ("hw", "k", "s", "p", "d"))
+    Ho, Wo = (H + 2 * ph - dh * (kh - 1) - 1) // sh + 1, (W + 2 * pw - dw * (kw - 1) - 1) // sw + 1
+    return Ho if all(np.ndim(cfg[f]) == 0 for f in ("hw", "k", "s", "p", "d")) else (Ho, Wo)
 
 
 def unfold(x, cfg):
-    """im2col of x [B, C, H, W] as rows [B * Ho * Wo, C * k * k] (torch.nn.functional.unfold's order)."""
+    """im2col of x [B, C, H, W] as rows [B * Ho * Wo, C * kh * kw] (torch.nn.functional.unfold's order); k, s, p,
+    d of cfg: an int or an (h, w) pair."""
     import torch
-    cols = torch.nn.functional.unfold(torch.from_numpy(np.ascontiguousarray(x)), (cfg["k"], cfg["k"]),
-                                      dilation=cfg["d"], padding=cfg["p"], stride=cfg["s"])
+    cols = torch.nn.functional.unfold(torch.from_numpy(np.ascontiguousarray(x)), pair(cfg["k"]),
+                                      dilation=pair(cfg["d"]), padding=pair(cfg["p"]), stride=pair(cfg["s"]))
     return cols.transpose(1, 2).reshape(-1, cols.shape[1]).numpy()
 
 
 def _conv_problem(c):
     E, M, cfg = c["E"], c["M"], c["cfg"]
+    (H, W), (kh, kw) = pair(cfg["hw"]), pair(cfg["k"])
     cig, cout = cfg["cin"] // cfg["g"], cfg["cout"]
-    K = cig * cfg["k"] ** 2
+    K = cig * kh * kw
     bA, bW, bR = case_biases(c, cout)
     (a_lo, a_hi), (b_lo, b_hi) = windows(E, M, bA, bW, bR, K, c["flags"])
-    rng = np.random.default_rng([11, E, M, cfg["cin"], cout, cfg["hw"], cfg["k"], int(c["flags"])])
-    x = draw(rng, E, M, (cfg["B"], cfg["cin"], cfg["hw"], cfg["hw"]), bA, a_lo, a_hi, 0.1)
+    seed = [11, E, M, cfg["cin"], cout, cfg["hw"], cfg["k"], int(c["flags"])]
+    if np.ndim(cfg["hw"]) or np.ndim(cfg["k"]):  # (a pair-valued geometry: every field of it in the seed)
+        seed = seed[:5] + [H, W, kh, kw, *pair(cfg["s"]), *pair(cfg["p"]), *pair(cfg["d"]), cfg["g"], int(c["flags"])]
+    rng = np.random.default_rng(seed)
+    zf = 0.0 if c["flags"] & pc.V5 else 0.1           # (v5: normal codes without zeros, see windows())
+    x = draw(rng, E, M, (cfg["B"], cfg["cin"], H, W), bA, a_lo, a_hi, zf)
     sh = (cout, 1, 1, 1)
-    w = draw(rng, E, M, (cout, cig, cfg["k"], cfg["k"]), bW.reshape(sh), b_lo.reshape(sh), b_hi.reshape(sh), 0.1)
+    w = draw(rng, E, M, (cout, cig, kh, kw), bW.reshape(sh), b_lo.reshape(sh), b_hi.reshape(sh), zf)
     if c.get("posA"):
         x = np.abs(x)
     return dict(x=x, w=w, bA=bA, bB=bW, bR=bR)
@@ -644,6 +912,8 @@ def problem_of(pkey):
         return _dense_problem(c)
     if c["kind"] == "qamaa":
         return _qamaa_problem(c)
+    if c["kind"] == "qconv":
+        return _qconv_problem(c)
     if c["kind"] == "tbdw":
         return _tbdw_problem(c)
     E, M, tab, fl = c["E"], c["M"], case_table(c), c["flags"]
@@ -699,9 +969,13 @@ def case_old_bar(p):
 
 def case_K(c):
     if c["kind"] == "conv":
-        return c["cfg"]["cin"] // c["cfg"]["g"] * c["cfg"]["k"] ** 2
+        kh, kw = pair(c["cfg"]["k"])
+        return c["cfg"]["cin"] // c["cfg"]["g"] * kh * kw
     if c["kind"] == "dconv":
         return c["geo"]["cin"] * c["geo"]["k"] ** 2
+    if c["kind"] == "qconv" or (c["kind"] == "tbdw" and "geo" in c):
+        kh, kw = pair(c["geo"]["k"])
+        return c["geo"]["cin"] // c["geo"]["g"] * kh * kw
     if c["kind"] in ("ddw", "tbdw"):
         return 9
     return c["shape"][1]

@@ -126,6 +126,79 @@ def test_budget_oracle_and_shares(group):
     assert not errs, f"{len(errs)} of {len(keys)} cases:\n" + "\n".join(errs)
 
 
+GEO_PROBLEMS = collections.OrderedDict()  # the non-square geometry problems, by geometry name
+for _c in xs.geo_cases() + [xs.QAMAA_CONV]:
+    _g = _c["cfg"] if _c["kind"] == "conv" else _c["geo"]
+    GEO_PROBLEMS.setdefault(_g["name"], collections.OrderedDict()).setdefault(_c["pkey"], (_c, _g))
+
+
+def _check_exchanges(c, geo):
+    """The case's expected output against what a kernel would give that took one (h, w) pair the wrong way round."""
+    p = xs.problem_of.__wrapped__(c["pkey"])
+    if c["fam"] == "qamaa":
+        def mm(A, B, sl):
+            return orc.matmul_qamaa(A, B, c["maxval"], 8, c["M"])[1]
+    else:
+        def mm(A, B, sl):
+            return orc.matmul(A, B, c["E"], c["M"], p["bA"], p["bB"][sl], p["bR"], p["table"], p.get("flags", c["flags"]))
+    want = np.concatenate([xs.expected(T) for (_, _, T, _) in p["parts"]], axis=1)
+    mine = xs.conv_output(geo, p["x"], p["w"], mm)
+    xs.assert_same(mine.reshape(want.shape), want, f"{c['pkey']}: conv_output against the terms")
+    want = want.reshape(mine.shape)
+    told = []
+    for which in xs.EXCHANGES:
+        ex = xs.exchanged(geo, p["x"], p["w"], which)
+        if ex is None:
+            continue
+        got = xs.conv_output(*ex, mm)
+        differ = 1.0 if got.shape != want.shape else float(np.mean(~pc.same_bits(got, want)))
+        assert differ >= 0.5, f"{c['pkey']}: with `{which}` exchanged only {differ:.2f} of the outputs differ"
+        told.append(which)
+    return told
+
+
+@pytest.mark.parametrize("name", list(GEO_PROBLEMS), ids=list(GEO_PROBLEMS))
+def test_geometry_cases_tell_an_exchanged_pair(name):
+    """Every non-square case: exchanging ph / pw, sh / sw, dh / dw, the taps' kh / kw or the planes' H / W -- each
+    exchange that changes the problem at all -- gives another output shape or differs in at least half of the
+    outputs.  A condition on the drawn data and sizes: a kernel with a transposed index cannot pass the case."""
+    items = list(GEO_PROBLEMS[name].values())
+    with ThreadPoolExecutor(min(8, len(items))) as ex:
+        futs = [(c["pkey"], ex.submit(_check_exchanges, c, g)) for c, g in items]
+    errs = [str(f.exception()) for _, f in futs if f.exception() is not None]
+    assert not errs, f"{len(errs)} of {len(items)} problems:\n" + "\n".join(errs)
+    for k, f in futs:  # H <-> W changes every case here, and so does at least one other pair
+        assert "hw" in f.result() and len(f.result()) >= 2, (k, f.result())
+
+
+@pytest.mark.parametrize("cid", [c["id"] for c in xs.chain_cases()])
+def test_chained_consumers_meet_the_budget_and_tell_an_exchange(cid):
+    """The consumer of each chained pair, on the oracle's quantizer of the producer's expected output: the budget, the
+    oracle's sum against the summed terms, at least 8 binades of terms and few zero outputs, and the exchanged pairs."""
+    c = next(v for v in xs.chain_cases() if v["id"] == cid)
+    p = xs.chain_problem(c)
+    lb = xs.case_budget_log2(p)
+    assert lb <= xs.BUDGET_LOG2, f"{cid}: max sum|T| = 2^{lb:.2f} u is over the 2^22 u budget"
+
+    def mm(A, B, sl):
+        return orc.matmul(A, B, c["E"], c["M"], p["bA"], p["bB"][sl], p["bR"], p["table"], p["flags"])
+    want = np.concatenate([xs.expected(T) for (_, _, T, _) in p["parts"]], axis=1)
+    for (A, B, T, sl) in p["parts"]:
+        xs.assert_same(mm(A, B, sl), xs.expected(T), f"{cid}: the oracle's sum against the summed terms", T)
+    nz = np.concatenate([np.abs(T[T != 0]).ravel() for (_, _, T, _) in p["parts"]])
+    assert np.unique(np.frexp(nz)[1]).size >= 8 and np.mean(want == 0) < 0.05
+    want = want.reshape(xs.conv_output(p["geo"], p["q"], p["w"], mm).shape)
+    told = 0
+    for which in xs.EXCHANGES:
+        ex = xs.exchanged(p["geo"], p["q"], p["w"], which)
+        if ex is not None:
+            got = xs.conv_output(*ex, mm)
+            differ = 1.0 if got.shape != want.shape else float(np.mean(~pc.same_bits(got, want)))
+            assert differ >= 0.5, f"{cid}: with `{which}` exchanged only {differ:.2f} of the outputs differ"
+            told += 1
+    assert told >= 1
+
+
 def test_unit_and_expected_on_known_values():
     T = np.array([[[0.75], [0.0], [-2.5]]], np.float32)  # multiples of 0.25
     assert xs.unit(T) == 0.25 and xs.unit(np.zeros(3, np.float32)) == 0.0

@@ -41,18 +41,25 @@ def _bits(t):
     return t.detach().cpu().contiguous().view(torch.int32)
 
 
+def _hw(v):
+    return (v, v) if isinstance(v, int) else tuple(v)
+
+
 def _run_pair(E, M, cin, cmid, cout, hw, Bn, k1, k2, p1, p2, epilogue, post, seed, bad_w=False, fmt_table=None):
     """producer conv1 (x -> y) and consumer conv2 (y -> z, fused input quantizer), unchained and
-    chained; returns (z, z_chained, consumer input bias pair)."""
+    chained; returns (z, z_chained, consumer input bias pair).  hw, k1, k2, p1, p2: an int or an (h, w) pair (the
+    producer keeps the plane's size: 2 p1 = k1 - 1 per direction)."""
+    (H, W), k1, k2, p1, p2 = _hw(hw), _hw(k1), _hw(k2), _hw(p1), _hw(p2)
+    assert (2 * p1[0], 2 * p1[1]) == (k1[0] - 1, k1[1] - 1), "the consumer's image is sized for the producer's input plane"
     from fp8_quantization_amd.approx_ops import approx_conv2d, make_flags, new_word_image, bn_act_epilogue
     from fp8_quantization_amd.error_tables import get_error_table_NN
     g = torch.Generator().manual_seed(seed)
     tab = fmt_table if fmt_table is not None else get_error_table_NN(E, M, False, 3, zero_table_ext=(E, M) == (5, 2))
     fl = make_flags(True, True, True)
     b = 2 ** (E - 1)
-    x = _grid(g, (Bn, cin, hw, hw), M).to(DEV)
-    w1 = _grid(g, (cmid, cin, k1, k1), M, -8, 0, 0.0).to(DEV)
-    w2 = _grid(g, (cout, cmid, k2, k2), M, -8, 0, 0.0).to(DEV)
+    x = _grid(g, (Bn, cin, H, W), M).to(DEV)
+    w1 = _grid(g, (cmid, cin) + k1, M, -8, 0, 0.0).to(DEV)
+    w2 = _grid(g, (cout, cmid) + k2, M, -8, 0, 0.0).to(DEV)
     if bad_w:  # off-grid weights: the producer's gated exact kernel recomputes their column units
         w1[3, 0, 0, 0] = 0.3333
     bA, bR1, bR2 = b + 2, b + 1, b
@@ -67,13 +74,13 @@ def _run_pair(E, M, cin, cmid, cout, hw, Bn, k1, k2, p1, p2, epilogue, post, see
     mx_out = torch.tensor([6.0], device=DEV)
     pst = None
     if post:
-        res = _grid(g, (Bn, cmid, hw, hw), M).to(DEV)
+        res = _grid(g, (Bn, cmid, H, W), M).to(DEV)
         pst = (res, 1, 0.0, float("inf"), (mx_out, 8, M, 1))
     mx2 = torch.tensor([5.5], device=DEV)
     qin2 = (mx2, 8, M, 1)
     bR2t = torch.tensor([bR2], dtype=torch.int32, device=DEV)
-    args1 = dict(flags=fl, padding=(p1, p1), epilogue=ep)
-    args2 = dict(flags=fl, padding=(p2, p2))
+    args1 = dict(flags=fl, padding=p1, epilogue=ep)
+    args2 = dict(flags=fl, padding=p2)
 
     def produce(chain=None):
         kw = dict(args1)
@@ -86,8 +93,8 @@ def _run_pair(E, M, cin, cmid, cout, hw, Bn, k1, k2, p1, p2, epilogue, post, see
 
     y = produce()
     z, ib, _ = approx_conv2d(y, w2, E, M, None, bW2, bR2t, tab, qin=qin2, **args2)
-    img = new_word_image(Bn, cmid, hw, hw, p2, p2, DEV)
-    y2 = produce(chain=(None, (img, (p2, p2), qin2, bR2t, M)))
+    img = new_word_image(Bn, cmid, H, W, p2[0], p2[1], DEV)
+    y2 = produce(chain=(None, (img, p2, qin2, bR2t, M)))
     assert torch.equal(_bits(y), _bits(y2)), "producer output changed by the emission"
     z2, ib2, _ = approx_conv2d(y2, w2, E, M, None, bW2, bR2t, tab, qin=qin2, chain=(img, None), **args2)
     torch.cuda.synchronize()

@@ -226,6 +226,9 @@ CONV_CASES = {
     "s2p1": dict(x=(2, 5, 9, 9), w=(6, 5, 3, 3), stride=(2, 2), padding=(1, 1), groups=1),
     "groups2": dict(x=(2, 4, 9, 9), w=(6, 2, 3, 3), stride=(1, 1), padding=(1, 1), groups=2),
     "depthwise": dict(x=(2, 5, 9, 9), w=(5, 1, 3, 3), stride=(1, 1), padding=(1, 1), groups=5),
+    # non-square (tests/exact_sums.py: GEO_CONVS dense-geo, GEO_TBDW kh5-s2): every (h, w) pair differs somewhere
+    "dense-geo": dict(x=(2, 16, 15, 17), w=(24, 16, 3, 3), stride=(2, 1), padding=(1, 2), dilation=(1, 2), groups=1),
+    "kh5-s2": dict(x=(2, 8, 13, 10), w=(8, 1, 5, 3), stride=(2, 2), padding=(2, 1), groups=8),
 }
 
 
@@ -247,7 +250,8 @@ def test_conv_check_equals_per_group_matmul_check(case, s2n):
     x = torch.from_numpy(xq).to(DEV)
     tab = _table(E, M)
     fl = fa.make_flags(True, s2n, True, False)
-    geo = dict(stride=c["stride"], padding=c["padding"], dilation=(1, 1), groups=c["groups"])
+    dil = c.get("dilation", (1, 1))
+    geo = dict(stride=c["stride"], padding=c["padding"], dilation=dil, groups=c["groups"])
     prod = fa.approx_conv2d(x, wq, E, M, bA, bW, bA, tab, flags=fl, **geo)
     y, G, st = fa.approx_conv2d_check(x, wq, E, M, bA, bW, bA, tab, flags=fl, prod=prod, **geo)
     print(case, "prod_max_rel", st.prod_max_rel, "max_err", st.max_err)
@@ -257,7 +261,7 @@ def test_conv_check_equals_per_group_matmul_check(case, s2n):
     tot = dict(n_out=0, a_norm=0, a_total=0, b_norm=0, b_total=0, r_norm=0, r_total=0, sum_err=0.0, sum_err2=0.0,
                sum_gold2=0.0, max_err=0.0)
     for g in range(groups):
-        rows = ApproxConv2dMixin.im2col(None, x[:, g * cig:(g + 1) * cig], kh, kw, c["stride"], c["padding"], (1, 1))
+        rows = ApproxConv2dMixin.im2col(None, x[:, g * cig:(g + 1) * cig], kh, kw, c["stride"], c["padding"], dil)
         wg = wq[g * cog:(g + 1) * cog].reshape(cog, -1).t()
         Cg, Gg, sg = fa.approx_matmul_check(rows, wg, E, M, bA, bW[g * cog:(g + 1) * cog], bA, tab,
                                             flags=fl | (_lib.TB if cog == 1 else 0))

@@ -40,25 +40,34 @@ def _codes(bias):
     return np.concatenate([v, -v]).astype(np.float32)
 
 
-def _dw_raw(x, w, bA, bW, bR, table, flags, stride, pad, fmt=(E, M)):
-    """fp8a_conv2d on a depthwise layer with a caller-owned workspace: (y, gate word)."""
+def _hw(v):
+    """A geometry argument as its (h, w) pair: an int stands for both."""
+    return (int(v), int(v)) if np.ndim(v) == 0 else (int(v[0]), int(v[1]))
+
+
+def _dw_raw(x, w, bA, bW, bR, table, flags, stride, pad, fmt=(E, M), dil=1, groups=None):
+    """fp8a_conv2d on a layer of single-output-channel groups (depthwise by default; w [Cout, cig, kh, kw] with
+    groups = Cin / cig) with a caller-owned workspace: (y, gate word).  stride, pad, dil: an int or an (h, w) pair."""
     from fp8_quantization_amd import _lib
     L = _lib.load()
-    Bn, C, H, W = x.shape
-    kh, kw = w.shape[2], w.shape[3]
-    Ho = (H + 2 * pad - kh) // stride + 1
-    Wo = (W + 2 * pad - kw) // stride + 1
+    Bn, Cin, H, W = x.shape
+    C, cig, kh, kw = w.shape
+    groups = Cin // cig if groups is None else groups
+    assert groups * cig == Cin and C % groups == 0, (x.shape, w.shape, groups)
+    (sh, sw), (ph, pw), (dh, dw) = _hw(stride), _hw(pad), _hw(dil)
+    Ho = (H + 2 * ph - dh * (kh - 1) - 1) // sh + 1
+    Wo = (W + 2 * pw - dw * (kw - 1) - 1) // sw + 1
     xt = torch.as_tensor(np.ascontiguousarray(x)).to(DEV)
     wt = torch.as_tensor(np.ascontiguousarray(w)).to(DEV)
     y = torch.empty((Bn, C, Ho, Wo), dtype=torch.float32, device=DEV)
-    n = int(L.fp8a_conv2d_workspace_size(Bn, C, H, W, C, kh, kw, stride, stride, pad, pad, 1, 1, C))
+    n = int(L.fp8a_conv2d_workspace_size(Bn, Cin, H, W, C, kh, kw, sh, sw, ph, pw, dh, dw, groups))
     ws = torch.zeros(n, dtype=torch.uint8, device=DEV)
     tA = torch.tensor([bA], dtype=torch.int32, device=DEV)
     tW = torch.as_tensor(np.asarray(bW, np.int32)).to(DEV)
     tR = torch.tensor([bR], dtype=torch.int32, device=DEV)
     tab = torch.as_tensor(np.ascontiguousarray(table, np.int32))
-    rc = L.fp8a_conv2d(_lib.dev_ptr(xt), _lib.dev_ptr(wt), _lib.dev_ptr(y), Bn, C, H, W, C, kh, kw, stride, stride,
-                       pad, pad, 1, 1, C, fmt[0], fmt[1], _lib.dev_ptr(tA), _lib.dev_ptr(tW), _lib.dev_ptr(tR),
+    rc = L.fp8a_conv2d(_lib.dev_ptr(xt), _lib.dev_ptr(wt), _lib.dev_ptr(y), Bn, Cin, H, W, C, kh, kw, sh, sw,
+                       ph, pw, dh, dw, groups, fmt[0], fmt[1], _lib.dev_ptr(tA), _lib.dev_ptr(tW), _lib.dev_ptr(tR),
                        _lib.host_ptr(tab), flags, _lib.dev_ptr(ws), ws.numel(), _lib.stream_ptr(DEV))
     _lib.check(rc, "fp8a_conv2d")
     torch.cuda.synchronize()

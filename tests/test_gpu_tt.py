@@ -87,21 +87,27 @@ def _matmul_raw(A, lda, B, sbk, sbn, Mr, N, K, E, M, bA, bB, bR, table, flags):
     return C.cpu().numpy(), int(ws[:4].view(torch.int32).item())
 
 
+def _hw(v):
+    """A geometry argument as its (h, w) pair: an int stands for both."""
+    return (int(v), int(v)) if np.ndim(v) == 0 else (int(v[0]), int(v[1]))
+
+
 def _conv_raw(x, w, E, M, bA, bW, bR, table, flags, stride, pad, dil, groups):
     from fp8_quantization_amd import _lib
     L = _lib.load()
     Bn, Cin, H, W = x.shape
     Cout, _, kh, kw = w.shape
-    Ho = (H + 2 * pad - dil * (kh - 1) - 1) // stride + 1
-    Wo = (W + 2 * pad - dil * (kw - 1) - 1) // stride + 1
+    (sh, sw), (ph, pw), (dh, dw) = _hw(stride), _hw(pad), _hw(dil)
+    Ho = (H + 2 * ph - dh * (kh - 1) - 1) // sh + 1
+    Wo = (W + 2 * pw - dw * (kw - 1) - 1) // sw + 1
     xt, wt = _dev(x), _dev(w)
     y = torch.empty((Bn, Cout, Ho, Wo), dtype=torch.float32, device=DEV)
-    need = int(L.fp8a_conv2d_workspace_size(Bn, Cin, H, W, Cout, kh, kw, stride, stride, pad, pad, dil, dil, groups))
+    need = int(L.fp8a_conv2d_workspace_size(Bn, Cin, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, groups))
     ws = torch.zeros(need, dtype=torch.uint8, device=DEV)
     tA, tW, tR = _dev([bA], torch.int32), _dev(bW, torch.int32), _dev([bR], torch.int32)
     tab = torch.as_tensor(np.ascontiguousarray(table, np.int32))
-    rc = L.fp8a_conv2d(_lib.dev_ptr(xt), _lib.dev_ptr(wt), _lib.dev_ptr(y), Bn, Cin, H, W, Cout, kh, kw, stride,
-                       stride, pad, pad, dil, dil, groups, E, M, _lib.dev_ptr(tA), _lib.dev_ptr(tW), _lib.dev_ptr(tR),
+    rc = L.fp8a_conv2d(_lib.dev_ptr(xt), _lib.dev_ptr(wt), _lib.dev_ptr(y), Bn, Cin, H, W, Cout, kh, kw, sh,
+                       sw, ph, pw, dh, dw, groups, E, M, _lib.dev_ptr(tA), _lib.dev_ptr(tW), _lib.dev_ptr(tR),
                        _lib.host_ptr(tab), flags, _lib.dev_ptr(ws), ws.numel(), _lib.stream_ptr(DEV))
     _lib.check(rc, "fp8a_conv2d")
     torch.cuda.synchronize()
