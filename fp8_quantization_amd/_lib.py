@@ -29,7 +29,8 @@ SYMBOLS = ("fp8a_version", "fp8a_last_error", "fp8a_fallback_stats", "fp8a_path_
            "fp8a_check_workspace_size", "fp8a_matmul_check", "fp8a_conv2d_check_workspace_size", "fp8a_conv2d_check",
            "fp8a_fp8_mse_workspace_size", "fp8a_fp8_mse_search", "fp8a_fq_selfcheck",
            "fp8a_bn_train_workspace_size", "fp8a_bn_train", "fp8a_bmm", "fp8a_bmm_stats",
-           "fp8a_bmm_check_workspace_size", "fp8a_bmm_check", "fp8a_grad_bmm", "fp8a_grad_stats")
+           "fp8a_bmm_check_workspace_size", "fp8a_bmm_check", "fp8a_grad_bmm", "fp8a_grad_stats",
+           "fp8a_fq_train_workspace_size", "fp8a_fq_train_forward", "fp8a_fq_train_backward")
 
 _lib = None
 
@@ -122,6 +123,9 @@ def load():
                             P, P, P, P, SZ, P], I),
         "fp8a_grad_bmm": ([P, P, P] + [I64] * 16 + [P], I),
         "fp8a_grad_stats": ([P, I], I),
+        "fp8a_fq_train_workspace_size": ([I64, I64], SZ),
+        "fp8a_fq_train_forward": ([P, I64, I64, P, I, I, I, P, P, P, P, P], I),
+        "fp8a_fq_train_backward": ([P, P, I64, I64, I, P, P, P, SZ, P], I),
     }
     for name, (args, res) in sig.items():
         f = getattr(L, name)

@@ -26,7 +26,7 @@ __all__ = ["custom_matmul_vectorize", "approx_matmul", "approx_bmm", "approx_mat
            "make_flags", "make_flags_v5", "fp8_fake_quantize", "bn_act_epilogue", "dense_format", "dense_matmul",
            "dense_conv2d", "grouped_conv2d", "dense_conv2d_fused", "approx_matmul_check", "approx_conv2d_check", "approx_bmm_check",
            "CheckStats", "format_self_check", "SELF_CHECK_LABELS", "fp8_mse_losses", "bn_train", "grad_bmm",
-           "ste_linear", "ste_bmm", "ste_conv2d"]
+           "ste_linear", "ste_bmm", "ste_conv2d", "fp8_fake_quantize_train", "fp8_fake_quantize_backward"]
 
 
 def make_flags(with_approx=True, with_s2nn2s_opt=False, quant_btw_mult_accu=True, golden_clip_OF=False,
@@ -1019,6 +1019,52 @@ def fp8_fake_quantize(x, maxval, n_bits, mantissa_bits, sign_bits=1, per_row=Fal
     return out, bias
 
 
+def fp8_fake_quantize_train(x, maxval, n_bits, mantissa_bits, sign_bits=1, per_row=False):
+    """fp8_fake_quantize for a forward that autograd records (fp8a_fq_train_forward, csrc/fq_train.h): returns
+    (values, float bias, code).  Values and bias are fp8_fake_quantize's bit for bit; code is one uint8 per
+    element, x's shape, carrying what fp8_fake_quantize_backward needs of x and maxval."""
+    L = _lib.load()
+    x = _as_f32(x).contiguous()
+    with torch.no_grad():  # (maxval may be a Parameter)
+        mx = _as_f32(maxval).reshape(-1).contiguous()
+        if mx.device != x.device:
+            mx = mx.to(x.device)
+    rows = mx.numel() if per_row else 1
+    out = torch.empty_like(x)
+    code = torch.empty(x.shape, dtype=torch.uint8, device=x.device)
+    bias = torch.empty(rows, dtype=torch.float32, device=x.device)
+    ibias = torch.empty(rows, dtype=torch.int32, device=x.device)
+    rc = L.fp8a_fq_train_forward(_lib.dev_ptr(x), rows, x.numel() // rows, _lib.dev_ptr(mx), int(n_bits),
+                                 int(mantissa_bits), int(sign_bits), _lib.dev_ptr(out), _lib.dev_ptr(code),
+                                 _lib.dev_ptr(bias), _lib.dev_ptr(ibias), _lib.stream_ptr(x.device))
+    _lib.check(rc, "fp8a_fq_train_forward")
+    if per_row and rows > 1:
+        bias = bias.view([-1] + [1] * (x.dim() - 1))
+    bias._fp8a_i32 = ibias
+    return out, bias, code
+
+
+def fp8_fake_quantize_backward(g, code, rows, sign_bits=1):
+    """The quantizer's backward in one pass over g and fp8_fake_quantize_train's code
+    (fp8a_fq_train_backward): returns (grad_x, grad_maxval) -- grad_x = g wx in g's shape, grad_maxval float32
+    [rows], the row's sum of g wm accumulated in double in a fixed order (two calls: identical bytes)."""
+    L = _lib.load()
+    g = _as_f32(g).contiguous()
+    if tuple(code.shape) != tuple(g.shape) or code.dtype != torch.uint8 or code.device != g.device:
+        raise AssertionError(f"fp8_fake_quantize_backward: code must be a uint8 {tuple(g.shape)} tensor on {g.device}")
+    code = code.contiguous()
+    rows = int(rows)
+    inner = g.numel() // max(rows, 1)
+    gx = torch.empty_like(g)
+    gmax = torch.empty(max(rows, 0), dtype=torch.float32, device=g.device)
+    nbytes = int(L.fp8a_fq_train_workspace_size(rows, inner))
+    ws = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=g.device)
+    rc = L.fp8a_fq_train_backward(_lib.dev_ptr(g), _lib.dev_ptr(code), rows, inner, int(sign_bits), _lib.dev_ptr(gx),
+                                  _lib.dev_ptr(gmax), _lib.dev_ptr(ws), nbytes, _lib.stream_ptr(g.device))
+    _lib.check(rc, "fp8a_fq_train_backward")
+    return gx, gmax
+
+
 def fp8_mse_losses(x, grid, mbit_list, n_bits, sign_bits, per_channel):
     """The FP8 MSE range search's losses in one pass over x (fp8a_fp8_mse_search, csrc/fq_mse.h):
 
@@ -1053,7 +1099,7 @@ def _res_quant_params(res_quantizer):
     mb = q.mantissa_bits
     mb = int(torch.clamp(torch.round(torch.as_tensor(mb, dtype=torch.float32)), 1, q.n_bits - q.sign_bits).item()) \
         if isinstance(mb, torch.Tensor) else int(mb)
-    return q.maxval, int(q.n_bits), mb, int(q.sign_bits)
+    return q.maxval.detach(), int(q.n_bits), mb, int(q.sign_bits)  # (a learned maxval: outside autograd)
 
 
 def qamaa_matmul(A, B, maxval, n_bits, mantissa_bits, sign_bits=1):

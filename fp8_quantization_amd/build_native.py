@@ -36,7 +36,7 @@ ARCH = os.environ.get("FP8A_OFFLOAD_ARCH", "gfx950")
 # (source, extra defines): one object per entry
 UNITS = [("fp8approx.hip", [])] + [("k_fast.hip", [f"-DFP8A_FAST_PART={p}"]) for p in range(4)] + \
         [("k_f8mx.hip", [f"-DFP8A_XF_PART={p}"]) for p in range(3)] + [("k_tt.hip", []), ("k_v5.hip", []), ("k_check.hip", []), ("k_mse.hip", []), ("k_bn.hip", [])] + \
-        [("k_bmm.hip", [f"-DFP8A_BMM_PART={p}"]) for p in range(4)] + [("k_grad.hip", [])]
+        [("k_bmm.hip", [f"-DFP8A_BMM_PART={p}"]) for p in range(4)] + [("k_grad.hip", []), ("k_fqt.hip", [])]
 
 
 def deps():

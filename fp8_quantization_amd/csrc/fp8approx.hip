@@ -30,6 +30,7 @@
 #include "conv_tbx.h"
 #include "gemm_check.h"
 #include "fq_mse.h"
+#include "fq_train.h"
 #include "bn_train.h"
 #include "gemm_bmm.h"
 #include "gemm_grad.h"
@@ -599,7 +600,7 @@ static void launch_f8mx(const GemmArgs &a, hipStream_t s) {
 enum OptKind { OPT_RAW, OPT_BOOL, OPT_AT_LEAST, OPT_CLAMP };
 enum OptId { OPT_XM_NCG, OPT_XM_SIGN_ROWS, OPT_XM_PIPE, OPT_XM_WAVE_ROWS, OPT_SPLITK_FIXUP, OPT_SPLITK, OPT_FQ_FAST,
              OPT_AF32_MAXCT, OPT_TT_BAND, OPT_TT16_MINK, OPT_TBX_RW, OPT_TBS, OPT_DW_LDS, OPT_DW_TARGET, OPT_DN_DIRECT,
-             OPT_V5DS, OPT_DW3, OPT_MSE_GROUP, OPT_N };
+             OPT_V5DS, OPT_DW3, OPT_MSE_GROUP, OPT_FQT_TARGET_WGS, OPT_N };
 struct Option {
     const char *name, *env;
     int def, kind, lo, hi;
@@ -625,6 +626,7 @@ static Option g_opts[OPT_N] = {
     {"v5ds", "FP8A_V5DS", 1, OPT_RAW},            // v5 depthwise 3x3 on conv_v5ds_kernel (0: conv_v5dw_kernel)
     {"dw3", "FP8A_DW3", 2, OPT_RAW},              // exact depthwise 3x3: dn_dw3g (2), dn_dw3 (1), dn_group_conv (0)
     {"mse_group", "FP8A_MSE_GROUP", 1, OPT_BOOL},  // fp8a_fp8_mse_search's grouped kernel (fq_mse.h)
+    {"fqt_target_wgs", "FP8A_FQT_TARGET_WGS", FQT_TARGET_WGS, OPT_CLAMP, 1, 1 << 20},  // fqt_parts' workgroups per launch (fq_train.h)
 };
 static int opt_norm(const Option &o, int v) {
     return o.kind == OPT_BOOL ? v != 0 : o.kind == OPT_AT_LEAST ? std::max(o.lo, v)
@@ -3075,6 +3077,58 @@ int fp8a_fp8_mse_search(const float *x, int64_t rows, int64_t inner, const float
     a.sse = sse;
     launch_mse(a, opt(OPT_MSE_GROUP) != 0, (hipStream_t)stream);
     return hip_check("fp8a_fp8_mse_search");
+}
+
+// The fake quantizer's training pair (fq_train.h).  Backward workspace: the workgroups' parts, doubles [rows][parts].
+static const char *fqt_shape_bad(int64_t rows, int64_t inner) {
+    if (rows <= 0) return "rows must be positive";
+    if (inner < 0) return "inner must not be negative";
+    if (rows > (int64_t)1 << 24 || inner > ((int64_t)1 << 62) / rows) return "shape too large";
+    return nullptr;
+}
+static int64_t fqt_parts_now(int64_t rows, int64_t inner) { return fqt_parts(rows, inner, opt(OPT_FQT_TARGET_WGS)); }
+
+size_t fp8a_fq_train_workspace_size(int64_t rows, int64_t inner) {
+    if (fqt_shape_bad(rows, inner)) return 0;
+    return (size_t)rows * (size_t)fqt_parts_now(rows, inner) * sizeof(double);
+}
+
+int fp8a_fq_train_forward(const float *x, int64_t rows, int64_t inner, const float *maxval, int n_bits, int Mbits,
+                          int sign_bits, float *y, uint8_t *code, float *bias_out, int32_t *ibias_out,
+                          fp8a_stream_t stream) {
+    if (const char *bad = fqt_shape_bad(rows, inner)) return fail(FP8A_EINVAL, bad);
+    const int E = n_bits - sign_bits - Mbits;
+    if (Mbits < 1 || E < 1 || sign_bits < 0 || sign_bits > 1) return fail(FP8A_EFORMAT, "bad FP8 quantizer format");
+    // (empty rows have no elements to point at: only the biases are written)
+    if (maxval == nullptr || (inner > 0 && (x == nullptr || y == nullptr || code == nullptr)))
+        return fail(FP8A_EINVAL, "null pointer");
+    FqtArgs a{};
+    a.rows = rows; a.inner = inner; a.parts = fqt_parts_now(rows, inner);
+    a.S = sign_bits; a.E = E; a.M = Mbits; a.fq_fast = opt(OPT_FQ_FAST);
+    a.x = x; a.maxval = maxval; a.y = y; a.code = code; a.bias_out = bias_out; a.ibias_out = ibias_out;
+    a.vec = (rows == 1 || inner % 4 == 0) && (((uintptr_t)x | (uintptr_t)y) & 15) == 0 && ((uintptr_t)code & 3) == 0;
+    launch_fqt_forward(a, (hipStream_t)stream);
+    return hip_check("fp8a_fq_train_forward");
+}
+
+int fp8a_fq_train_backward(const float *g, const uint8_t *code, int64_t rows, int64_t inner, int sign_bits,
+                           float *grad_x, float *grad_maxval, void *workspace, size_t workspace_bytes,
+                           fp8a_stream_t stream) {
+    if (const char *bad = fqt_shape_bad(rows, inner)) return fail(FP8A_EINVAL, bad);
+    if (sign_bits < 0 || sign_bits > 1) return fail(FP8A_EFORMAT, "bad FP8 quantizer format");
+    // (empty rows have no elements to point at: only the zero sums are written)
+    if (grad_maxval == nullptr || workspace == nullptr || (inner > 0 && (g == nullptr || code == nullptr || grad_x == nullptr)))
+        return fail(FP8A_EINVAL, "null pointer");
+    if (workspace_bytes < fp8a_fq_train_workspace_size(rows, inner)) return fail(FP8A_EINVAL, "workspace too small");
+    if (((uintptr_t)workspace & 7) != 0) return fail(FP8A_EINVAL, "misaligned workspace");
+    FqtArgs a{};
+    a.rows = rows; a.inner = inner; a.parts = inner == 0 ? 0 : fqt_parts_now(rows, inner);
+    a.S = sign_bits;
+    a.g = g; a.code = const_cast<uint8_t *>(code); a.gx = grad_x; a.gmax = grad_maxval;
+    a.part = static_cast<double *>(workspace);
+    a.vec = (rows == 1 || inner % 4 == 0) && (((uintptr_t)g | (uintptr_t)grad_x) & 15) == 0 && ((uintptr_t)code & 3) == 0;
+    launch_fqt_backward(a, (hipStream_t)stream);
+    return hip_check("fp8a_fq_train_backward");
 }
 
 // Training-mode batch norm (bn_train.h).  Workspace: the (S, Q) double pairs [C][parts].

@@ -57,4 +57,10 @@ void launch_mse(const MseArgs &a, bool group, hipStream_t s);
 struct BnArgs;
 void launch_bn_train(const BnArgs &a, hipStream_t s);
 
+// k_fqt.hip: the fake quantizer's training pair (fq_train.h) -- the forward (values, biases, code bytes),
+// and the backward (grad_x, the workgroups' parts of grad_maxval) with its ordered reduction.
+struct FqtArgs;
+void launch_fqt_forward(const FqtArgs &a, hipStream_t s);
+void launch_fqt_backward(const FqtArgs &a, hipStream_t s);
+
 }  // namespace fp8a

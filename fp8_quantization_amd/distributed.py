@@ -122,7 +122,7 @@ def broadcast_quant_state(model, src=0):
     off = 0
     for q, h in zip(qs, hdr.tolist()):
         n, sb, nd = h[0], h[1], h[2]
-        q.maxval = flat[off:off + n].clone().view(h[3:3 + nd])
+        q._assign_maxval(flat[off:off + n].clone().view(h[3:3 + nd]))  # (a learned maxval: written in place)
         q.sign_bits = sb
         if rank != src and h[15] != q._mbits_int:
             q.mantissa_bits = torch.tensor(float(h[15]), device=q.mantissa_bits.device)

@@ -3,7 +3,8 @@ forward and whose backward is the straight-through estimator (custom_approx_para
 quantizer masks, the exact product's gradients on the gradient GEMM fp8a_grad_bmm).
 
     python -m fp8_quantization_amd.finetune --synthetic 64 --arch resnet18|mobilenet_v2|vit_b16 \
-        --steps 10 --lr 1e-3 [--batch-size 64] [--momentum 0.9] [--approx-attention]
+        --steps 10 --lr 1e-3 [--batch-size 64] [--momentum 0.9] [--approx-attention] \
+        [--learn-ranges [--range-lr 1e-4]] [--seed 0]
 
 A driver, not a trainer (no schedule, checkpoints or augmentation): it calibrates and fixes the FP8 ranges as
 the validation driver does (imagenet.py: estimate_ranges over --num-est-batches batches, fix_ranges), keeps the
@@ -12,6 +13,12 @@ parameter.  One JSON line per step: the loss, the step's milliseconds with their
 inside the backward, the gradient GEMMs and the convolutions' im2col + fold plumbing (HIP events), and the
 64 x 64 tiles the gradient GEMM recomputed in fp32 -- 0 as long as every saved operand is on its FP8 grid; a
 step that recomputed any makes the exit status 1.
+--learn-ranges: the FP8 ranges train too (FPQuantizer.learn_maxval): the model is built with
+learn_maxval, learn_ranges() follows the calibration, the maxvals form their own parameter group with
+--range-lr (default: --lr), and fix_ranges() follows the last step.  Each record also carries the number
+of learned ranges, the quantizers' recorded forward + backward milliseconds and the largest relative change
+of any maxval since calibration (without the flag: 0 ranges, the milliseconds, 0.0).  The driver does not
+clamp a range: a maxval that is not finite or not positive after a step ends the run with exit status 1.
 Data: --synthetic N random images and labels, or <images-dir>/train as imagenet.py reads it.
 """
 import argparse
@@ -44,6 +51,10 @@ def parse(argv=None):
     ap.add_argument("--with-comp", action="store_true")
     ap.add_argument("--approx-attention", action="store_true",
                     help="ViT only: QK^T and PV of every attention through the approx multiplier")
+    ap.add_argument("--seed", type=int, default=None, help="seed of the model's initialization and the data order")
+    ap.add_argument("--learn-ranges", action="store_true",
+                    help="train every FP8 quantizer's maxval as well (its own parameter group)")
+    ap.add_argument("--range-lr", type=float, default=None, help="learning rate of the maxvals (default: --lr)")
     ap.add_argument("--output", default=None, help="also write the step records (a JSON list) here")
     return ap.parse_args(argv)
 
@@ -53,6 +64,8 @@ def approx_cfg(args):
                withComp=args.with_comp, ste_backward=True)
     if args.approx_attention:
         cfg["approx_attention"] = True
+    if args.learn_ranges:
+        cfg["learn_maxval"] = True
     return cfg
 
 
@@ -72,8 +85,18 @@ def finetune(model, data, args, dev):
                 break
     calibrate_on_rank0(model, cal())
     model.eval()  # BN on its running statistics, dropout off: only the products, quantizers and affines train
-    params = [p for p in model.parameters() if p.requires_grad]
-    opt = torch.optim.SGD(params, lr=args.lr, momentum=args.momentum)
+    ranges, cal0 = [], None
+    if args.learn_ranges:
+        from .distributed import quantizers
+        model.learn_ranges()
+        ranges = list({id(q.maxval): q.maxval for q in quantizers(model)
+                       if isinstance(q.maxval, torch.nn.Parameter)}.values())
+        cal0 = torch.cat([p.detach().reshape(-1) for p in ranges]).clone()
+    rid = {id(p) for p in ranges}
+    groups = [dict(params=[p for p in model.parameters() if p.requires_grad and id(p) not in rid])]
+    if ranges:
+        groups.append(dict(params=ranges, lr=args.lr if args.range_lr is None else args.range_lr))
+    opt = torch.optim.SGD(groups, lr=args.lr, momentum=args.momentum)
     records, step = [], 0
     _lib.grad_stats(reset=True)
     while step < args.steps:
@@ -99,9 +122,21 @@ def finetune(model, data, args, dev):
                        grad_gemm_ms=_events_ms(prof.get("grad_gemm", ())),
                        im2col_fold_ms=_events_ms(prof.get("im2col", ())) + _events_ms(prof.get("fold", ())),
                        grad_gemm_launches=st["launches"], recomputed_tiles=st["recomputed"])
+            rec.update(learned_ranges=len(ranges), max_range_change=0.0, bad_ranges=0,
+                       quantizer_ms=_events_ms(prof.get("fq_forward", ())) + _events_ms(prof.get("fq_backward", ())))
+            if ranges:
+                now = torch.cat([p.detach().reshape(-1) for p in ranges])
+                rec.update(max_range_change=float(((now - cal0).abs() / cal0.abs()).max()),
+                           bad_ranges=int((~(torch.isfinite(now) & (now > 0))).sum()))
             print(json.dumps(rec), flush=True)
             records.append(rec)
             step += 1
+            if rec.get("bad_ranges"):
+                print(f"step {rec['step']}: {rec['bad_ranges']} learned maxval(s) not finite or not positive "
+                      "(lower --range-lr)", file=sys.stderr)
+                return records
+    if ranges:
+        model.fix_ranges()
     return records
 
 
@@ -113,6 +148,8 @@ def main(argv=None):
         raise SystemExit("give --synthetic N or --images-dir")
     dev = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")))
     torch.cuda.set_device(dev)
+    if args.seed is not None:
+        torch.manual_seed(args.seed)
     if args.synthetic:
         data = SyntheticImages(args.synthetic, args.image_size)
     else:
@@ -122,7 +159,7 @@ def main(argv=None):
     if args.output:
         with open(args.output, "w") as f:
             json.dump(records, f, indent=1)
-    return 1 if any(r["recomputed_tiles"] for r in records) else 0
+    return 1 if any(r["recomputed_tiles"] or r.get("bad_ranges") for r in records) else 0
 
 
 if __name__ == "__main__":

@@ -27,7 +27,8 @@ from torch.nn.modules.pooling import _AdaptiveAvgPoolNd, _AvgPoolNd
 from . import chain
 from .approx_calculation import QCustomBNConv2dTorch, QCustomConv2dTorch, QCustomLinearTorch
 from .quantization.base_quantized_classes import (QuantizedActivation, QuantizedModule, _set_layer_approx_calculation,
-                                                  _set_layer_estimate_ranges, _set_layer_fix_ranges, sync_ste)
+                                                  _set_layer_estimate_ranges, _set_layer_fix_ranges,
+                                                  _set_layer_learn_ranges, sync_ste)
 from .quantization.hijacker import QuantizationHijacker, activations_set
 from .quantization.quantization_manager import QuantizationManager
 
@@ -90,6 +91,10 @@ class QuantizedModel(nn.Module):
 
     def fix_ranges(self):
         self.apply(_set_layer_fix_ranges)
+
+    def learn_ranges(self):
+        """Every initialized quantizer's range becomes a trainable Parameter (base_quantized_model.py:132)."""
+        self.apply(_set_layer_learn_ranges)
 
     def approx_calculation(self):
         self.apply(_set_layer_approx_calculation)

@@ -21,6 +21,12 @@ def _set_layer_fix_ranges(layer):
         layer.fix_ranges_flag = True
 
 
+def _set_layer_learn_ranges(layer):
+    # (base_quantized_classes.py:17-20: managers whose quantizer is initialized; fix_ranges_flag stays)
+    if isinstance(layer, QuantizationManager) and layer.quantizer.is_initialized:
+        layer.learn_ranges()
+
+
 def _set_layer_estimate_ranges(layer):
     if isinstance(layer, QuantizationManager):
         layer.estimate_ranges()
@@ -135,6 +141,9 @@ class QuantizedModule(nn.Module):
     def estimate_ranges(self):
         self.apply(_set_layer_estimate_ranges)
         self.fix_ranges_flag = False
+
+    def learn_ranges(self):
+        self.apply(_set_layer_learn_ranges)
 
     def approx_calculation(self):
         self.approx_flag = True

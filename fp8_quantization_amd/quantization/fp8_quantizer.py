@@ -10,7 +10,7 @@ width forward hands to the kernels follows the assignment.
 import torch
 from torch import nn
 
-from ..approx_ops import fp8_fake_quantize
+from ..approx_ops import _ste_timed, fp8_fake_quantize, fp8_fake_quantize_backward, fp8_fake_quantize_train
 
 
 def quantize_to_fp8_ste_MM(x_float, n_bits, maxval, num_mantissa_bits, sign_bits):
@@ -22,36 +22,46 @@ def quantize_to_fp8_ste_MM(x_float, n_bits, maxval, num_mantissa_bits, sign_bits
     return fp8_fake_quantize(x_float, maxval, n_bits, M, sign_bits=sign_bits, per_row=per_row)
 
 
-class _FakeQuantSTE(torch.autograd.Function):
-    """The quantizer's forward kernel, unchanged, with the reference's backward: quantize_to_fp8_ste_MM
-    (fp8_quantizer.py:97-173) is differentiable torch whose gradient with respect to x at fixed maxval is that
-    of the clamp min(max(x, minval), maxval) -- the rounding is straight-through and its power-of-two scales
-    are detached, so (g s) / s = g exactly.  The gradient passes inside the clamp, is zero outside, and -- as
-    ATen's maximum / minimum split a tie -- half at x == minval or x == maxval.  Saved: one byte per element."""
+class _FakeQuantTrain(torch.autograd.Function):
+    """The quantizer's recorded forward with the reference's backward, one kernel pass each way
+    (fp8a_fq_train_forward / fp8a_fq_train_backward, csrc/fq_train.h).  quantize_to_fp8_ste_MM
+    (fp8_quantizer.py:97-173) is differentiable torch: its bias is rounded, its power-of-two scales are detached
+    and its rounding is straight-through, so (g s) / s = g exactly and what remains is the gradient of the clamp
+    min(max(x, minval), maxval), minval = -maxval or the constant 0.  With respect to x it passes inside the
+    clamp, is zero outside, and -- as ATen's maximum / minimum split a tie -- half at x == minval or
+    x == maxval.  With respect to maxval it is the sum of g over the elements the upper bound clamps minus the
+    sum over those the signed lower bound clamps, a tie counting half.  Saved: one code byte per element."""
 
     @staticmethod
-    def forward(ctx, x, q):
-        res, q.custom_bias = quantize_to_fp8_ste_MM(x, q.n_bits, q.maxval, q._mbits_int, q.sign_bits)
-        mx = q.maxval
-        if mx.numel() != 1 and mx.dim() != x.dim():
-            mx = mx.view([-1] + [1] * (x.dim() - 1))
-        lo = -mx if q.sign_bits == 1 else torch.zeros_like(mx)
-        # twice the clamp's derivative: 2 inside, 1 on a bound, 0 outside (NaN: 0)
-        ctx.save_for_backward(((x > lo) & (x < mx)).to(torch.uint8) + ((x >= lo) & (x <= mx)).to(torch.uint8))
+    def forward(ctx, x, maxval, q):
+        rows = maxval.numel()
+        with _ste_timed("fq_forward"):
+            res, q.custom_bias, code = fp8_fake_quantize_train(x, maxval, q.n_bits, q._mbits_int,
+                                                               sign_bits=q.sign_bits, per_row=rows != 1)
+        ctx.save_for_backward(code)
+        ctx.fq = (rows, q.sign_bits, maxval.shape)
         return res
 
     @staticmethod
     def backward(ctx, g):
-        (twice,) = ctx.saved_tensors
-        return g * (twice.to(g.dtype) * 0.5), None
+        (code,) = ctx.saved_tensors
+        rows, sign_bits, shape = ctx.fq
+        with _ste_timed("fq_backward"):
+            gx, gm = fp8_fake_quantize_backward(g, code, rows, sign_bits)
+        return (gx if ctx.needs_input_grad[0] else None, gm.view(shape) if ctx.needs_input_grad[1] else None, None)
 
 
 class FPQuantizer(nn.Module):
-    """8-bit floating-point quantizer with a learnable-free custom exponent bias.
+    """8-bit floating-point quantizer with a custom exponent bias set by ``maxval``.
 
     ``ste_backward`` (default off; set by the owning layer from custom_approx_params['ste_backward']): a
-    forward that autograd records goes through _FakeQuantSTE, the same kernel with the reference's gradient
-    with respect to x.  The ranges stay fixed: make_range_trainable keeps raising."""
+    forward that autograd records goes through _FakeQuantTrain, the quantize kernel's values with the
+    reference's gradient with respect to x and -- for a learned range -- maxval.
+
+    Learned ranges: built with ``learn_maxval=True``, make_range_trainable() (QuantizationManager.learn_ranges)
+    turns ``maxval`` into an nn.Parameter; fix_ranges() turns it back into a plain tensor with the same data.
+    While it is a Parameter every range update writes it in place.  Learned mantissa widths stay out: an approx
+    layer's error table belongs to one format and the kernels take an integer width."""
     ste_backward = False
 
     def __init__(self, n_bits=8, per_channel=False, scale_domain=None, mantissa_bits=4, maxval=3,
@@ -98,13 +108,31 @@ class FPQuantizer(nn.Module):
         # default maxval, so fix_ranges never raises for it (QuantizationManager.fix_ranges)
         return True
 
+    def _assign_maxval(self, value):
+        """maxval <- value.  A Parameter keeps its identity (an optimizer holds it; torch refuses a plain
+        tensor under its name): it is written in place, under no_grad."""
+        if isinstance(self.maxval, nn.Parameter):
+            with torch.no_grad():
+                value = value.detach().to(dtype=self.maxval.dtype)
+                if value.device != self.maxval.device or value.shape != self.maxval.shape:
+                    self.maxval.data = value.clone()
+                else:
+                    self.maxval.copy_(value)
+        else:
+            self.maxval = value
+
     def forward(self, x_float):
         if self.maxval.device != x_float.device:
-            self.maxval = self.maxval.to(x_float.device)
-        if self.ste_backward and torch.is_grad_enabled() and x_float.requires_grad:
-            return _FakeQuantSTE.apply(x_float, self)
-        res, self.custom_bias = quantize_to_fp8_ste_MM(x_float, self.n_bits, self.maxval, self._mbits_int,
-                                                       self.sign_bits)
+            self._assign_maxval(self.maxval.to(x_float.device))
+        mx = self.maxval
+        if torch.is_grad_enabled():
+            if mx.requires_grad and not self.ste_backward:
+                raise RuntimeError("FPQuantizer: maxval is learned but custom_approx_params['ste_backward'] is off: "
+                                   "this forward would train nothing (switch ste_backward on, or run under no_grad)")
+            if self.ste_backward and (x_float.requires_grad or mx.requires_grad):
+                return _FakeQuantTrain.apply(x_float, mx, self)
+        res, self.custom_bias = quantize_to_fp8_ste_MM(x_float, self.n_bits, mx.detach() if mx.requires_grad else mx,
+                                                       self._mbits_int, self.sign_bits)
         return res
 
     def set_quant_range(self, x_min, x_max):
@@ -115,13 +143,29 @@ class FPQuantizer(nn.Module):
                 x_max = torch.tensor([float(x_max)], device=self.maxval.device)
                 x_min = torch.tensor([float(x_min)], device=self.maxval.device)
             mx = torch.abs(torch.max(torch.abs(x_min), x_max))
-            self.maxval = mx.reshape(1) if mx.dim() == 0 else mx
+            self._assign_maxval(mx.reshape(1) if mx.dim() == 0 else mx)
 
     def fix_ranges(self):
-        pass
+        """A learned maxval becomes a plain tensor again, same data (the reference calls a parameter_to_fixed
+        that it never defines)."""
+        if isinstance(self.maxval, nn.Parameter):
+            data = self.maxval.detach()
+            del self.maxval
+            self.maxval = data
+
+    def learn_maxval(self):
+        self.learning_maxval = True
+        if not isinstance(self.maxval, nn.Parameter):
+            self.maxval = nn.Parameter(self.maxval.detach())
 
     def make_range_trainable(self):
-        raise NotImplementedError("learned FP8 ranges are outside the approx hot path")
+        if self.learning_mantissa_bits:
+            raise NotImplementedError("learned mantissa widths are out of scope: an approx layer's error table "
+                                      "belongs to one format and the kernels take an integer width")
+        if not self.learning_maxval:
+            # (the reference is a silent no-op here; training nothing is the failure to avoid)
+            raise NotImplementedError("this FPQuantizer was not built with learn_maxval=True: nothing to learn")
+        self.learn_maxval()
 
     def reset(self):
         pass

@@ -60,6 +60,7 @@ class QuantizationManager(nn.Module):
     def fix_ranges(self):
         if not self.quantizer.is_initialized:  # quantization_manager.py:93-98
             raise QuantizerNotInitializedError()
+        self.quantizer.fix_ranges()  # (a learned range becomes a plain tensor again)
         self._set_state(Qstates.fix_ranges)
 
     def estimate_ranges_train(self):

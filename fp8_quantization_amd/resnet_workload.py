@@ -25,7 +25,7 @@ def approx_qparams(expo_width=4, mant_width=3, dnsmp_factor=3, withComp=False, w
                    zero_table_ext=None, approx_version=9, sim_hw_add_OFUF=False, with_OF_opt=False,
                    with_UF_opt=False, weight_range_method="current_minmax", weight_range_options=None,
                    act_range_method="allminmax", act_range_options=None, mse_include_mantissa_bits=False,
-                   error_table=None, ste_backward=False):
+                   error_table=None, ste_backward=False, learn_maxval=False):
     """qparams exactly as the reference scripts build them (utils/click_options.py:544-606,
     scripts/generated_scripts.py): per-channel current_minmax weights, allminmax activations,
     quantize_input, FP8 quantizer with set_maxval, approx + res_quantizer run method.
@@ -36,7 +36,9 @@ def approx_qparams(expo_width=4, mant_width=3, dnsmp_factor=3, withComp=False, w
     user's own multiplier as anything error_tables.load_error_table accepts -- it replaces the built-in
     table selection (withComp / dnsmp_factor / zero_table_ext) for the v9 model, for any format;
     ste_backward (opt-in, custom_approx_params["ste_backward"]): forwards that autograd records run unfused
-    with a straight-through backward on the gradient GEMM, nothing else changes.
+    with a straight-through backward on the gradient GEMM (INTEGRATION.md), nothing else changes;
+    learn_maxval (the reference's --fp8-learn-maxval): every FP8 quantizer is built so that learn_ranges()
+    turns its maxval into a Parameter (needs ste_backward for its gradient).
 
     weight_range_method / act_range_method: a RangeEstimators name (current_minmax, allminmax,
     running_minmax, MSE: the reference's --weight-quant-method / --act-quant-method) or an estimator
@@ -51,7 +53,7 @@ def approx_qparams(expo_width=4, mant_width=3, dnsmp_factor=3, withComp=False, w
         weight_range_method=estimator(weight_range_method), weight_range_options=dict(weight_range_options or {}),
         act_range_method=estimator(act_range_method), act_range_options=dict(act_range_options or {}),
         quantize_input=True,
-        fp8_kwargs=dict(maxval=None, mantissa_bits=mant_width, set_maxval=True, learn_maxval=False,
+        fp8_kwargs=dict(maxval=None, mantissa_bits=mant_width, set_maxval=True, learn_maxval=bool(learn_maxval),
                         learn_mantissa_bits=False, mse_include_mantissa_bits=bool(mse_include_mantissa_bits),
                         allow_unsigned=False),
         custom_approx_params=dict(expo_width=expo_width, mant_width=mant_width, dnsmp_factor=dnsmp_factor,

@@ -148,6 +148,9 @@ int fp8a_kernel_time(double *out, int reset);
  * "xm_wave_rows" (default 1; FP8A_XM_WAVE_ROWS) -- with "xm_pipe", the 128 x 64 instances of gemm_f8mx_kernel
  * map the math loop's waves by rows (a wave 32 rows x all 64 columns: one table address per row block and
  * K-step instead of one per wave; 0: waves by columns).
+ * "fqt_target_wgs" (default 2048; FP8A_FQT_TARGET_WGS) -- the workgroups a launch of the fake quantizer's
+ * training kernels aims for when rows are split (csrc/fq_train.h fqt_parts; 1 .. 2^20).  It changes the
+ * summation split of fp8a_fq_train_backward, so grad_maxval may differ in its last bit between two values of it.
  * All of these change the schedule only: the outputs are bit-identical.  Returns the previous value, or FP8A_EINVAL
  * for an unknown name.  Not synchronised with launches in flight on other threads.
  */
@@ -684,6 +687,37 @@ size_t fp8a_fp8_mse_workspace_size(int64_t rows, int64_t inner, int n_cand, int 
 int fp8a_fp8_mse_search(const float *x, int64_t rows, int64_t inner, const float *grid, int n_cand,
                         const int32_t *mbits, int n_mbits, int n_bits, int sign_bits, double *sse,
                         void *workspace, size_t workspace_bytes, fp8a_stream_t stream);
+
+/*
+ * The FP8 fake quantizer's training pair (csrc/fq_train.h): a quantizer whose maxval may be learned
+ * (FPQuantizer.learn_maxval).  x viewed as [rows][inner], maxval device float [rows] (rows = 1: per tensor).
+ *
+ * fp8a_fq_train_forward -- one pass over x: y and the biases (bias_out float [rows], ibias_out int32 [rows],
+ * either may be NULL) are fp8a_fp8_quantize's bit for bit; code gets one byte per element for the backward:
+ * bits 0-1 twice the clamp's derivative (2 inside (lo, maxval), 1 on a bound, 0 outside or NaN), bits 2-3 the
+ * bound the element is on or beyond (0 none, 1 upper, 2 the lower bound -maxval of a signed quantizer).
+ *
+ * fp8a_fq_train_backward -- one pass over g and code (of a forward with the same rows, inner, sign_bits):
+ *   grad_x[i] = g[i] wx[i]                          wx = 1, 1/2, 0 (a multiplication: inf * 0 = NaN)
+ *   grad_maxval[r] = sum over row r of g[i] wm[i]   wm = +1 / +1/2 above / on maxval, -1 / -1/2 below / on
+ *                                                   -maxval (signed), else 0
+ * each term one fp32 multiply, summed in double in a fixed order and rounded to fp32 once:
+ * |grad_maxval - exact| <= (2^-24 + inner 2^-53) sum |g wm|; no floating-point atomics; the split of a row
+ * over workgroups depends on the shape and option "fqt_target_wgs" alone: two calls return identical bytes.
+ * inner == 0: success, only the biases / grad_maxval = 0 are written (the element pointers may be NULL).
+ * Workspace: fp8a_fq_train_workspace_size bytes (host-only; 0 for bad arguments; it follows
+ * "fqt_target_wgs"), 8-byte aligned.
+ *
+ * Every check runs before any HIP call: FP8A_EINVAL for a null pointer, rows <= 0, inner < 0, a workspace
+ * that is too small or misaligned; FP8A_EFORMAT for E < 1, Mbits < 1 or sign_bits outside {0, 1}.
+ */
+size_t fp8a_fq_train_workspace_size(int64_t rows, int64_t inner);
+int fp8a_fq_train_forward(const float *x, int64_t rows, int64_t inner, const float *maxval, int n_bits,
+                          int Mbits, int sign_bits, float *y, uint8_t *code, float *bias_out,
+                          int32_t *ibias_out, fp8a_stream_t stream);
+int fp8a_fq_train_backward(const float *g, const uint8_t *code, int64_t rows, int64_t inner,
+                           int sign_bits, float *grad_x, float *grad_maxval, void *workspace,
+                           size_t workspace_bytes, fp8a_stream_t stream);
 
 /*
  * Training-mode batch norm on deterministic kernels (csrc/bn_train.h): x viewed as [N][C][inner]
