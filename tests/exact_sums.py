@@ -331,7 +331,8 @@ def _conv(fam, E, M, table, flags, cfg, **kw):
           f"d{geo_tag(cfg['d'])}g{cfg['g']}hw{geo_tag(cfg['hw'])}"
     if "name" in cfg:                                   # (the geometry cases go by their names)
         geo = cfg["name"]
-    key = f"conv-{fam}-E{E}M{M}-{table}-f{flags}-{geo}" + ("-posA" if kw.get("posA") else "")
+    key = f"conv-{fam}-E{E}M{M}-{table}-f{flags}-{geo}" + ("-posA" if kw.get("posA") else "") + \
+        ("-offgrid" if kw.get("offgrid") else "")
     cid = key + (f"-{tag}" if tag else "")
     return dict(kind="conv", id=cid, pkey=key, fam=fam, E=E, M=M, table=table, flags=flags, cfg=cfg, **kw)
 
@@ -672,9 +673,20 @@ def _tbdw_problem(c):
     return dict(x=x, w=w, bA=bA, bB=bW, bR=bR, table=tab, parts=parts, flags=tfl)
 
 
+CONV_OFFGRID_SPOT = (1, 3, 4, 7)   # (image, channel, row, column) of the off-grid input value
+
+
+def conv_offgrid_cases():
+    """h9w16 on gemm_f8mx with one off-grid input value: the producer whose gated exact kernel stores (and, chained,
+    emits) the recomputed units (store_cases).  The oracle's terms quantize each product, so the budget holds as for
+    the clean twin; tests/test_exact_sums_cpu.py proves it like every case's."""
+    cfg = next(g for g in GEO_CONVS if g["name"] == "h9w16")
+    return [_conv("f8mx", 4, 3, "nocomp", FL, cfg, offgrid=True), _conv("f8mx", 5, 2, "zero", FL, cfg, offgrid=True)]
+
+
 def all_cases():
     return matmul_cases() + splitk_cases() + schedule_cases() + band_cases() + conv_cases() + bmm_cases() + \
-        dense_cases() + [QAMAA] + tbdw_cases() + geo_conv_cases() + geo_tbdw_cases() + [QAMAA_CONV]
+        dense_cases() + [QAMAA] + tbdw_cases() + geo_conv_cases() + geo_tbdw_cases() + [QAMAA_CONV] + conv_offgrid_cases()
 
 
 def geo_cases():
@@ -878,6 +890,8 @@ def _conv_problem(c):
     w = draw(rng, E, M, (cout, cig, kh, kw), bW.reshape(sh), b_lo.reshape(sh), b_hi.reshape(sh), zf)
     if c.get("posA"):
         x = np.abs(x)
+    if c.get("offgrid"):  # one value off the grid: the approx kernel marks its units, the exact kernel recomputes them
+        x[CONV_OFFGRID_SPOT] = off_grid_value(bA, (a_lo, a_hi))
     return dict(x=x, w=w, bA=bA, bB=bW, bR=bR)
 
 
@@ -983,3 +997,321 @@ def case_K(c):
 
 CASES = {c["id"]: c for c in all_cases()}
 assert len(CASES) == len(all_cases()), "case ids are not unique"
+
+
+# ------------------------------------------------------------------------------------------ store cases
+# The fused store on top of the cases above (tests/store_ref.py, tests/test_gpu_store_exact.py): the launch's
+# accumulator is the proved exact sum of its base case, and the store parameters -- BN scale / shift, activation
+# clamp, residual, output quantizer, the next convolution's quantizer and word image -- are drawn here, on the CPU,
+# so that the values the store meets cover the classes its quantizers and clamps distinguish:
+#   tie_dn / tie_up   exactly on a rounding tie of the first quantizer the value meets, the lower neighbour even / odd
+#   max_p / max_n     exactly +maxval / -maxval;  over_p / over_n: one float32 step beyond
+#   sub               in the quantizer's subnormal band;  tiny_p / tiny_n: below half its smallest step (rounds to zero)
+#   lo / hi           the BN output exactly on the activation clamp's bounds
+#   plo / phi         the value after the residual exactly on the post clamp's bounds
+# Planting: a residual is free per element -- res = target - v where float32(v + res) is the target (checked; an
+# element where it is not keeps its random residual); without a residual whole channels are planted: a power-of-two
+# scale so small that float32(acc * scale + target) is the target for every accumulator of the channel (scale 0 for
+# the target 0).  The other channels take random float32 scale and shift of both signs, normalised by the channel's
+# own accumulator spread so that the activation clamps a share of the values at each bound.
+# tests/test_store_ref_cpu.py proves the conditions on every case from the CPU model alone.
+STORE_ACTS = {"none": (0, 0.0, 0.0), "relu6": (1, 0.0, 6.0), "hardtanh": (1, -0.5, 0.75)}
+_ACT_DRAW = {"none": (1.0, 0.0), "relu6": (2.5, 3.0), "hardtanh": (0.5, 0.125)}   # spread and centre of the BN output
+STORE_TAILS = ("res", "res_clamp_q", "relu_uq", "bias_res_q")     # (and res_q: residual + signed quantizer, no clamp)
+CONV_TAILS = ("res", "res_clamp_q", "relu_uq", "res_q")
+# activation quantizers (maxval, n_bits, mantissa bits, sign bits): the block's output quantizer, signed / unsigned
+OUT_Q = {1: (3.0, 8, 3, 1), 0: (6.0, 8, 3, 0)}
+# The post clamps lie strictly inside the quantizers' ranges, so that the clamp itself decides values: without it
+# the quantizer's own clamp to maxval would give another result (tests/test_store_ref_cpu.py asserts that dropping
+# the clamp changes the output).  +-maxval and the step beyond are then out of reach behind a clamp: res_q,
+# bias_res_q and the emitting cases hold those classes.
+POST_CLAMP = (-1.0, 1.25)                                 # res_clamp_q's clamp, inside OUT_Q[1]'s maxval 3
+RELU_CLAMP = (0.0, 1.25)                                  # relu_uq's: a clipped ReLU, inside OUT_Q[0]'s maxval 6
+RES_SD = 1.0                                              # spread of the random residual: both bounds are met
+Q_LITERAL = (float(2.0 ** 70), 8, 3, 1)                   # maxval outside fq_fast_ok: the literal form under fq_fast = 1
+Q_INVALID = (float(2.0 ** -70), 8, None, 1)               # next quantizer whose grid lies below the window 2^-62
+NEXT_BR = {3: 8, 2: 10}                                   # the consumer's result bias per word format (chain_cases)
+NEXT_MX = 5.5
+CLASSES_Q = ("tie_dn", "tie_up", "max_p", "max_n", "over_p", "over_n", "sub", "tiny_p", "tiny_n")
+CLASSES_CLAMP = ("plo", "phi")
+
+
+def _st(base, tag, entry, bn="rand", act="none", tail=None, emit=None, opts=None, fq=None, site=None):
+    """One store case.  entry: conv (approx_conv2d on the base case's x / w) or mat (approx_matmul_block on its A /
+    B); bn: rand (random BN + planted channels) or None; tail: one of STORE_TAILS; emit: dict(form, S, pad) or None;
+    fq: the output quantizer when it is not OUT_Q's; every tail case runs with fq_fast 0 and 1."""
+    return dict(kind="store", id=f"st-{base}-{tag}", base=base, entry=entry, bn=bn, act=act, tail=tail, emit=emit,
+                opts=opts or {}, fq=fq, site=site or CASES[base]["fam"])
+
+
+def _geo_case(cases, name, E, M, fam, opts=None):
+    return next(c["id"] for c in cases if (c.get("cfg") or c.get("geo") or {}).get("name") == name and
+                (c["E"], c["M"]) == (E, M) and c["fam"] == fam and (c.get("opts") or {}) == (opts or {}))
+
+
+def store_cases():
+    """See the site table in tests/test_gpu_store_exact.py's docstring."""
+    conv, tb = geo_conv_cases(), geo_tbdw_cases()
+    out = []
+    # -- the implicit-GEMM stores, NCHW: h9w16 (Ho Wo = 144: the 16-byte store; 288 rows and 24 channels: row and column
+    # tails), k1-padded (90: the scalar store), k1-s2x1 (90, gemm_f8mx's fp32-staged A), k2x4-s2x3 (30, K = 64)
+    fams = [("f8mx", 4, 3), ("f8mx", 5, 2), ("tt", 2, 5), ("fast", 4, 3), ("v5mx", 5, 2), ("v5fast", 4, 3)]
+    for name in ("h9w16", "k1-padded"):
+        for fam, E, M in fams + [("tt16" if name == "h9w16" else "tt", 3, 4)]:
+            base = _geo_case(conv, name, E, M, fam)
+            out += [_st(base, f"bn-{a}", "conv", act=a) for a in ("none", "relu6", "hardtanh")]
+            out += [_st(base, t, "conv", act="none" if t != "res_clamp_q" else "hardtanh", tail=t) for t in CONV_TAILS]
+    for name, fam, E, M in (("k1-s2x1", "f8mx", 4, 3), ("k1-s2x1", "f8mx", 5, 2), ("k2x4-s2x3", "tt16", 3, 4)):
+        base = _geo_case(conv, name, E, M, fam)
+        out += [_st(base, "bn-relu6", "conv", act="relu6"), _st(base, "res_clamp_q", "conv", tail="res_clamp_q")]
+    # gemm_f8mx's tile shapes and wave orders (store_tile_xm per xm_ncg, xm_wave_rows)
+    base = _geo_case(conv, "h9w16", 4, 3, "f8mx")
+    for o in ({"xm_ncg": 1}, {"xm_ncg": 2}, {"xm_ncg": 4, "xm_wave_rows": 0}, {"xm_ncg": 4, "xm_wave_rows": 1}):
+        out += [_st(base, f"bn-hardtanh-{_opt_tag(o)}", "conv", act="hardtanh", opts=o),
+                _st(base, f"res_clamp_q-{_opt_tag(o)}", "conv", act="hardtanh", tail="res_clamp_q", opts=o)]
+    out.append(_st(base, "res_q-literal", "conv", tail="res_q", fq=Q_LITERAL))
+    # -- row-major stores (approx_matmul_block; ldc = N): 129 columns (ldc % 4 != 0, row and column tails), the
+    # off-grid twins (the gated exact kernel's store of the recomputed units), split-K (N = ldc = 64: the vector
+    # forms of the reduction and of the in-launch sum)
+    big = MAT_SHAPES[-1]
+    # (fp8a_matmul_block takes the int-bias v9 families only: the v5 stores run through the convolutions above)
+    for fam, E, M in (("f8mx", 4, 3), ("f8mx", 5, 2), ("tt", 2, 5), ("tt16", 3, 4), ("fast", 4, 3)):
+        for off in (False, True):
+            cands = [c for c in matmul_cases() if c["fam"] == fam and (c["E"], c["M"]) == (E, M) and c["shape"] == big and
+                     bool(c.get("offgrid")) == off and c["table"] != ("zero" if E == 4 else "comp3") and
+                     (fam != "fast" or c["flags"] == FL_FAST)]
+            base = cands[0]["id"]
+            site = ("exact+" if off else "") + fam
+            out.append(_st(base, "bn", "mat", site=site))
+            out += [_st(base, t, "mat", bn="bias" if t == "bias_res_q" else "rand", tail=t, site=site)
+                    for t in (STORE_TAILS if not off else ("res_clamp_q",))]
+    sk_site = lambda fam, o: "splitk-" + fam + ("-fixup" if o["splitk_fixup"] else "")  # noqa: E731
+    for c in splitk_cases():
+        o = c["opts"]
+        out.append(_st(c["id"], "bn", "mat", opts=o, site=sk_site(c["fam"], o)))
+        out += [_st(c["id"], t, "mat", bn="bias" if t == "bias_res_q" else "rand", tail=t, opts=o,
+                    site=sk_site(c["fam"], o)) for t in STORE_TAILS]
+        if c["fam"] == "f8mx" and o == {"splitk": 2, "splitk_fixup": 1}:   # the in-launch sum on the narrow tile shapes
+            for ncg in (1, 2):
+                o2 = dict(o, xm_ncg=ncg)
+                out += [_st(c["id"], f"bn-xm_ncg{ncg}", "mat", opts=o2, site=sk_site("f8mx", o)),
+                        _st(c["id"], f"res_clamp_q-xm_ncg{ncg}", "mat", tail="res_clamp_q", opts=o2, site=sk_site("f8mx", o))]
+    # split-K forced on cases that are not the split-K shape (an exact sum does not depend on its order): the scalar
+    # forms of the reduction and of the in-launch sum on ldc = 129 and on the NCHW plane of 30 pixels (k2x4-s2x3,
+    # K = 64), their NCHW vector forms on the plane of 144
+    for S, fix in ((2, 0), (3, 0), (2, 1)):
+        o = {"splitk": S, "splitk_fixup": fix}
+        base = next(c["id"] for c in matmul_cases() if c["fam"] == "f8mx" and (c["E"], c["table"]) == (4, "nocomp") and
+                    c["shape"] == big and not c.get("offgrid"))
+        out += [_st(base, f"bn-{_opt_tag(o)}", "mat", opts=o, site=sk_site("f8mx", o)),
+                _st(base, f"res_clamp_q-{_opt_tag(o)}", "mat", tail="res_clamp_q", opts=o, site=sk_site("f8mx", o))]
+        for name in ("h9w16", "k2x4-s2x3"):   # (k1-padded has K = 16, one K chunk: it cannot split)
+            for fam, E, M in (("f8mx", 4, 3), ("tt", 2, 5)) if fix == 0 else (("f8mx", 4, 3),):
+                base = _geo_case(conv, name, E, M, fam)
+                out += [_st(base, f"bn-relu6-{_opt_tag(o)}", "conv", act="relu6", opts=o, site=sk_site(fam, o)),
+                        _st(base, f"res_clamp_q-{_opt_tag(o)}", "conv", act="hardtanh", tail="res_clamp_q", opts=o,
+                            site=sk_site(fam, o))]
+    # -- the depthwise stores: 3 x 3 planes of width 4 (hw 7, stride 2), 9 and 14, every option set of tbdw_cases
+    for c in tbdw_cases():
+        if (c["hw"], c["stride"]) in ((7, 2), (9, 1), (14, 1)):
+            out += [_st(c["id"], f"bn-{a}", "conv", act=a, opts=c["opts"]) for a in ("none", "relu6")]
+    # -- emission: gemm_f8mx's store and the staged depthwise producer, word forms 0 and 1, E4M3 and E5M2 words, the
+    # next quantizer signed and unsigned, next padding (0, 0), (1, 1), (0, 3), Wo = 16 and Wo = 10
+    for (E, M) in ((4, 3), (5, 2)):
+        for name in ("h9w16", "k1-padded"):
+            base = _geo_case(conv, name, E, M, "f8mx")
+            for S in (1, 0):
+                for pad in ((0, 0), (1, 1), (0, 3)):
+                    out.append(_st(base, f"emit0-s{S}-p{pad[0]}x{pad[1]}", "conv", act="relu6" if S == 0 else "none",
+                                   emit=dict(form=0, S=S, pad=pad)))
+                out.append(_st(base, f"emit1-s{S}", "conv", act="relu6" if S == 0 else "none", emit=dict(form=1, S=S, pad=(0, 1))))
+            out.append(_st(base, "emit0-tail", "conv", act="hardtanh", tail="res_clamp_q", emit=dict(form=0, S=1, pad=(1, 1))))
+            if E == 4:   # the split-K reduction and the in-launch sum emit instead of the store
+                sbase = base if name == "h9w16" else _geo_case(conv, "k2x4-s2x3", E, M, "f8mx")   # (Wo = 16 / Wo = 5)
+                for fix in (0, 1):
+                    o = {"splitk": 2, "splitk_fixup": fix}
+                    out += [_st(sbase, f"emit0-s1-p1x1-{_opt_tag(o)}", "conv", emit=dict(form=0, S=1, pad=(1, 1)), opts=o,
+                                site=sk_site("f8mx", o)),
+                            _st(sbase, f"emit1-s0-{_opt_tag(o)}", "conv", act="relu6", emit=dict(form=1, S=0, pad=(0, 1)),
+                                opts=o, site=sk_site("f8mx", o))]
+            out.append(_st(base, "emit0-invalid", "conv", emit=dict(form=0, S=1, pad=(1, 1), q=Q_INVALID)))
+        # the gated exact kernel: an off-grid input value in the producer; the recomputed units are stored and emitted
+        off = next(c["id"] for c in conv_offgrid_cases() if (c["E"], c["M"]) == (E, M))
+        out += [_st(off, "bn-relu6", "conv", act="relu6", site="exact+f8mx"),
+                _st(off, "res_clamp_q", "conv", act="hardtanh", tail="res_clamp_q", site="exact+f8mx"),
+                _st(off, "emit0-s1-p1x1", "conv", emit=dict(form=0, S=1, pad=(1, 1)), site="exact+f8mx"),
+                _st(off, "emit0-s0-p0x3", "conv", act="relu6", emit=dict(form=0, S=0, pad=(0, 3)), site="exact+f8mx"),
+                _st(off, "emit1-s1", "conv", emit=dict(form=1, S=1, pad=(0, 1)), site="exact+f8mx")]
+        # the staged depthwise producer: Wo = 14 (dw-p0x1) and Wo = 20 (dw-p1x5)
+        for name in ("dw-p0x1", "dw-p1x5"):
+            dw = _geo_case(tb, name, E, M, "tbx", {"tbs": 2, "tbx_rw": 2})
+            out += [_st(dw, f"emit0-s{S}-p{pad[0]}x{pad[1]}", "conv", act="relu6" if S == 0 else "none",
+                        emit=dict(form=0, S=S, pad=pad), opts={"tbs": 2, "tbx_rw": 2}, site="tbx-emit")
+                    for S, pad in ((1, (0, 0)), (0, (0, 0)), (1, (1, 1)), (0, (0, 3)))]
+    return out
+
+
+def store_acc(c):
+    """The base case's exact accumulator as the launch lays it out: [Mr, N] (mat) or NCHW (conv)."""
+    b = CASES[c["base"]]
+    p = problem_of(b["pkey"])
+    rows = None
+    for (_, _, T, sl) in p["parts"]:
+        e = expected(T)
+        if rows is None:
+            ncol = e.shape[1] if sl == slice(None) else (b.get("cfg") or tbdw_geo(b))["cout"]
+            rows = np.zeros((e.shape[0], ncol), np.float32)
+        rows[:, sl] = e
+    if c["entry"] == "mat":
+        return p, rows
+    g = b.get("cfg") or tbdw_geo(b)
+    Ho, Wo = conv_out_hw(dict(g, hw=pair(g["hw"]), k=pair(g["k"])))
+    return p, np.ascontiguousarray(rows.reshape(g["B"], Ho, Wo, rows.shape[1]).transpose(0, 3, 1, 2))
+
+
+def _q_targets(fq):
+    """One value per class of CLASSES_Q for the quantizer fq (its ties in the binade [0.25, 0.5), inside every
+    activation clamp used here)."""
+    from tests import store_ref as sr
+    mx, nb, M, S = fq
+    bias = sr.fq_bias(mx, nb, M, S)
+    step = 2.0 ** (1 - bias - M)
+    f = np.float32
+    t = dict(tie_dn=0.25 * (2 ** M + 2.5) / 2 ** M, tie_up=0.25 * (2 ** M + 1.5) / 2 ** M, max_p=mx, max_n=-mx,
+             over_p=np.nextafter(f(mx), f(np.inf)), over_n=np.nextafter(f(-mx), f(-np.inf)), sub=3 * step,
+             tiny_p=0.25 * step, tiny_n=-0.25 * step)     # (powers of two: a residual reaches them exactly)
+    return {k: f(v) for k, v in t.items()}
+
+
+def store_classes(xin, fq):
+    """How many elements of xin (the values entering the quantizer fq, before its clamp) fall in each class."""
+    from tests import store_ref as sr
+    mx, nb, M, S = fq
+    bias = sr.fq_bias(mx, nb, M, S)
+    x = np.asarray(xin, np.float32)
+    xc = np.minimum(np.maximum(x, np.float32(-mx if S else 0.0)), np.float32(mx)).astype(np.float64)
+    _, e = np.frexp(xc)
+    k = (np.where(xc == 0, 1.0, np.maximum(e - 1 + bias, 1.0)) - M - bias).astype(np.int32)
+    t = np.abs(np.ldexp(xc, -k))
+    tie = (t - np.floor(t)) == 0.5
+    half = 2.0 ** (-bias - M)
+    f = np.float32
+    return dict(tie_dn=int((tie & (np.floor(t) % 2 == 0)).sum()), tie_up=int((tie & (np.floor(t) % 2 == 1)).sum()),
+                max_p=int((x == f(mx)).sum()), max_n=int((x == f(-mx)).sum()),
+                over_p=int((x == np.nextafter(f(mx), f(np.inf))).sum()),
+                over_n=int((x == np.nextafter(f(-mx), f(-np.inf))).sum()),
+                sub=int(((np.abs(xc) >= half) & (np.abs(xc) < 2.0 ** (1 - bias))).sum()),
+                tiny_p=int(((x > 0) & (x < half)).sum()), tiny_n=int(((x < 0) & (x > -half)).sum()))
+
+
+def clamp_classes(xin, lo, hi):
+    """Values entering the post clamp exactly on its bounds, and the shares it cuts at each."""
+    x = np.asarray(xin, np.float32)
+    return dict(plo=int((x == np.float32(lo)).sum()), phi=int((x == np.float32(hi)).sum()),
+                below=float(np.mean(x < np.float32(lo))), above=float(np.mean(x > np.float32(hi))))
+
+
+@functools.lru_cache(maxsize=4)
+def store_problem(cid):
+    """Everything a store case's launch takes and everything the CPU model says it writes: dict with the base
+    problem `p`, acc, ss (scale_shift [C, 2] or None), act (act, lo, hi), res, post (post_act, lo, hi, quantizer or
+    None), nextq / bR_next / Mw / form / pad (emission), bn_out (after BN + activation), y (final), obias, neg_zero
+    (where y's zero has a defined sign), xin / q_first (the values entering the first quantizer, and it), and for an
+    emitting case words / ok / header / img (store_ref.image)."""
+    import zlib
+    from tests import store_ref as sr
+    c = STORE_CASES[cid]
+    b = CASES[c["base"]]
+    p, acc = store_acc(c)
+    rng = np.random.default_rng([SEED + 31, zlib.crc32(cid.encode())])
+    C = acc.shape[1]
+    act, alo, ahi = STORE_ACTS[c["act"]]
+    tail, em = c["tail"], c["emit"]
+    post_q = None
+    if tail in ("res_clamp_q", "bias_res_q", "res_q"):
+        post_q = c["fq"] or OUT_Q[1]
+    elif tail == "relu_uq":
+        post_q = OUT_Q[0]
+    Mw = b["M"]
+    nextq = None
+    if em:
+        nextq = em.get("q") or (NEXT_MX, 8, Mw, em["S"])
+        nextq = (nextq[0], nextq[1], Mw, nextq[3])
+    q_first = post_q or nextq
+    has_res = tail in ("res", "res_clamp_q", "bias_res_q", "res_q")
+    post = (0, 0.0, 0.0)
+    if tail == "res_clamp_q":
+        post = (1,) + POST_CLAMP
+    elif tail == "relu_uq":
+        post = (1,) + RELU_CLAMP
+    # what lies between the BN output and the first quantizer: the clamps a planted value must pass
+    # (a residual comes after the activation: then the post clamp alone bounds what reaches the quantizer)
+    lo = max(alo if act and not has_res else -np.inf, post[1] if post[0] else -np.inf)
+    hi = min(ahi if act and not has_res else np.inf, post[2] if post[0] else np.inf)
+    qt = {k: v for k, v in _q_targets(q_first).items() if lo <= float(v) <= hi} if q_first and q_first[0] < 2.0 ** 64 \
+        and q_first[0] > 2.0 ** -62 else {}
+    if post[0]:
+        qt.update(plo=np.float32(post[1]), phi=np.float32(post[2]))
+    # ---- BN
+    ss = None
+    chan_targets = {}
+    if c["bn"] == "bias":
+        ss = np.stack([np.ones(C, np.float32), rng.normal(0, 0.5, C).astype(np.float32)], axis=1)
+    elif c["bn"] == "rand":
+        a = np.moveaxis(acc, 1, 0).reshape(C, -1).astype(np.float64)
+        spread = np.sqrt((a ** 2).mean(axis=1))
+        spread[spread == 0] = 1.0
+        sd, mid = _ACT_DRAW[c["act"]]
+        sign = rng.choice([-1.0, 1.0], C)
+        sign[:2] = (1.0, -1.0)
+        ss = np.stack([(sign * rng.uniform(0.7, 1.3, C) * sd / spread).astype(np.float32),
+                       (mid + rng.normal(0, 0.3 * sd, C)).astype(np.float32)], axis=1)
+        # planted channels: the quantizer's classes first, then the clamp's bounds; at even indices (two planted
+        # channels are never neighbours: max_p and over_p end in the same value) and never the last channel; at most
+        # half of the channels, a third where there are fewer than 16
+        plant = ([] if has_res else list(qt.items())) + ([("lo", np.float32(alo)), ("hi", np.float32(ahi))] if act else [])
+        plant = plant[:C // 2 if C >= 16 else C // 3]
+        chans = rng.permutation(np.arange(0, C - 1, 2))[:len(plant)]
+        plant = plant[:len(chans)]
+        for ch, (name, t) in zip(chans, plant):
+            amax = float(np.abs(a[ch]).max()) or 1.0
+            j = max(-120, int(np.floor(np.log2(abs(float(t)) * 2.0 ** -30 / amax)))) if t != 0 else None
+            ss[ch] = (np.float32(0.0) if j is None else np.float32(2.0 ** j), t)
+            chan_targets[int(ch)] = name
+    bn_raw = sr.bn_act(acc, ss, 0, 0.0, 0.0, 1) if ss is not None else acc
+    bn_out = sr.bn_act(acc, ss, act, alo, ahi, 1) if ss is not None else acc
+    # ---- residual
+    res = None
+    if has_res:
+        # (Q_LITERAL's grid has the step 2^52: its residual alone reaches it, far above the BN output)
+        res = (rng.normal(0, RES_SD, acc.shape) * (2.0 ** 58 if post_q and post_q[0] > 2.0 ** 64 else 1.0)).astype(np.float32)
+        if qt:  # per class a share of the elements: res = target - v, or its float32 neighbour, where v + res is the target
+            flat = rng.permutation(acc.size)[:acc.size // 3]
+            rr, vv = res.reshape(-1), bn_out.reshape(-1)
+            for i, (name, t) in enumerate(qt.items()):
+                idx = flat[i::len(qt)][:200]
+                v = vv[idx]
+                r0 = (np.float64(t) - v.astype(np.float64)).astype(np.float32)
+                for r in (r0, np.nextafter(r0, np.float32(np.inf)), np.nextafter(r0, np.float32(-np.inf))):
+                    hit = ((v + r).astype(np.float32) == t) & (rr[idx] != r)
+                    hit &= ~np.isin(idx, idx[(v + rr[idx]).astype(np.float32) == t])
+                    rr[idx[hit]] = r[hit]
+    y, obias = sr.tail(bn_out, res, post[0], post[1], post[2], post_q)
+    xpre = (bn_out + res).astype(np.float32) if has_res else bn_out       # what enters the post clamp
+    xin = y if not post_q else sr.tail(bn_out, res, post[0], post[1], post[2], None)[0]   # ... the first quantizer
+    neg_zero = sr.signed_zero(xin, *post_q) if post_q else None
+    out = dict(case=c, base=b, p=p, acc=acc, ss=ss, act=(act, alo, ahi), res=res, post=post + (post_q,), nextq=nextq,
+               bn_raw=bn_raw, bn_out=bn_out, y=y, obias=obias, neg_zero=neg_zero, xin=xin, xpre=xpre, q_first=q_first,
+               chan_targets=chan_targets,
+               required=[k for k in CLASSES_Q + CLASSES_CLAMP if k in qt and (has_res or k in chan_targets.values())],
+               q_clamp=(post[1], post[2]) if post[0] else None)
+    if em:
+        out.update(bR_next=NEXT_BR[Mw], Mw=Mw, form=em["form"], pad=em["pad"])
+        w, ok, header = sr.words(y, nextq, NEXT_BR[Mw], Mw, em["form"])
+        ipad = (0, 0) if em["form"] == 1 else em["pad"]
+        out.update(words=w, ok=ok, header=header, img=sr.image(acc.shape[0], C, acc.shape[2], acc.shape[3], *ipad))
+    return out
+
+
+STORE_CASES = {c["id"]: c for c in store_cases()}
+assert len(STORE_CASES) == len(store_cases()), "store case ids are not unique"
