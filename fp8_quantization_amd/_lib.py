@@ -30,6 +30,7 @@ SYMBOLS = ("fp8a_version", "fp8a_last_error", "fp8a_fallback_stats", "fp8a_path_
            "fp8a_fp8_mse_workspace_size", "fp8a_fp8_mse_search", "fp8a_fq_selfcheck",
            "fp8a_bn_train_workspace_size", "fp8a_bn_train", "fp8a_bmm", "fp8a_bmm_stats",
            "fp8a_bmm_check_workspace_size", "fp8a_bmm_check", "fp8a_grad_bmm", "fp8a_grad_stats",
+           "fp8a_grad_bmm_split_workspace_size", "fp8a_grad_bmm_split",
            "fp8a_fq_train_workspace_size", "fp8a_fq_train_forward", "fp8a_fq_train_backward")
 
 _lib = None
@@ -123,6 +124,8 @@ def load():
                             P, P, P, P, SZ, P], I),
         "fp8a_grad_bmm": ([P, P, P] + [I64] * 16 + [P], I),
         "fp8a_grad_stats": ([P, I], I),
+        "fp8a_grad_bmm_split_workspace_size": ([I64] * 6 + [P, P], I),
+        "fp8a_grad_bmm_split": ([P, P, P] + [I64] * 17 + [P, I64, P], I),
         "fp8a_fq_train_workspace_size": ([I64, I64], SZ),
         "fp8a_fq_train_forward": ([P, I64, I64, P, I, I, I, P, P, P, P, P], I),
         "fp8a_fq_train_backward": ([P, P, I64, I64, I, P, P, P, SZ, P], I),
@@ -276,9 +279,20 @@ def bmm_stats(reset=False):
     return dict(launches=int(out[0]), tiles=int(out[1]), recomputed=int(out[2]))
 
 
+def grad_split_plan(nb, M, N, K0, K1, splits):
+    """fp8a_grad_bmm_split_workspace_size: (S, bytes) -- the effective part count of a split along K and the
+    workspace fp8a_grad_bmm_split needs for it (0 when S == 1).  No device call."""
+    L = load()
+    S, nbytes = ctypes.c_int64(0), ctypes.c_int64(0)
+    check(L.fp8a_grad_bmm_split_workspace_size(nb, M, N, K0, K1, splits, ctypes.byref(S), ctypes.byref(nbytes)),
+          "fp8a_grad_bmm_split_workspace_size")
+    return int(S.value), int(nbytes.value)
+
+
 def grad_stats(reset=False):
-    """fp8a_grad_stats: dict(launches, tiles, recomputed) -- fp8a_grad_bmm launches and their 64 x 64 output
-    tiles (host-side counters) and the tiles recomputed in fp32 (synchronises the device)."""
+    """fp8a_grad_stats: dict(launches, tiles, recomputed) -- fp8a_grad_bmm / fp8a_grad_bmm_split calls and their
+    product-pass workgroups, one per (64 x 64 output tile, part of a split) (host-side counters), and the
+    workgroups recomputed in fp32 (synchronises the device)."""
     L = load()
     out = (ctypes.c_uint64 * 3)()
     check(L.fp8a_grad_stats(ctypes.cast(out, ctypes.c_void_p), 1 if reset else 0), "fp8a_grad_stats")

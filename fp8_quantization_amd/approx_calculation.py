@@ -32,7 +32,7 @@ from .approx_ops import (_bias_dev, _res_quant_params, approx_bmm, approx_bmm_ch
 from .error_tables import get_comp_table_NN_v5, get_error_table_NN, load_error_table
 from .quantization.hijacker import QuantizationHijacker
 from .quantization.quantization_manager import QuantizationManager
-from .quantization.base_quantized_classes import QuantizedActivation, QuantizedModule, sync_ste
+from .quantization.base_quantized_classes import QuantizedActivation, QuantizedModule, grad_split_k, sync_ste
 from .quantization.hijacker import activations_set
 from .quantization.quantized_folded_bn import BNFusedHijacker
 from .chain import ChainConsumerMixin
@@ -246,7 +246,8 @@ class ApproxConv2dMixin(ApproxOpMixin, ChainConsumerMixin):
                 if self._ste_on():  # the same launch, recorded with the straight-through backward
                     out = ste_conv2d(x, weight, lambda xq, wq: approx_conv2d(xq, wq, E, M, a_b, w_bias, r_b, table,
                                                                              **args),
-                                     self.stride, self.padding, self.dilation, self.groups)
+                                     self.stride, self.padding, self.dilation, self.groups,
+                                     split_k=grad_split_k(self))
                 else:
                     out = approx_conv2d(x.detach(), weight.detach(), E, M, a_b, w_bias, r_b, table, **args)
                 if self._self_check_on():
@@ -371,7 +372,8 @@ class ApproxLinearMixin(ApproxOpMixin):
                 raise AssertionError("fused input quantization / tail without the fused linear launch")
             biases = (self.get_acts_fp_bias(), self.get_weights_fp_bias(), self.get_res_fp_bias())
             if self._ste_on() and self.approx_flag:  # the same launch, recorded with the straight-through backward
-                out = ste_linear(x, weight, lambda xq, wq: self.approx_multiply(xq, wq.t(), *biases))
+                out = ste_linear(x, weight, lambda xq, wq: self.approx_multiply(xq, wq.t(), *biases),
+                                 split_k=grad_split_k(self))
             else:
                 out = self.approx_multiply(x.detach(), weight.detach().t(), *biases)
             if bias is not None:
@@ -434,7 +436,8 @@ class ApproxMatMulMixin(ApproxOpMixin):
                       self._default_bias(self.res_quantizer.get_fp_bias(), E, dev))
             if self._ste_on():  # the same launch, recorded with the straight-through backward; out is
                 # filled by the (differentiable) copy below
-                res = ste_bmm(a, b, lambda aq, bq: approx_bmm(aq, bq, E, M, *biases, table, flags=flags))
+                res = ste_bmm(a, b, lambda aq, bq: approx_bmm(aq, bq, E, M, *biases, table, flags=flags),
+                              split_k=grad_split_k(self))
             else:
                 res = approx_bmm(a.detach(), b.detach(), E, M, *biases, table, flags=flags, out=out)
             if self._self_check_on():

@@ -25,7 +25,7 @@ __all__ = ["custom_matmul_vectorize", "approx_matmul", "approx_bmm", "approx_mat
            "quant_to_fp_any_vectorize_torch", "float_to_fpany_absint_torch", "get_error_table_NN",
            "make_flags", "make_flags_v5", "fp8_fake_quantize", "bn_act_epilogue", "dense_format", "dense_matmul",
            "dense_conv2d", "grouped_conv2d", "dense_conv2d_fused", "approx_matmul_check", "approx_conv2d_check", "approx_bmm_check",
-           "CheckStats", "format_self_check", "SELF_CHECK_LABELS", "fp8_mse_losses", "bn_train", "grad_bmm",
+           "CheckStats", "format_self_check", "SELF_CHECK_LABELS", "fp8_mse_losses", "bn_train", "grad_bmm", "grad_split_auto",
            "ste_linear", "ste_bmm", "ste_conv2d", "fp8_fake_quantize_train", "fp8_fake_quantize_backward"]
 
 
@@ -1427,18 +1427,82 @@ def _grad_batch(t, nd, what):
     raise AssertionError(f"grad_bmm: {what} has more than two leading batch dims: {tuple(t.shape)}")
 
 
-def _grad_launch(A, B, C, nb, M, N, K0, K1, oa, ob, oc, sa, sb, sc):
-    """One fp8a_grad_bmm launch; oa / ob / oc: element offsets of the first batch item, sa / sb / sc the
+# grad_split_auto's rule: split until the product pass has GRAD_SPLIT_BLOCKS_PER_CU workgroups
+# per compute unit, never below GRAD_SPLIT_MIN_STAGES 32-k stages per part, never above GRAD_SPLIT_MAX_BYTES of
+# workspace.  From profiles/grad_split/sweep.jsonl and sweep_fine.jsonl (tools/grad_bench.py --split-k
+# 1,2,4,...,64,auto and 1,48,56,64,128,256,512,auto on one MI355X, 256 CUs; ms at split 1 -> the best fixed split):
+#   ResNet-18 layer2.conv2 dW    36 tiles, 1568 stages   3.485 -> 0.361 at 64 (48 .. 64 level; 16: 0.393, 128: 0.384)
+#   ResNet-18 conv1 dW            3 tiles, 25088 stages  60.97 -> 0.397 at 256 (64: 0.976, 128: 0.519, 512: 0.478)
+#   ResNet-18 layer4.1.conv2 dW 576 tiles, 98 stages     0.367 -> 0.303 at 4 (8, 16 within 2 %; 32: 0.344)
+#   ViT fc1 dW                  576 tiles, 394 stages    1.034 -> 0.586 at 16 (8: 0.587, 4: 0.618, 32: 0.619)
+#   the six data-gradient and attention products (2364 .. 14976 workgroups unsplit): no split gains more than 3 %
+#   (fc1 dX at 2), attention loses 1.5x .. 2.9x.
+# The guide's 1/2 - 1 workgroups per CU is too low for this kernel (several of its workgroups fit a CU): the dW
+# shapes keep gaining up to 7 - 18 per CU.  8 per CU (2048) is the largest power of two below the smallest product
+# that must stay unsplit (fc1 dX, 2364); the minimum of 8 stages keeps a part's walk longer than its prologue and, by
+# itself, leaves attention's K = 197 and 64 alone; the rule's workspace is its target times 16 KB, 32 MiB, so the
+# byte cap binds only where a caller's own split_k meets it.  What auto then does (spread.jsonl; run-to-run spread
+# 0.2 - 0.7 %): layer2.conv2 57 parts, 0.367 (1.5 % above the best fixed); layer4.1.conv2 4, 0.306 (the best); fc1 dW
+# 4, 0.623 (6 % above: 8 would need a target above fc1 dX's blocks); conv1 683, 0.499 (26 % above 256 parts: with 3
+# tiles the reduce pass is 48 workgroups walking 683 partials each -- a cap on the parts, or a wider reduce, is what
+# that shape still needs); 1 on the other six.
+GRAD_SPLIT_BLOCKS_PER_CU = 8
+GRAD_SPLIT_MIN_STAGES = 8
+GRAD_SPLIT_MAX_BYTES = 64 << 20
+
+
+def check_split_k(split_k, what="split_k"):
+    """split_k as grad_bmm takes it: an int >= 1 or "auto"; anything else is a ValueError naming `what`."""
+    if split_k == "auto" or (isinstance(split_k, int) and not isinstance(split_k, bool) and split_k >= 1):
+        return split_k
+    raise ValueError(f"{what} must be an int >= 1 or \"auto\", got {split_k!r}")
+
+
+def _split_kw(split_k):
+    """grad_bmm's keywords for a backward's split_k: none at 1.  Not the same as passing split_k=1: the default
+    backward then calls grad_bmm(A, B, out=, k2=) as it always has, so a stand-in for grad_bmm with those two
+    keywords (tests/test_gpu_ste.py replaces it with a float64 twin) keeps working."""
+    return {} if split_k == 1 else {"split_k": split_k}
+
+
+def grad_split_auto(nb, M, N, K, device):
+    """The number of splits along K that grad_bmm(..., split_k="auto") asks for on a product of nb items of
+    [M x K] @ [K x N]: 1 when its nb * tiles workgroups already reach GRAD_SPLIT_BLOCKS_PER_CU per compute unit of
+    `device`; else as many as reach it, with at least GRAD_SPLIT_MIN_STAGES stages per part and at most
+    GRAD_SPLIT_MAX_BYTES of workspace."""
+    blocks = nb * (-(-M // 64)) * (-(-N // 64))
+    target = GRAD_SPLIT_BLOCKS_PER_CU * torch.cuda.get_device_properties(device).multi_processor_count
+    if blocks <= 0 or blocks >= target:
+        return 1
+    nst = -(-K // 32)
+    s = min(-(-target // blocks), nst // GRAD_SPLIT_MIN_STAGES, GRAD_SPLIT_MAX_BYTES // (blocks * 64 * 64 * 4))
+    return max(1, s)
+
+
+def _grad_launch(A, B, C, nb, M, N, K0, K1, oa, ob, oc, sa, sb, sc, split_k=1):
+    """One fp8a_grad_bmm launch (split_k != 1: one fp8a_grad_bmm_split, with its workspace from the caching
+    allocator on the current stream); oa / ob / oc: element offsets of the first batch item, sa / sb / sc the
     operands' (batch, ...) element strides."""
     L = _lib.load()
     ptr = lambda t, o: ctypes.c_void_p(t.data_ptr() + 4 * o)  # noqa: E731
+    if split_k == "auto":
+        split_k = grad_split_auto(nb, M, N, K0 * K1, A.device)
+    if split_k == 1:
+        with _ste_timed("grad_gemm"):
+            rc = L.fp8a_grad_bmm(ptr(A, oa), ptr(B, ob), ptr(C, oc), nb, M, N, K0, K1, *sa, *sb, *sc,
+                                 _lib.stream_ptr(A.device))
+        _lib.check(rc, "fp8a_grad_bmm")
+        return
+    _, nbytes = _lib.grad_split_plan(nb, M, N, K0, K1, split_k)
+    # (a K too short to split plans one part and no workspace: the entry then takes none and launches unsplit)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=A.device) if nbytes else None
     with _ste_timed("grad_gemm"):
-        rc = L.fp8a_grad_bmm(ptr(A, oa), ptr(B, ob), ptr(C, oc), nb, M, N, K0, K1, *sa, *sb, *sc,
-                             _lib.stream_ptr(A.device))
-    _lib.check(rc, "fp8a_grad_bmm")
+        rc = L.fp8a_grad_bmm_split(ptr(A, oa), ptr(B, ob), ptr(C, oc), nb, M, N, K0, K1, *sa, *sb, *sc, split_k,
+                                   _lib.dev_ptr(ws) if nbytes else None, nbytes, _lib.stream_ptr(A.device))
+    _lib.check(rc, "fp8a_grad_bmm_split")
 
 
-def grad_bmm(A, B, out=None, k2=False):
+def grad_bmm(A, B, out=None, k2=False, split_k=1):
     """The gradient GEMM (fp8a_grad_bmm, csrc/gemm_grad.h): C[..., m, n] = sum_k A[..., m, k] B[..., k, n] as an
     exact fp32 product on the bf16 matrix core -- A any float32 (a gradient), B a bf16-exact operand (a saved
     FP8-quantized forward operand; anything else is still summed correctly, on the kernel's fp32 path).
@@ -1448,7 +1512,13 @@ def grad_bmm(A, B, out=None, k2=False):
     reduces over (image, pixel) this way).  Views are read in place whatever their strides (expand() gives a
     broadcast operand its zero stride); out: None, or the float32 view of [..., M, N] that receives C (any
     positive strides: a transposed view is written through its strides), not overlapping A or B.  Two batch
-    dims that do not collapse into one stride in every operand run one launch per index of the shorter one."""
+    dims that do not collapse into one stride in every operand run one launch per index of the shorter one.
+
+    split_k: 1 (one launch, no split), an int >= 2 or "auto" (grad_split_auto): the reduction split into that many
+    parts along K (fewer when K has fewer 32-k stages), each summed by its own workgroups into a workspace and
+    the parts added in index order by a second launch (fp8a_grad_bmm_split) -- deterministic, and exact wherever
+    the unsplit product is; every launch of the call gets the same split_k."""
+    check_split_k(split_k)
     nk = 2 if k2 else 1
     if A.dim() < 1 + nk or B.dim() != A.dim() or A.shape[:-1 - nk] != B.shape[:-1 - nk] or \
             A.shape[-nk:] != B.shape[-1 - nk:-1]:
@@ -1474,13 +1544,15 @@ def grad_bmm(A, B, out=None, k2=False):
         # one batch stride per operand
         one = lambda s0, s1: s0 if n1 == 1 else s1  # noqa: E731
         _grad_launch(A, B, out, n0 * n1, M, N, K0, K1, 0, 0, 0, (one(a0, a1), *sa), (one(b0, b1), *sb),
-                     (one(c0, c1), *sc))
+                     (one(c0, c1), *sc), split_k)
     elif n0 <= n1:
         for i in range(n0):
-            _grad_launch(A, B, out, n1, M, N, K0, K1, i * a0, i * b0, i * c0, (a1, *sa), (b1, *sb), (c1, *sc))
+            _grad_launch(A, B, out, n1, M, N, K0, K1, i * a0, i * b0, i * c0, (a1, *sa), (b1, *sb), (c1, *sc),
+                         split_k)
     else:
         for i in range(n1):
-            _grad_launch(A, B, out, n0, M, N, K0, K1, i * a1, i * b1, i * c1, (a0, *sa), (b0, *sb), (c0, *sc))
+            _grad_launch(A, B, out, n0, M, N, K0, K1, i * a1, i * b1, i * c1, (a0, *sa), (b0, *sb), (c0, *sc),
+                         split_k)
     return out
 
 
@@ -1489,16 +1561,17 @@ class _LinearSTE(torch.autograd.Function):
     straight-through estimator: the exact product's gradients dX = dY Wq, dW = dY^T Xq."""
 
     @staticmethod
-    def forward(ctx, xq, wq, launch):
+    def forward(ctx, xq, wq, launch, split_k):
         ctx.save_for_backward(xq, wq)
+        ctx.split_k = split_k
         return launch(xq, wq)
 
     @staticmethod
     def backward(ctx, dy):
         xq, wq = ctx.saved_tensors
-        dx = grad_bmm(dy, wq) if ctx.needs_input_grad[0] else None
-        dw = grad_bmm(dy.t(), xq) if ctx.needs_input_grad[1] else None
-        return dx, dw, None
+        dx = grad_bmm(dy, wq, **_split_kw(ctx.split_k)) if ctx.needs_input_grad[0] else None
+        dw = grad_bmm(dy.t(), xq, **_split_kw(ctx.split_k)) if ctx.needs_input_grad[1] else None
+        return dx, dw, None, None
 
 
 class _BmmSTE(torch.autograd.Function):
@@ -1507,8 +1580,9 @@ class _BmmSTE(torch.autograd.Function):
     both products."""
 
     @staticmethod
-    def forward(ctx, aq, bq, launch):
+    def forward(ctx, aq, bq, launch, split_k):
         ctx.save_for_backward(aq, bq)
+        ctx.split_k = split_k
         return launch(aq, bq)
 
     @staticmethod
@@ -1516,11 +1590,11 @@ class _BmmSTE(torch.autograd.Function):
         aq, bq = ctx.saved_tensors
         da = db = None
         if ctx.needs_input_grad[0]:
-            da = grad_bmm(dc, bq.transpose(-1, -2))
+            da = grad_bmm(dc, bq.transpose(-1, -2), **_split_kw(ctx.split_k))
         if ctx.needs_input_grad[1]:
             db = torch.empty(bq.shape, dtype=torch.float32, device=bq.device)
-            grad_bmm(dc.transpose(-1, -2), aq, out=db.transpose(-1, -2))
-        return da, db, None
+            grad_bmm(dc.transpose(-1, -2), aq, out=db.transpose(-1, -2), **_split_kw(ctx.split_k))
+        return da, db, None, None
 
 
 class _Conv2dSTE(torch.autograd.Function):
@@ -1534,8 +1608,9 @@ class _Conv2dSTE(torch.autograd.Function):
     tensor-bias semantics (F5) are a quirk of the forward product only."""
 
     @staticmethod
-    def forward(ctx, xq, wq, launch, stride, padding, dilation, groups):
+    def forward(ctx, xq, wq, launch, stride, padding, dilation, groups, split_k):
         ctx.save_for_backward(xq, wq)
+        ctx.split_k = split_k
         ctx.geo = (tuple(stride), tuple(padding), tuple(dilation), int(groups))
         return launch(xq, wq)
 
@@ -1560,29 +1635,31 @@ class _Conv2dSTE(torch.autograd.Function):
             _lib.check(rc, "fp8a_im2col")
             dw = torch.empty((G, Og, Kg), dtype=torch.float32, device=x.device)
             # A [G, Og, Bn, L] (the gradient), B [G, Bn, L, Kg] (the im2col image)
-            grad_bmm(dyg.permute(1, 2, 0, 3), cols.permute(2, 0, 1, 3), out=dw, k2=True)
+            grad_bmm(dyg.permute(1, 2, 0, 3), cols.permute(2, 0, 1, 3), out=dw, k2=True, **_split_kw(ctx.split_k))
             del cols
             dw = dw.view(wq.shape)
         if ctx.needs_input_grad[0]:
             w = wq.contiguous().view(G, Og, Kg)
             dxcol = torch.empty((Bn, G, Kg, Ln), dtype=torch.float32, device=dy.device)
             # C^T [Bn, G, L, Kg] = A [Bn, G, L, Og] (the gradient, pixels as rows) @ B [G, Og, Kg]
-            grad_bmm(dyg.transpose(-1, -2), w.unsqueeze(0).expand(Bn, G, Og, Kg), out=dxcol.transpose(-1, -2))
+            grad_bmm(dyg.transpose(-1, -2), w.unsqueeze(0).expand(Bn, G, Og, Kg), out=dxcol.transpose(-1, -2),
+                     **_split_kw(ctx.split_k))
             with _ste_timed("fold"):
                 dx = torch.nn.functional.fold(dxcol.view(Bn, G * Kg, Ln), (H, W), (kh, kw), dilation, padding, stride)
-        return dx, dw, None, None, None, None, None
+        return dx, dw, None, None, None, None, None, None
 
 
-def ste_linear(xq, wq, launch):
-    """launch(xq, wq) -> [R, N] with the straight-through backward (xq [R, K], wq [N, K] quantized operands)."""
-    return _LinearSTE.apply(xq, wq, launch)
+def ste_linear(xq, wq, launch, split_k=1):
+    """launch(xq, wq) -> [R, N] with the straight-through backward (xq [R, K], wq [N, K] quantized operands);
+    split_k: grad_bmm's, for every product of the backward (ste_bmm and ste_conv2d alike)."""
+    return _LinearSTE.apply(xq, wq, launch, check_split_k(split_k))
 
 
-def ste_bmm(aq, bq, launch):
+def ste_bmm(aq, bq, launch, split_k=1):
     """launch(aq, bq) -> [..., M, N] with the straight-through backward (quantized batched operands)."""
-    return _BmmSTE.apply(aq, bq, launch)
+    return _BmmSTE.apply(aq, bq, launch, check_split_k(split_k))
 
 
-def ste_conv2d(xq, wq, launch, stride=(1, 1), padding=(0, 0), dilation=(1, 1), groups=1):
+def ste_conv2d(xq, wq, launch, stride=(1, 1), padding=(0, 0), dilation=(1, 1), groups=1, split_k=1):
     """launch(xq, wq) -> NCHW y with the straight-through backward (quantized NCHW input and weights)."""
-    return _Conv2dSTE.apply(xq, wq, launch, stride, padding, dilation, groups)
+    return _Conv2dSTE.apply(xq, wq, launch, stride, padding, dilation, groups, check_split_k(split_k))

@@ -2057,27 +2057,32 @@ int fp8a_bmm_stats(uint64_t out[3], int reset) {
 
 // ------------------------------------------------------------------------- gradient GEMM
 // fp8a_grad_bmm (gemm_grad.h): one launch of gemm_grad_kernel over (64 x 64 tiles, batch items), nothing else
-// on the stream, as fp8a_bmm.
+// on the stream, as fp8a_bmm.  fp8a_grad_bmm_split: the same product with K split into S parts -- the product
+// pass over (tiles, batch items, parts) into the caller's workspace, then the reduce pass, both on the stream.
 static std::atomic<uint64_t> g_grad_launches, g_grad_tiles;  // host-side (a replayed graph adds nothing)
 
-int fp8a_grad_bmm(const float *A, const float *B, float *C, int64_t nb, int64_t M, int64_t N, int64_t K0, int64_t K1,
-                  int64_t sa_i, int64_t sa_m, int64_t sa_k0, int64_t sa_k1, int64_t sb_i, int64_t sb_k0, int64_t sb_k1,
-                  int64_t sb_n, int64_t sc_i, int64_t sc_m, int64_t sc_n, fp8a_stream_t stream) {
-    if (nb < 0 || M < 0 || N < 0 || K0 < 0 || K1 < 0) return fail(FP8A_EINVAL, "fp8a_grad_bmm: negative extent");
+// What both entries check, with the same texts under the entry's own name, and the kernel's arguments.
+// FP8A_OK with run = false: an empty product, nothing to launch.
+static int grad_args(const char *who, const float *A, const float *B, float *C, int64_t nb, int64_t M, int64_t N,
+                     int64_t K0, int64_t K1, int64_t sa_i, int64_t sa_m, int64_t sa_k0, int64_t sa_k1, int64_t sb_i,
+                     int64_t sb_k0, int64_t sb_k1, int64_t sb_n, int64_t sc_i, int64_t sc_m, int64_t sc_n, GradArgs &a,
+                     bool &run) {
+    const std::string w = std::string(who) + ": ";
+    run = false;
+    if (nb < 0 || M < 0 || N < 0 || K0 < 0 || K1 < 0) return fail(FP8A_EINVAL, w + "negative extent");
     if (sa_i < 0 || sa_m < 0 || sa_k0 < 0 || sa_k1 < 0 || sb_i < 0 || sb_k0 < 0 || sb_k1 < 0 || sb_n < 0 || sc_i < 0 ||
         sc_m < 0 || sc_n < 0)
-        return fail(FP8A_EINVAL, "fp8a_grad_bmm: negative stride");
-    if (K0 > 0 && K1 > 0x7FFFFFFFll / K0) return fail(FP8A_EINVAL, "fp8a_grad_bmm: K0 * K1 exceeds 2^31 - 1");
+        return fail(FP8A_EINVAL, w + "negative stride");
+    if (K0 > 0 && K1 > 0x7FFFFFFFll / K0) return fail(FP8A_EINVAL, w + "K0 * K1 exceeds 2^31 - 1");
     const int64_t K = K0 * K1;
     if (nb == 0 || M == 0 || N == 0) return FP8A_OK;
-    if (!C || (K > 0 && (!A || !B))) return fail(FP8A_EINVAL, "fp8a_grad_bmm: null pointer");
+    if (!C || (K > 0 && (!A || !B))) return fail(FP8A_EINVAL, w + "null pointer");
     if ((sc_m == 0 && M > 1) || (sc_n == 0 && N > 1) || (sc_i == 0 && nb > 1))
-        return fail(FP8A_EINVAL, "fp8a_grad_bmm: a zero stride of C over an extent above 1");
+        return fail(FP8A_EINVAL, w + "a zero stride of C over an extent above 1");
     if (K > 0 && c_overlaps_operand(A, bmm_span(nb, sa_i, M, sa_m, K0, sa_k0, K1, sa_k1), B,
                                     bmm_span(nb, sb_i, K0, sb_k0, K1, sb_k1, N, sb_n), C,
                                     bmm_span(1, 0, nb, sc_i, M, sc_m, N, sc_n), nb, M, N, K))
-        return fail(FP8A_EINVAL, "fp8a_grad_bmm: C overlaps an operand");
-    GradArgs a;
+        return fail(FP8A_EINVAL, w + "C overlaps an operand");
     memset(&a, 0, sizeof(a));
     a.A = A; a.B = B; a.C = C; a.M = M; a.N = N;
     a.K0 = (uint32_t)K0; a.K1 = (uint32_t)K1; a.K = (uint32_t)K;
@@ -2086,13 +2091,93 @@ int fp8a_grad_bmm(const float *A, const float *B, float *C, int64_t nb, int64_t 
     a.sc_i = sc_i; a.sc_m = sc_m; a.sc_n = sc_n;
     a.num_mt = (M + GR_T - 1) / GR_T;
     a.tiles = a.num_mt * ((N + GR_T - 1) / GR_T);
-    if (a.tiles > 0x7FFFFFFFll / nb) return fail(FP8A_EINVAL, "fp8a_grad_bmm: more than 2^31 - 1 tiles");
+    if (a.tiles > 0x7FFFFFFFll / nb) return fail(FP8A_EINVAL, w + "more than 2^31 - 1 tiles");
+    run = true;
+    return FP8A_OK;
+}
+
+int fp8a_grad_bmm(const float *A, const float *B, float *C, int64_t nb, int64_t M, int64_t N, int64_t K0, int64_t K1,
+                  int64_t sa_i, int64_t sa_m, int64_t sa_k0, int64_t sa_k1, int64_t sb_i, int64_t sb_k0, int64_t sb_k1,
+                  int64_t sb_n, int64_t sc_i, int64_t sc_m, int64_t sc_n, fp8a_stream_t stream) {
+    GradArgs a;
+    bool run;
+    const int rc = grad_args("fp8a_grad_bmm", A, B, C, nb, M, N, K0, K1, sa_i, sa_m, sa_k0, sa_k1, sb_i, sb_k0, sb_k1,
+                             sb_n, sc_i, sc_m, sc_n, a, run);
+    if (rc || !run) return rc;
     a.recount = grad_recount_ptr();
     if (a.recount == nullptr) return fail(FP8A_EHIP, "fp8a_grad_bmm: the recomputed-tile counter's address");
     launch_grad(a, dim3((unsigned)(a.tiles * nb)), (hipStream_t)stream);
     ++g_grad_launches;
     g_grad_tiles += (uint64_t)(a.tiles * nb);
     return hip_check("fp8a_grad_bmm launch");
+}
+
+// The split plan: nst = ceil(K / 32) stages, per = ceil(nst / splits) stages per part, S = ceil(nst / per)
+// parts, none empty; part s owns the stages [s per, min((s + 1) per, nst)).  S = 1 when nst <= 1 or splits = 1.
+static void grad_split_plan(int64_t K, int64_t splits, int64_t &per, int64_t &S) {
+    const int64_t nst = (K + GR_BK - 1) / GR_BK;
+    per = nst > 0 ? (nst + splits - 1) / splits : 1;
+    S = nst > 0 ? (nst + per - 1) / per : 1;
+}
+
+int fp8a_grad_bmm_split_workspace_size(int64_t nb, int64_t M, int64_t N, int64_t K0, int64_t K1, int64_t splits,
+                                       int64_t *eff_splits, int64_t *bytes) {
+    const char *const w = "fp8a_grad_bmm_split_workspace_size: ";
+    if (!eff_splits || !bytes) return fail(FP8A_EINVAL, std::string(w) + "null pointer");
+    if (nb < 0 || M < 0 || N < 0 || K0 < 0 || K1 < 0) return fail(FP8A_EINVAL, std::string(w) + "negative extent");
+    if (K0 > 0 && K1 > 0x7FFFFFFFll / K0) return fail(FP8A_EINVAL, std::string(w) + "K0 * K1 exceeds 2^31 - 1");
+    if (splits < 1) return fail(FP8A_EINVAL, std::string(w) + "splits below 1");
+    int64_t per, S;
+    grad_split_plan(K0 * K1, splits, per, S);
+    const int64_t tiles = ((M + GR_T - 1) / GR_T) * ((N + GR_T - 1) / GR_T);
+    if (nb > 0 && tiles > 0 && tiles > 0x7FFFFFFFll / nb / S)
+        return fail(FP8A_EINVAL, std::string(w) + "more than 2^31 - 1 blocks");
+    *eff_splits = S;
+    *bytes = S > 1 ? S * nb * tiles * (GR_T * GR_T) * (int64_t)sizeof(float) : 0;
+    return FP8A_OK;
+}
+
+int fp8a_grad_bmm_split(const float *A, const float *B, float *C, int64_t nb, int64_t M, int64_t N, int64_t K0,
+                        int64_t K1, int64_t sa_i, int64_t sa_m, int64_t sa_k0, int64_t sa_k1, int64_t sb_i,
+                        int64_t sb_k0, int64_t sb_k1, int64_t sb_n, int64_t sc_i, int64_t sc_m, int64_t sc_n,
+                        int64_t splits, void *workspace, int64_t workspace_bytes, fp8a_stream_t stream) {
+    GradArgs a;
+    bool run;
+    const int rc = grad_args("fp8a_grad_bmm_split", A, B, C, nb, M, N, K0, K1, sa_i, sa_m, sa_k0, sa_k1, sb_i, sb_k0,
+                             sb_k1, sb_n, sc_i, sc_m, sc_n, a, run);
+    if (rc) return rc;
+    if (splits < 1) return fail(FP8A_EINVAL, "fp8a_grad_bmm_split: splits below 1");
+    if (!run) return FP8A_OK;
+    int64_t per, S;
+    grad_split_plan(K0 * K1, splits, per, S);
+    if (a.tiles * nb > 0x7FFFFFFFll / S) return fail(FP8A_EINVAL, "fp8a_grad_bmm_split: more than 2^31 - 1 blocks");
+    const int64_t need = S * nb * a.tiles * (GR_T * GR_T) * (int64_t)sizeof(float);
+    if (S > 1) {
+        if (!workspace) return fail(FP8A_EINVAL, "fp8a_grad_bmm_split: null workspace");
+        if (workspace_bytes < need)
+            return fail(FP8A_EINVAL, "fp8a_grad_bmm_split: workspace of " + std::to_string(workspace_bytes) +
+                                         " bytes, " + std::to_string(need) + " needed");
+        if (((uintptr_t)workspace & 15u) != 0)
+            return fail(FP8A_EINVAL, "fp8a_grad_bmm_split: workspace not 16-byte aligned");
+        // the workspace over A, B or C, where that is cheap to see: c_overlaps_operand's rule with the workspace
+        // (dense by construction) in C's place, and C as an operand when it is dense
+        const float *const W = (const float *)workspace;
+        const int64_t ew = need / (int64_t)sizeof(float), K = K0 * K1;
+        const int64_t ea = bmm_span(nb, sa_i, M, sa_m, K0, sa_k0, K1, sa_k1);
+        const int64_t eb = bmm_span(nb, sb_i, K0, sb_k0, K1, sb_k1, N, sb_n);
+        const int64_t ec = bmm_span(1, 0, nb, sc_i, M, sc_m, N, sc_n);
+        const bool oa = W == A || (ea == nb * M * K && W < A + ea && A < W + ew);
+        const bool ob = W == B || (eb == nb * K * N && W < B + eb && B < W + ew);
+        const bool oc = W == C || (ec == nb * M * N && W < C + ec && C < W + ew);
+        if (oa || ob || oc) return fail(FP8A_EINVAL, "fp8a_grad_bmm_split: the workspace overlaps A, B or C");
+    }
+    a.recount = grad_recount_ptr();
+    if (a.recount == nullptr) return fail(FP8A_EHIP, "fp8a_grad_bmm_split: the recomputed-tile counter's address");
+    if (S == 1) launch_grad(a, dim3((unsigned)(a.tiles * nb)), (hipStream_t)stream);
+    else launch_grad_split(a, nb, S, per, (float *)workspace, (hipStream_t)stream);
+    ++g_grad_launches;
+    g_grad_tiles += (uint64_t)(a.tiles * nb * S);
+    return hip_check("fp8a_grad_bmm_split launch");
 }
 
 int fp8a_grad_stats(uint64_t out[3], int reset) {

@@ -21,6 +21,11 @@
 // A tile whose staging saw a B element that is not bf16-exact, or an A element the split loses (above; inf /
 // NaN included), recomputes itself with fp32 FMAs in the same k order after a workgroup-uniform branch and
 // counts itself in *recount (one atomic per recomputed tile, none otherwise), as gemm_bmm_kernel does.
+//
+// The split along K (fp8a_grad_bmm_split) is two more kernels around the same tile body:
+// gemm_grad_split_kernel gives each (tile, batch item, part) a workgroup that runs the part's stages and stores
+// its accumulator tile in a workspace, grad_reduce_kernel adds an output's parts in index order.  Two launches,
+// no flags or atomics between workgroups: as deterministic as the unsplit kernel.
 #pragma once
 #include "fp8approx_common.h"
 
@@ -39,6 +44,9 @@ struct GradArgs {
 };
 
 void launch_grad(const GradArgs &a, dim3 grid, hipStream_t s);
+// the split along K: gemm_grad_split_kernel over tiles nb S blocks into ws (S dense [nb][tiles][64][64] fp32
+// images), then grad_reduce_kernel over (tiles nb, 16) blocks; per: stages per part
+void launch_grad_split(const GradArgs &a, int64_t nb, int64_t S, int64_t per, float *ws, hipStream_t s);
 unsigned long long *grad_recount_ptr();  // nullptr: the address query failed
 int grad_recount_read(unsigned long long *v, bool reset);
 
@@ -69,25 +77,37 @@ __device__ __forceinline__ bool gr_split(float x, uint32_t &h0, uint32_t &h1, ui
     return ok;
 }
 
-__global__ __launch_bounds__(256) void gemm_grad_kernel(const GradArgs p) {
+// One workgroup's work, shared by the two product kernels.  SPLIT = false is gemm_grad_kernel: block = (tile,
+// item), the k range [0, K), the tile stored through C's strides.  SPLIT = true is gemm_grad_split_kernel: block =
+// (tile, item, part), part slowest; part s owns the stages [s per, (s + 1) per) -- kper = 32 per flat k -- runs the
+// same staged loads, piece splits and 12-MFMA steps on them from zero accumulators, and stores its whole 64 x 64
+// accumulator tile, dense and row-major, at ws + 4096 blockIdx.x: rows and columns beyond M and N hold the zeros
+// their zero-filled staging sums to, so grad_reduce_kernel reads nothing that was not written.  A block that
+// staged a lost element recomputes its own k range and counts itself once.
+template <bool SPLIT>
+__device__ __forceinline__ void gr_block(const GradArgs &p, float *const ws, const int64_t nb, const uint32_t kper) {
     __shared__ __attribute__((aligned(16))) uint8_t sA[3][GR_T][GR_RS];
     __shared__ __attribute__((aligned(16))) uint8_t sB[GR_T][GR_RS];
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int r16 = lane & 15, g = lane >> 4;
-    const int64_t bid = (int64_t)blockIdx.x % p.tiles, z = (int64_t)blockIdx.x / p.tiles;
+    const int64_t bid = (int64_t)blockIdx.x % p.tiles, zs = (int64_t)blockIdx.x / p.tiles;
+    const int64_t z = SPLIT ? zs % nb : zs, part = SPLIT ? zs / nb : 0;
     const int64_t m0 = (bid % p.num_mt) * GR_T, n0 = (bid / p.num_mt) * GR_T;
     const float *const A = p.A + z * p.sa_i;
     const float *const B = p.B + z * p.sb_i;
     float *const C = p.C + z * p.sc_i;
-    const uint32_t K = p.K, K1 = p.K1;
+    // the flat k range [kbeg, K) of this block (K: where its walk ends)
+    const uint64_t kpast = (uint64_t)kper * (uint64_t)(part + 1);
+    const uint32_t kbeg = SPLIT ? kper * (uint32_t)part : 0u;
+    const uint32_t K = SPLIT && kpast < p.K ? (uint32_t)kpast : p.K, K1 = p.K1;
 
     gr_v4f acc[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) acc[j] = (gr_v4f){0.0f, 0.0f, 0.0f, 0.0f};
 
-    if (K > 0) {  // (K = 0: the sum over an empty axis, zeros; nothing but C is touched)
+    if (K > kbeg) {  // (an empty range: the sum over an empty axis, zeros; nothing but C is touched)
         // staging: thread = (row / column sr, k group sg): 8 consecutive k of the stage.  Lanes run along
         // the rows, so an operand with unit m (n) stride loads full lines and one with unit k stride 32
         // contiguous bytes per lane.
@@ -115,10 +135,10 @@ __global__ __launch_bounds__(256) void gemm_grad_kernel(const GradArgs p) {
                 }
             }
         };
-        load_tile(0);
+        load_tile(kbeg);
 
         int anybad = 0;
-        for (uint32_t ks = 0; ks < K; ks += GR_BK) {
+        for (uint32_t ks = kbeg; ks < K; ks += GR_BK) {
             bool bad = false;
             uint32_t w0[4], w1[4], w2[4], wb[4];
 #pragma unroll
@@ -170,10 +190,26 @@ __global__ __launch_bounds__(256) void gemm_grad_kernel(const GradArgs p) {
                     if (m < p.M && n < p.N) {
                         const float *const ap = A + m * p.sa_m;
                         const float *const bp = B + n * p.sb_n;
-                        for (uint32_t k0 = 0; k0 < p.K0; ++k0)
-                            for (uint32_t k1 = 0; k1 < K1; ++k1)
-                                s = __fmaf_rn(ap[(int64_t)k0 * p.sa_k0 + (int64_t)k1 * p.sa_k1],
-                                              bp[(int64_t)k0 * p.sb_k0 + (int64_t)k1 * p.sb_k1], s);
+                        if constexpr (!SPLIT) {  // [0, K0 K1): the two levels as they are
+                            for (uint32_t k0 = 0; k0 < p.K0; ++k0)
+                                for (uint32_t k1 = 0; k1 < K1; ++k1)
+                                    s = __fmaf_rn(ap[(int64_t)k0 * p.sa_k0 + (int64_t)k1 * p.sa_k1],
+                                                  bp[(int64_t)k0 * p.sb_k0 + (int64_t)k1 * p.sb_k1], s);
+                        } else {  // a part may begin and end inside a k0 row: the flat walk of load_tile
+                            uint32_t q1 = kbeg % K1;
+                            int64_t oa = (int64_t)(kbeg / K1) * p.sa_k0 + (int64_t)q1 * p.sa_k1;
+                            int64_t ob = (int64_t)(kbeg / K1) * p.sb_k0 + (int64_t)q1 * p.sb_k1;
+                            for (uint32_t k = kbeg; k < K; ++k) {
+                                s = __fmaf_rn(ap[oa], bp[ob], s);
+                                oa += p.sa_k1;
+                                ob += p.sb_k1;
+                                if (++q1 == K1) {
+                                    q1 = 0;
+                                    oa += p.sa_k0 - (int64_t)K1 * p.sa_k1;
+                                    ob += p.sb_k0 - (int64_t)K1 * p.sb_k1;
+                                }
+                            }
+                        }
                     }
                     // (a dynamic index: one select chain over the 16 accumulators, off the hot path)
 #pragma unroll
@@ -187,6 +223,14 @@ __global__ __launch_bounds__(256) void gemm_grad_kernel(const GradArgs p) {
     }
 
     // ---- store: D[m][n], lane (r16, g) holds rows 4 g + r of its wave's 16, column r16 of block j
+    if constexpr (SPLIT) {
+        float *const W = ws + (int64_t)blockIdx.x * (GR_T * GR_T);
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) W[GR_T * (16 * wv + 4 * g + r) + 16 * j + r16] = acc[j][r];
+        return;
+    }
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         const int64_t n = n0 + 16 * j + r16;
@@ -197,6 +241,33 @@ __global__ __launch_bounds__(256) void gemm_grad_kernel(const GradArgs p) {
             if (m < p.M) C[m * p.sc_m + n * p.sc_n] = acc[j][r];
         }
     }
+}
+
+__global__ __launch_bounds__(256) void gemm_grad_kernel(const GradArgs p) { gr_block<false>(p, nullptr, 1, 0u); }
+
+__global__ __launch_bounds__(256) void gemm_grad_split_kernel(const GradArgs p, float *const ws, const int64_t nb,
+                                                              const uint32_t kper) {
+    gr_block<true>(p, ws, nb, kper);
+}
+
+// The reduce pass: one thread per output element, block = four rows of one (item, tile), blockIdx.y the row
+// group; lane = column, so every workspace read is a full 256-byte row.  The parts are added in index order
+// from P_0 (not from +0: a sum of negative zeros stays negative), plain fp32 adds; stored through C's strides.
+__global__ __launch_bounds__(256) void grad_reduce_kernel(const GradArgs p, const float *const ws, const int64_t nb,
+                                                          const int S) {
+    const int col = threadIdx.x & 63, row = 4 * (int)blockIdx.y + (int)(threadIdx.x >> 6);
+    const int64_t bid = (int64_t)blockIdx.x % p.tiles, z = (int64_t)blockIdx.x / p.tiles;
+    const int64_t m = (bid % p.num_mt) * GR_T + row, n = (bid / p.num_mt) * GR_T + col;
+    if (m >= p.M || n >= p.N) return;
+    const int64_t part = nb * p.tiles * (GR_T * GR_T);
+    const float *w = ws + (int64_t)blockIdx.x * (GR_T * GR_T) + GR_T * row + col;
+    float acc = *w;
+#pragma unroll 4
+    for (int s = 1; s < S; ++s) {
+        w += part;
+        acc = acc + *w;
+    }
+    p.C[z * p.sc_i + m * p.sc_m + n * p.sc_n] = acc;
 }
 #endif  // FP8A_OWN_GRAD
 

@@ -1,4 +1,5 @@
-// k_grad.hip -- gemm_grad_kernel (gemm_grad.h: the gradient GEMM of fp8a_grad_bmm) in its own translation
+// k_grad.hip -- gemm_grad_kernel (gemm_grad.h: the gradient GEMM of fp8a_grad_bmm) and the two passes of its
+// split along K (gemm_grad_split_kernel, grad_reduce_kernel: fp8a_grad_bmm_split) in their own translation
 // unit, with the recomputed-tile counter.
 #define FP8A_OWN_GRAD 1
 #include "gemm_grad.h"
@@ -29,5 +30,10 @@ int grad_recount_read(unsigned long long *v, bool reset) {
 }
 
 void launch_grad(const GradArgs &a, dim3 grid, hipStream_t s) { gemm_grad_kernel<<<grid, 256, 0, s>>>(a); }
+
+void launch_grad_split(const GradArgs &a, int64_t nb, int64_t S, int64_t per, float *ws, hipStream_t s) {
+    gemm_grad_split_kernel<<<dim3((unsigned)(a.tiles * nb * S)), 256, 0, s>>>(a, ws, nb, (uint32_t)(per * GR_BK));
+    grad_reduce_kernel<<<dim3((unsigned)(a.tiles * nb), GR_T / 4), 256, 0, s>>>(a, ws, nb, (int)S);
+}
 
 }  // namespace fp8a

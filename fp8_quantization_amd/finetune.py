@@ -4,7 +4,7 @@ quantizer masks, the exact product's gradients on the gradient GEMM fp8a_grad_bm
 
     python -m fp8_quantization_amd.finetune --synthetic 64 --arch resnet18|mobilenet_v2|vit_b16 \
         --steps 10 --lr 1e-3 [--batch-size 64] [--momentum 0.9] [--approx-attention] \
-        [--learn-ranges [--range-lr 1e-4]] [--seed 0]
+        [--learn-ranges [--range-lr 1e-4]] [--grad-split-k N|auto] [--seed 0]
 
 A driver, not a trainer (no schedule, checkpoints or augmentation): it calibrates and fixes the FP8 ranges as
 the validation driver does (imagenet.py: estimate_ranges over --num-est-batches batches, fix_ranges), keeps the
@@ -19,6 +19,9 @@ learn_maxval, learn_ranges() follows the calibration, the maxvals form their own
 of learned ranges, the quantizers' recorded forward + backward milliseconds and the largest relative change
 of any maxval since calibration (without the flag: 0 ranges, the milliseconds, 0.0).  The driver does not
 clamp a range: a maxval that is not finite or not positive after a step ends the run with exit status 1.
+--grad-split-k: every gradient GEMM of the backward splits its reduction along K into N parts, or into what
+approx_ops.grad_split_auto picks per product ("auto"), and adds the parts in a fixed order:
+custom_approx_params["grad_split_k"]; default 1, off.  grad_gemm_ms then includes the reduce passes.
 Data: --synthetic N random images and labels, or <images-dir>/train as imagenet.py reads it.
 """
 import argparse
@@ -30,6 +33,18 @@ import torch
 
 from . import _lib, approx_ops
 from .imagenet import NumericImageFolder, SyntheticImages, _loader, build_model
+
+
+def _split_k(v):
+    if v == "auto":
+        return v
+    try:
+        n = int(v)
+    except ValueError:
+        n = 0
+    if n < 1:
+        raise argparse.ArgumentTypeError(f"an integer >= 1 or auto, not {v!r}")
+    return n
 
 
 def parse(argv=None):
@@ -55,6 +70,8 @@ def parse(argv=None):
     ap.add_argument("--learn-ranges", action="store_true",
                     help="train every FP8 quantizer's maxval as well (its own parameter group)")
     ap.add_argument("--range-lr", type=float, default=None, help="learning rate of the maxvals (default: --lr)")
+    ap.add_argument("--grad-split-k", type=_split_k, default=1, metavar="{N,auto}",
+                    help="split the gradient GEMMs' reductions along K: a part count, or auto (default 1: off)")
     ap.add_argument("--output", default=None, help="also write the step records (a JSON list) here")
     return ap.parse_args(argv)
 
@@ -66,6 +83,8 @@ def approx_cfg(args):
         cfg["approx_attention"] = True
     if args.learn_ranges:
         cfg["learn_maxval"] = True
+    if getattr(args, "grad_split_k", 1) != 1:
+        cfg["grad_split_k"] = args.grad_split_k
     return cfg
 
 

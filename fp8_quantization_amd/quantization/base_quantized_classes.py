@@ -65,6 +65,15 @@ def sync_ste(module):
     return torch.is_grad_enabled()
 
 
+def grad_split_k(module):
+    """custom_approx_params['grad_split_k'] of a layer: the split along K of its backward's gradient GEMMs
+    (approx_ops.grad_bmm's split_k).  Absent or 1: off; else an int >= 2 or "auto"; anything else raises
+    ValueError (at construction too).  Without ste_backward the layer records no backward and the key does nothing."""
+    from ..approx_ops import check_split_k  # (approx_ops does not import this package: no cycle, but keep it lazy)
+    return check_split_k((getattr(module, "custom_approx_params", None) or {}).get("grad_split_k", 1),
+                         "custom_approx_params['grad_split_k']")
+
+
 def _version5(module):
     return (getattr(module, "custom_approx_params", None) or {}).get("approx_version", 9) == 5
 
@@ -80,6 +89,7 @@ class QuantizedModule(nn.Module):
                  act_quant_kwargs=None, weight_quant_kwargs=None, quantize_input=False, fp8_kwargs=None, **kwargs):
         kwargs.pop("act_quant_dict", None)
         self.custom_approx_params = kwargs.pop("custom_approx_params", None)
+        grad_split_k(self)  # (a value the backward cannot take raises here, not in the first backward)
         self.run_method = kwargs.pop("run_method", None) or dict(_DEFAULT_RUN_METHOD)
         self.approx_flag = self.run_method["approx_flag"]
         self.quantize_after_mult_and_add = self.run_method["quantize_after_mult_and_add"]

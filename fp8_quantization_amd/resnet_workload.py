@@ -25,7 +25,7 @@ def approx_qparams(expo_width=4, mant_width=3, dnsmp_factor=3, withComp=False, w
                    zero_table_ext=None, approx_version=9, sim_hw_add_OFUF=False, with_OF_opt=False,
                    with_UF_opt=False, weight_range_method="current_minmax", weight_range_options=None,
                    act_range_method="allminmax", act_range_options=None, mse_include_mantissa_bits=False,
-                   error_table=None, ste_backward=False, learn_maxval=False):
+                   error_table=None, ste_backward=False, learn_maxval=False, grad_split_k=1):
     """qparams exactly as the reference scripts build them (utils/click_options.py:544-606,
     scripts/generated_scripts.py): per-channel current_minmax weights, allminmax activations,
     quantize_input, FP8 quantizer with set_maxval, approx + res_quantizer run method.
@@ -37,6 +37,8 @@ def approx_qparams(expo_width=4, mant_width=3, dnsmp_factor=3, withComp=False, w
     table selection (withComp / dnsmp_factor / zero_table_ext) for the v9 model, for any format;
     ste_backward (opt-in, custom_approx_params["ste_backward"]): forwards that autograd records run unfused
     with a straight-through backward on the gradient GEMM (INTEGRATION.md), nothing else changes;
+    grad_split_k (custom_approx_params["grad_split_k"]: an int >= 2 or "auto"; 1 = off): that backward's gradient
+    GEMMs split their reduction along K (approx_ops.grad_bmm's split_k), nothing without ste_backward;
     learn_maxval (the reference's --fp8-learn-maxval): every FP8 quantizer is built so that learn_ranges()
     turns its maxval into a Parameter (needs ste_backward for its gradient).
 
@@ -64,6 +66,7 @@ def approx_qparams(expo_width=4, mant_width=3, dnsmp_factor=3, withComp=False, w
                                   **({"zero_table_ext": True} if zero_table_ext else {}),
                                   **({"error_table": error_table} if error_table is not None else {}),
                                   **({"ste_backward": True} if ste_backward else {}),
+                                  **({"grad_split_k": grad_split_k} if grad_split_k != 1 else {}),
                                   **({"approx_version": 5} if approx_version == 5 else {})),
         run_method=dict(run_method) if run_method else dict(
             approx_flag=True, quantize_after_mult_and_add=False, res_quantizer_flag=True, original_quantize_res=False))

@@ -341,6 +341,33 @@ int fp8a_grad_bmm(const float *A, const float *B, float *C,
 int fp8a_grad_stats(uint64_t out[3], int reset);
 
 /*
+ * The gradient GEMM with a deterministic split along K: the same product as fp8a_grad_bmm,
+ * for reductions whose output has too few 64 x 64 tiles to fill the device (a convolution's weight gradient).
+ * The plan: nst = ceil(K0 K1 / 32) stages, per = ceil(nst / splits), S = ceil(nst / per) parts (S = 1 when
+ * nst <= 1 or splits == 1; no part is empty); part s owns the flat k in [32 per s, min(32 per (s + 1), K)).
+ * Two launches on the stream: the product pass, one workgroup per (tile, batch item, part), stores each
+ * part's 64 x 64 fp32 tile in the workspace; the reduce pass adds the parts of an output in index order,
+ * P_0 + P_1 + ... in plain fp32, and stores through C's strides.  No atomics on floats, no arrival order:
+ * two calls give the same bytes, and the result is the index-order fp32 sum of what fp8a_grad_bmm gives on
+ * the parts' K-slices (on exact-sum inputs: the exact sum).  A part whose staging saw a lost element
+ * recomputes its own K range and counts once.
+ * fp8a_grad_bmm_split_workspace_size: the plan's S and the workspace's bytes, S nb tiles 4096 4 (0 when
+ * S == 1); no HIP call.  fp8a_grad_bmm_split: fp8a_grad_bmm's arguments and checks, then splits >= 1, and
+ * with S > 1 a workspace of at least that size, 16-byte aligned, not overlapping A, B or C; with S == 1 it
+ * is fp8a_grad_bmm's launch and the workspace is not touched.  Every check runs before any HIP call.
+ * fp8a_grad_stats counts a call of either entry as one launch, tiles nb S product-pass workgroups as tiles,
+ * and each recomputed (tile, part) workgroup.
+ */
+int fp8a_grad_bmm_split_workspace_size(int64_t nb, int64_t M, int64_t N, int64_t K0, int64_t K1,
+                                       int64_t splits, int64_t *eff_splits, int64_t *bytes);
+int fp8a_grad_bmm_split(const float *A, const float *B, float *C,
+                        int64_t nb, int64_t M, int64_t N, int64_t K0, int64_t K1,
+                        int64_t sa_i, int64_t sa_m, int64_t sa_k0, int64_t sa_k1,
+                        int64_t sb_i, int64_t sb_k0, int64_t sb_k1, int64_t sb_n,
+                        int64_t sc_i, int64_t sc_m, int64_t sc_n,
+                        int64_t splits, void *workspace, int64_t workspace_bytes, fp8a_stream_t stream);
+
+/*
  * Per-product terms (debug / parity): T[m, k, n] = the value the reference sums at v9:113.
  * Same arguments as fp8a_matmul; T is dense [M][K][N].
  */
