@@ -116,6 +116,30 @@ static bool xm_table_form(const TablePack &tp, int Mw, int *vmin) {
     return true;
 }
 
+// The error tables the E3M4 / E2M5 tile-table forms (gemm_tt.h, gemm_tt16.h) are exact on:
+// every N = (2^M + m_a)(2^M + m_b) - 2^M t >= 0, i.e. no V = N 2^-2M is negative.  Both forms apply Q_R's
+// pre-clamp to V as a value, not to |V|, so a negative V whose mantissa lies above the bound would carry; the
+// F7 forms (a table with a negative entry) put the golden product's sign on |term| and would drop V's own; and
+// the forms without F7 (no negative entry) give the term the sign s_a s_b, which is the reference's only while
+// the approximate magnitude does not exceed the golden one: with t >= 0 and V >= 0 it never does, and V < 4,
+// which gemm_tt_kernel's band / zero wave-tile thresholds (E2M5) rest on.  V == 0 and 0 < V < 1 are exact in
+// both forms (V is a (2M + 2)-bit integer times 2^-2M in any binade); V >= 4 (a negative entry) leaves
+// gemm_tt16_kernel's f16 window, which tt_decode_b flags, and the f32 form reruns the launch.  *neg: some
+// entry is negative (the F7 forms).  Every other table runs gemm_fast_kernel<TM_LUT>.
+static bool tt_table_form(const TablePack &tp, int Mw, bool *neg) {
+    if (Mw < 1 || Mw > 5) return false;
+    const int n = 1 << Mw;
+    bool any_neg = false, ok = true;
+    for (int ma = 0; ma < n; ++ma)
+        for (int mb = 0; mb < n; ++mb) {
+            const int t = tp.raw[ma * n + mb];
+            any_neg |= t < 0;
+            ok = ok && (n + ma) * (n + mb) - n * t >= 0;
+        }
+    if (neg) *neg = any_neg;
+    return ok;
+}
+
 // Fallback statistics since load (or the last reset): [0] launches whose gated exact kernel
 // ran, [1] 64 x 64 output units it recomputed, [2] launches rerun in gemm_tt_kernel's f32 form
 // (gemm_tt16_kernel's f16 window left), [3] tensor-bias launches recomputed by
@@ -431,7 +455,9 @@ __global__ __launch_bounds__(256) void conv_tb_fast_kernel(const float *x, const
                 // F7: Q_R(g) == 0 (so the sign is +) only for |g| in [2^-bR, 2^-bR (1 + 2^-(M+1))]; without
                 // quant_btw_mult_accu the sign is that of the unquantized g (v9:35-36, 68)
                 const float ag = fabsf(gq);
-                if (qbma && gq < 0.0f && ag >= zlo && ag <= zhi) v = fabsf(v);
+                // (v = V 2^e sign(g) with g < 0: the term V 2^e is -v, |v| only where V > 0 -- a custom table's
+                // V may be negative)
+                if (qbma && gq < 0.0f && ag >= zlo && ag <= zhi) v = -v;
                 if (qbma) {
                     const uint32_t pb = __float_as_uint(v) & 0x7F800000u;
                     const float pe = __uint_as_float(pb);
@@ -868,14 +894,16 @@ static bool v5mx_form(int Mw, uint32_t flags, int table_mode) {
 // The tile-table kernel (gemm_tt_kernel) applies: E3M4 / E2M5 (mantissa 4 or 5), any table mode
 // of the int-bias path, s2n + qbma, no golden clip, not v5 (FP8A_NO_TT=1 keeps gemm_fast_kernel);
 // not E2M5 with a signed table: its F7 form (two 32-row tables, one K-step per staged tile) was
-// measured slower than gemm_fast_kernel.
-static bool tt_form(int Mw, uint32_t flags, const TablePack &tab) {
+// measured slower than gemm_fast_kernel -- and with it goes every E2M5 table whose V can reach
+// 4, which the band / zero thresholds of gemm_tt_kernel<5> exclude; and only a table of tt_table_form (no
+// negative V).
+static bool tt_form(int Mw, uint32_t flags, const TablePack &tab, bool *f7) {
+    *f7 = false;
     if (g_env.no_tt || (flags & F_V5) || !(Mw == 4 || Mw == 5) || !(flags & F_S2N) || !(flags & F_QBMA) ||
         (flags & F_GCLIP) || (flags & F_TB))
         return false;
-    bool neg = false;
-    for (int i = 0; i < (1 << (2 * Mw)); ++i) neg |= tab.raw[i] < 0;
-    return Mw == 4 || !neg;
+    if (!tt_table_form(tab, Mw, f7)) return false;  // (*f7: a negative entry, the F7 forms)
+    return Mw == 4 || !*f7;
 }
 
 // E3M4 on the tile-table path runs the packed-f16 form (gemm_tt16_kernel) for signed tables (F7:
@@ -893,7 +921,7 @@ static bool tt16_form(int Mw, bool f7, int64_t K) {
 // pre-decoded operands lie within the kernels' 32-bit byte offsets: the part of the decision that
 // run_gemm and the callers that fuse an input quantizer ahead of it share.  on: not FP8A_NO_MX.
 struct MxPlan {
-    bool f8, tt, v5mx, on, fits32;
+    bool f8, tt, ttf7, v5mx, on, fits32;  // ttf7: the tile-table launch's table has a negative entry
     int64_t kpad, npad;
     bool any() const { return (f8 || tt || v5mx) && on; }
 };
@@ -905,7 +933,7 @@ static MxPlan mx_plan(int E, int Mw, uint32_t flags, const TablePack &tab, int m
                       int64_t a_words) {
     MxPlan p;
     p.f8 = f8_form(E, Mw, flags, tab);
-    p.tt = !p.f8 && tt_form(Mw, flags, tab);
+    p.tt = tt_form(Mw, flags, tab, &p.ttf7) && !p.f8;
     p.v5mx = !p.f8 && v5mx_form(Mw, flags, mode);
     p.on = !g_env.no_mx;
     p.kpad = (K + BK - 1) / BK * BK;
@@ -1188,8 +1216,7 @@ static int run_gemm(GemmArgs &a, const int32_t *table, void *ws, size_t ws_bytes
             a.xm_vmin = 0;  // the table's lowest V' binade (the E5M2 halved-block form's `tok` threshold)
             if (mode == TM_F8) (void)xm_table_form(a.tab, a.Mw, &a.xm_vmin);
             a.npad = npad;
-            a.ttf7 = 0;
-            for (int i = 0; tt && i < (1 << (2 * a.Mw)); ++i) a.ttf7 |= a.tab.raw[i] < 0;
+            a.ttf7 = tt && mx.ttf7;
             a.wfmt = v5mx ? 4 : tt ? (tt16_form(a.Mw, a.ttf7, a.K) ? 2 : 1) : 0;
             if (a.wfmt == 1 && !opt(OPT_TT_BAND)) a.ebr = nullptr;  // (gemm_tt_kernel: no band test)
             a.xncg = tt ? 4 : xm_ncg(a.N);

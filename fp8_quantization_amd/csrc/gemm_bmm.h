@@ -296,7 +296,10 @@ __global__ __launch_bounds__(NT) void gemm_bmm_kernel(const BmmArgs p) {
                                 v0 = NEED_G ? __fmaf_rn(-tf, cab, g) : __fmaf_rn(a[i], b[j], -(tf * cab));
                             }
                             if (!S2N) v0 = (fabsf(g) >= qc.mnR) ? v0 : g;  // norm mask, v9:87
-                            if (S2N && QBMA && SGN) v0 = (g >= -qc.thr) ? fabsf(v0) : v0;  // F7
+                            // F7 (gemm_fast_kernel's rule: a TM_LUT table's V may be negative, the term keeps its sign)
+                            if (S2N && QBMA && SGN && TMODE == TM_LUT)
+                                v0 = (g >= -qc.thr) ? __uint_as_float(__float_as_uint(v0) ^ (__float_as_uint(g) & 0x80000000u)) : v0;
+                            else if (S2N && QBMA && SGN) v0 = (g >= -qc.thr) ? fabsf(v0) : v0;
                             acc[i][j] += QBMA ? q_fast<GCLIP>(v0, qc) : v0;
                         }
                 }

@@ -354,8 +354,13 @@ __global__ __launch_bounds__(NT) void gemm_fast_kernel(const GemmArgs p) {
                         }
                         if (!S2N) v0 = (fabsf(g) >= qc.mnR) ? v0 : g;  // norm mask, v9:87
                         // F7: the sign comes from Q_R(g), which is -0 (sign +1) for g in [-thr, 0);
-                        // v0 has g's sign, so for every g >= -thr the term is |v0|
-                        if (S2N && QBMA && SGN) v0 = (g >= -qc.thr) ? fabsf(v0) : v0;
+                        // v0 = V 2^e sign(g), so for every g >= -thr the term is v0 with g's sign taken
+                        // off: |v0| where V > 0 (the signed two-bit modes: T <= 1, so V >= 1 - 2^-M > 0 for
+                        // every M >= 1); a TM_LUT table holds any int8 entry, its V may be negative and
+                        // the term keeps V's sign
+                        if (S2N && QBMA && SGN && TMODE == TM_LUT)
+                            v0 = (g >= -qc.thr) ? __uint_as_float(__float_as_uint(v0) ^ (__float_as_uint(g) & 0x80000000u)) : v0;
+                        else if (S2N && QBMA && SGN) v0 = (g >= -qc.thr) ? fabsf(v0) : v0;
                         tacc[i][j] += QBMA ? q_fast<GCLIP>(v0, qc) : v0;
                     }
             }

@@ -147,6 +147,16 @@ def xm_table_form(table, M, approx=True):
     return bool(table.min() >= 0 and ((n + ma) * (n + mb) - n * table).min() >= 1)
 
 
+def tt_table_form(table, M, approx=True):
+    """tt_table_form (csrc/fp8approx.hip), restated: the tile-table forms take a table none of whose
+    V = ((2^M + m_a)(2^M + m_b) - 2^M t) 2^-2M is negative.  With approx off the kernels see a zero table."""
+    if not approx:
+        return True
+    n = 1 << M
+    ma, mb = np.meshgrid(np.arange(n), np.arange(n), indexing="ij")
+    return bool(((n + ma) * (n + mb) - n * table).min() >= 0)
+
+
 def expected_matmul_path(E, M, table, flags, K=1):
     """The path counter run_gemm advances (csrc/fp8approx.hip: f8_form, tt_form, tt16_form, v5mx_form) for a
     launch whose workspace holds the pre-decoded operands, with default options: the matrix-core and
@@ -160,7 +170,7 @@ def expected_matmul_path(E, M, table, flags, K=1):
         return "f8mx" if xm_table_form(table, M, approx) else "fast"
     if M in (4, 5):
         neg = approx and bool(table.min() < 0)
-        if M == 5 and neg:
+        if (M == 5 and neg) or not tt_table_form(table, M, approx):
             return "fast"
         return "tt16" if M == 4 and (neg or K >= 64) else "tt"
     return "fast"

@@ -13,6 +13,8 @@ against the CPU oracle:
   * the depthwise table form, the expo-0 binade included, gate word 0;
   * the hand-off between two convolutions; the operators and ResNet-18 with
     custom_approx_params["error_table"]; the validate driver's --error-table.
+The tables here are E4M3 / E5M2 ones with small entries.  E3M4 and E2M5, and tables over the whole int8 range
+on all four formats (V >= 4, V <= 0, 0 < V < 1/2), are in tests/test_gpu_wide_tables.py.
 """
 import json
 
