@@ -31,6 +31,7 @@ SYMBOLS = ("fp8a_version", "fp8a_last_error", "fp8a_fallback_stats", "fp8a_path_
            "fp8a_bn_train_workspace_size", "fp8a_bn_train", "fp8a_bmm", "fp8a_bmm_stats",
            "fp8a_bmm_check_workspace_size", "fp8a_bmm_check", "fp8a_grad_bmm", "fp8a_grad_stats",
            "fp8a_grad_bmm_split_workspace_size", "fp8a_grad_bmm_split",
+           "fp8a_grad_conv2d_dgrad", "fp8a_grad_conv2d_wgrad_workspace_size", "fp8a_grad_conv2d_wgrad",
            "fp8a_fq_train_workspace_size", "fp8a_fq_train_forward", "fp8a_fq_train_backward")
 
 _lib = None
@@ -126,6 +127,9 @@ def load():
         "fp8a_grad_stats": ([P, I], I),
         "fp8a_grad_bmm_split_workspace_size": ([I64] * 6 + [P, P], I),
         "fp8a_grad_bmm_split": ([P, P, P] + [I64] * 17 + [P, I64, P], I),
+        "fp8a_grad_conv2d_dgrad": ([P, P, P] + [I64] * 5 + [I] * 9 + [P], I),
+        "fp8a_grad_conv2d_wgrad_workspace_size": ([I64] * 5 + [I] * 9 + [I64, P, P], I),
+        "fp8a_grad_conv2d_wgrad": ([P, P, P] + [I64] * 5 + [I] * 9 + [I64, P, I64, P], I),
         "fp8a_fq_train_workspace_size": ([I64, I64], SZ),
         "fp8a_fq_train_forward": ([P, I64, I64, P, I, I, I, P, P, P, P, P], I),
         "fp8a_fq_train_backward": ([P, P, I64, I64, I, P, P, P, SZ, P], I),
@@ -286,6 +290,16 @@ def grad_split_plan(nb, M, N, K0, K1, splits):
     S, nbytes = ctypes.c_int64(0), ctypes.c_int64(0)
     check(L.fp8a_grad_bmm_split_workspace_size(nb, M, N, K0, K1, splits, ctypes.byref(S), ctypes.byref(nbytes)),
           "fp8a_grad_bmm_split_workspace_size")
+    return int(S.value), int(nbytes.value)
+
+
+def grad_conv_wgrad_plan(geo, splits):
+    """fp8a_grad_conv2d_wgrad_workspace_size: (S, bytes) of the weight gradient of the geometry geo = (Bn, Cin, H,
+    W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, groups) split into `splits` parts along K = Bn Ho Wo.  No device call."""
+    L = load()
+    S, nbytes = ctypes.c_int64(0), ctypes.c_int64(0)
+    check(L.fp8a_grad_conv2d_wgrad_workspace_size(*geo, splits, ctypes.byref(S), ctypes.byref(nbytes)),
+          "fp8a_grad_conv2d_wgrad_workspace_size")
     return int(S.value), int(nbytes.value)
 
 

@@ -32,7 +32,8 @@ from .approx_ops import (_bias_dev, _res_quant_params, approx_bmm, approx_bmm_ch
 from .error_tables import get_comp_table_NN_v5, get_error_table_NN, load_error_table
 from .quantization.hijacker import QuantizationHijacker
 from .quantization.quantization_manager import QuantizationManager
-from .quantization.base_quantized_classes import QuantizedActivation, QuantizedModule, grad_split_k, sync_ste
+from .quantization.base_quantized_classes import (QuantizedActivation, QuantizedModule, conv_backward, grad_split_k,
+                                                  sync_ste)
 from .quantization.hijacker import activations_set
 from .quantization.quantized_folded_bn import BNFusedHijacker
 from .chain import ChainConsumerMixin
@@ -47,6 +48,13 @@ __all__ = ["QCustomBNConv2dTorch", "QCustomLinearTorch", "QCustomConv2dTorch", "
            "bind_matmul_class",
            "QuantizationHijacker", "BNFusedHijacker", "QuantizationManager",
            "QuantizedActivation", "QuantizedModule", "activations_set"]
+
+
+def _conv_backward_kw(module):
+    """ste_conv2d's keyword for a layer's conv_backward key: none on the default path, which then calls ste_conv2d
+    exactly as it always has."""
+    path = conv_backward(module)
+    return {} if path == "im2col" else {"backward": path}
 
 
 class ApproxOpMixin:
@@ -247,7 +255,7 @@ class ApproxConv2dMixin(ApproxOpMixin, ChainConsumerMixin):
                     out = ste_conv2d(x, weight, lambda xq, wq: approx_conv2d(xq, wq, E, M, a_b, w_bias, r_b, table,
                                                                              **args),
                                      self.stride, self.padding, self.dilation, self.groups,
-                                     split_k=grad_split_k(self))
+                                     split_k=grad_split_k(self), **_conv_backward_kw(self))
                 else:
                     out = approx_conv2d(x.detach(), weight.detach(), E, M, a_b, w_bias, r_b, table, **args)
                 if self._self_check_on():

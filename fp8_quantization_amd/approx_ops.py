@@ -26,6 +26,7 @@ __all__ = ["custom_matmul_vectorize", "approx_matmul", "approx_bmm", "approx_mat
            "make_flags", "make_flags_v5", "fp8_fake_quantize", "bn_act_epilogue", "dense_format", "dense_matmul",
            "dense_conv2d", "grouped_conv2d", "dense_conv2d_fused", "approx_matmul_check", "approx_conv2d_check", "approx_bmm_check",
            "CheckStats", "format_self_check", "SELF_CHECK_LABELS", "fp8_mse_losses", "bn_train", "grad_bmm", "grad_split_auto",
+           "grad_conv2d_input", "grad_conv2d_weight",
            "ste_linear", "ste_bmm", "ste_conv2d", "fp8_fake_quantize_train", "fp8_fake_quantize_backward"]
 
 
@@ -1597,6 +1598,103 @@ class _BmmSTE(torch.autograd.Function):
         return da, db, None, None
 
 
+CONV_BACKWARDS = ("im2col", "implicit")
+
+
+def check_conv_backward(value, what="backward"):
+    """A convolution's backward path: "im2col" (fp8a_im2col + grad_bmm + F.fold) or "implicit" (the implicit-GEMM
+    kernels, grad_conv2d_input / grad_conv2d_weight); anything else is a ValueError naming `what`."""
+    if isinstance(value, str) and value in CONV_BACKWARDS:
+        return value
+    raise ValueError(f"{what} must be one of {CONV_BACKWARDS}, got {value!r}")
+
+
+def _conv_geo(xshape, wshape, stride, padding, dilation, groups):
+    """fp8a_im2col's geometry, then Cout and groups, as the conv-backward entries take it, and dy's shape."""
+    pair = lambda v: (int(v), int(v)) if isinstance(v, int) else tuple(int(t) for t in v)  # noqa: E731
+    (sh, sw), (ph, pw), (dh, dw) = pair(stride), pair(padding), pair(dilation)
+    Bn, Cin, H, W = (int(v) for v in xshape)
+    Cout, Cg, kh, kw = (int(v) for v in wshape)
+    if Cg * int(groups) != Cin:
+        raise AssertionError(f"conv backward: weight {tuple(wshape)} does not fit input {tuple(xshape)}, groups {groups}")
+    Ho, Wo = (H + 2 * ph - dh * (kh - 1) - 1) // sh + 1, (W + 2 * pw - dw * (kw - 1) - 1) // sw + 1
+    return (Bn, Cin, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, int(groups)), (Bn, Cout, Ho, Wo)
+
+
+def _conv_operands(dy, op, dyshape, opshape, out, outshape, who):
+    dy, op = _as_f32(dy).contiguous(), _as_f32(op).contiguous()
+    if not dy.is_cuda or op.device != dy.device:
+        raise RuntimeError("fp8approx kernels need HIP device tensors (no CPU fallback)")
+    if tuple(dy.shape) != tuple(dyshape) or tuple(op.shape) != tuple(opshape):
+        raise AssertionError(f"{who}: dy {tuple(dy.shape)} / operand {tuple(op.shape)}, expected {tuple(dyshape)} / "
+                             f"{tuple(opshape)}")
+    if out is None:
+        out = torch.empty(tuple(outshape), dtype=torch.float32, device=dy.device)
+    elif tuple(out.shape) != tuple(outshape) or out.dtype != torch.float32 or out.device != dy.device or \
+            not out.is_contiguous():
+        raise AssertionError(f"{who}: out must be a contiguous float32 {tuple(outshape)} tensor on {dy.device}")
+    return dy, op, out
+
+
+def grad_conv2d_input(dy, wq, input_shape, stride, padding, dilation, groups, out=None):
+    """The data gradient of y = conv2d(x, wq) without an im2col image (fp8a_grad_conv2d_dgrad,
+    csrc/gemm_grad_conv.h): dX [input_shape] from dy [Bn, Cout, Ho, Wo] (any float32: the three-piece operand) and
+    wq [Cout, Cin / groups, kh, kw] (bf16-exact; anything else is still summed correctly, in fp32).  One launch
+    for any groups; every element of dX is written (+0 where no window reaches); padding contributes nothing."""
+    geo, dyshape = _conv_geo(input_shape, wq.shape, stride, padding, dilation, groups)
+    dy, w, out = _conv_operands(dy, wq, dyshape, wq.shape, out, input_shape, "grad_conv2d_input")
+    L = _lib.load()
+    with _ste_timed("grad_gemm"):
+        rc = L.fp8a_grad_conv2d_dgrad(_lib.dev_ptr(dy), _lib.dev_ptr(w), _lib.dev_ptr(out), *geo,
+                                      _lib.stream_ptr(dy.device))
+    _lib.check(rc, "fp8a_grad_conv2d_dgrad")
+    return out
+
+
+def grad_conv2d_weight(dy, xq, weight_shape, stride, padding, dilation, groups, split_k=1, out=None):
+    """The weight gradient of y = conv2d(xq, w) without an im2col image (fp8a_grad_conv2d_wgrad): dW [weight_shape]
+    from dy and the saved input xq [Bn, Cin, H, W] (bf16-exact), reduced over (image, output pixel).  split_k as
+    grad_bmm's: the reduction in that many parts ("auto": grad_split_auto on (groups, Og, Cg kh kw, Bn Ho Wo)), each
+    stored in a per-call workspace from the caching allocator and added in index order; deterministic."""
+    check_split_k(split_k)
+    geo, dyshape = _conv_geo(xq.shape, weight_shape, stride, padding, dilation, groups)
+    dy, x, out = _conv_operands(dy, xq, dyshape, xq.shape, out, weight_shape, "grad_conv2d_weight")
+    G, Og, Kg = geo[-1], geo[4] // geo[-1], int(weight_shape[1]) * geo[5] * geo[6]
+    if split_k == "auto":
+        split_k = grad_split_auto(G, Og, Kg, dyshape[0] * dyshape[2] * dyshape[3], dy.device)
+    _, nbytes = _lib.grad_conv_wgrad_plan(geo, split_k)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dy.device) if nbytes else None
+    L = _lib.load()
+    with _ste_timed("grad_gemm"):
+        rc = L.fp8a_grad_conv2d_wgrad(_lib.dev_ptr(dy), _lib.dev_ptr(x), _lib.dev_ptr(out), *geo, split_k,
+                                      _lib.dev_ptr(ws) if nbytes else None, nbytes, _lib.stream_ptr(dy.device))
+    _lib.check(rc, "fp8a_grad_conv2d_wgrad")
+    return out
+
+
+class _Conv2dImplicitSTE(torch.autograd.Function):
+    """_Conv2dSTE's forward with the implicit-GEMM backward: grad_conv2d_weight and grad_conv2d_input on the saved
+    operands where they lie.  Transient memory: the split's workspace (at most GRAD_SPLIT_MAX_BYTES under "auto")."""
+
+    @staticmethod
+    def forward(ctx, xq, wq, launch, stride, padding, dilation, groups, split_k):
+        ctx.save_for_backward(xq, wq)
+        ctx.split_k = split_k
+        ctx.geo = (tuple(stride), tuple(padding), tuple(dilation), int(groups))
+        return launch(xq, wq)
+
+    @staticmethod
+    def backward(ctx, dy):
+        xq, wq = ctx.saved_tensors
+        dy = _as_f32(dy).contiguous()  # (once for both products)
+        dx = dw = None
+        if ctx.needs_input_grad[1]:
+            dw = grad_conv2d_weight(dy, xq, wq.shape, *ctx.geo, split_k=ctx.split_k)
+        if ctx.needs_input_grad[0]:
+            dx = grad_conv2d_input(dy, wq, xq.shape, *ctx.geo)
+        return dx, dw, None, None, None, None, None, None
+
+
 class _Conv2dSTE(torch.autograd.Function):
     """y = launch(xq, wq) (the approx convolution, unchanged); backward the exact convolution's gradients on
     the gradient GEMM.  The saved input goes through fp8a_im2col once ([Bn L, Cin kh kw], L = Ho Wo);
@@ -1660,6 +1758,10 @@ def ste_bmm(aq, bq, launch, split_k=1):
     return _BmmSTE.apply(aq, bq, launch, check_split_k(split_k))
 
 
-def ste_conv2d(xq, wq, launch, stride=(1, 1), padding=(0, 0), dilation=(1, 1), groups=1, split_k=1):
-    """launch(xq, wq) -> NCHW y with the straight-through backward (quantized NCHW input and weights)."""
-    return _Conv2dSTE.apply(xq, wq, launch, stride, padding, dilation, groups, check_split_k(split_k))
+def ste_conv2d(xq, wq, launch, stride=(1, 1), padding=(0, 0), dilation=(1, 1), groups=1, split_k=1,
+               backward="im2col"):
+    """launch(xq, wq) -> NCHW y with the straight-through backward (quantized NCHW input and weights).
+    backward: "im2col" (the default: fp8a_im2col, grad_bmm and F.fold) or "implicit" (the implicit-GEMM kernels:
+    no im2col image and no fold, one launch per gradient for any groups)."""
+    fn = _Conv2dImplicitSTE if check_conv_backward(backward) == "implicit" else _Conv2dSTE
+    return fn.apply(xq, wq, launch, stride, padding, dilation, groups, check_split_k(split_k))

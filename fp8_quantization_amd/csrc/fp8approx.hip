@@ -34,6 +34,7 @@
 #include "bn_train.h"
 #include "gemm_bmm.h"
 #include "gemm_grad.h"
+#include "gemm_grad_conv.h"
 
 // (defined with C linkage below; run_gemm launches it too)
 extern "C" __global__ void fq_bias_kernel(fp8a::FqIn fq, float *bias_out, int32_t *ibias_out);
@@ -2205,6 +2206,142 @@ int fp8a_grad_bmm_split(const float *A, const float *B, float *C, int64_t nb, in
     ++g_grad_launches;
     g_grad_tiles += (uint64_t)(a.tiles * nb * S);
     return hip_check("fp8a_grad_bmm_split launch");
+}
+
+// ---- the implicit-GEMM convolution backward (gemm_grad_conv.h)
+// What the three entries check alike in a geometry, under the entry's own name, and the kernels' arguments.
+static int gconv_args(const char *who, int64_t Bn, int64_t Cin, int64_t H, int64_t W, int64_t Cout, int kh, int kw,
+                      int sh, int sw, int ph, int pw, int dh, int dw, int groups, ConvGradArgs &a) {
+    const std::string w = std::string(who) + ": ";
+    if (Bn <= 0 || Cin <= 0 || H <= 0 || W <= 0 || Cout <= 0 || kh <= 0 || kw <= 0 || sh <= 0 || sw <= 0 || dh <= 0 ||
+        dw <= 0 || groups <= 0)
+        return fail(FP8A_EINVAL, w + "non-positive size");
+    if (ph < 0 || pw < 0) return fail(FP8A_EINVAL, w + "negative padding");
+    if (Cin % groups != 0 || Cout % groups != 0)
+        return fail(FP8A_EINVAL, w + "groups does not divide both channel counts");
+    const int64_t lim = 0x7FFFFFFFll;
+    // (every term bounded before it enters a product: no int64 overflow below)
+    if (Bn > lim || Cin > lim || H > lim || W > lim || Cout > lim || kh > (1 << 15) || kw > (1 << 15) || sh > (1 << 15) ||
+        sw > (1 << 15) || dh > (1 << 15) || dw > (1 << 15) || ph > (1 << 20) || pw > (1 << 20))
+        return fail(FP8A_EINVAL, w + "index range beyond the 32-bit in-tile arithmetic");
+    const int64_t Ho = (H + 2 * (int64_t)ph - (int64_t)dh * (kh - 1) - 1) / sh + 1;
+    const int64_t Wo = (W + 2 * (int64_t)pw - (int64_t)dw * (kw - 1) - 1) / sw + 1;
+    if (H + 2 * (int64_t)ph < (int64_t)dh * (kh - 1) + 1 || W + 2 * (int64_t)pw < (int64_t)dw * (kw - 1) + 1)
+        return fail(FP8A_EINVAL, w + "empty output");
+    // the padded extents and the three tensors' element counts hold in an int, with room for a tile past the end
+    const int64_t Cg = Cin / groups, khw = (int64_t)kh * kw;
+    if (H * W > lim / Cin / Bn || Ho * Wo > lim / Cout / Bn || Cg * khw > lim / Cout ||
+        (H + 2 * (int64_t)ph + (int64_t)dh * kh) * (W + 2 * (int64_t)pw + (int64_t)dw * kw) > lim / 2)
+        return fail(FP8A_EINVAL, w + "index range beyond the 32-bit in-tile arithmetic");
+    memset(&a, 0, sizeof(a));
+    a.Bn = (int)Bn; a.Cin = (int)Cin; a.H = (int)H; a.W = (int)W; a.Cout = (int)Cout; a.Ho = (int)Ho; a.Wo = (int)Wo;
+    a.kh = kh; a.kw = kw; a.sh = sh; a.sw = sw; a.ph = ph; a.pw = pw; a.dh = dh; a.dw = dw;
+    a.G = groups; a.Cg = (int)Cg; a.Og = (int)(Cout / groups);
+    auto gcd = [](int u, int v) {
+        while (v) { const int t = u % v; u = v; v = t; }
+        return u;
+    };
+    a.py = sh / gcd(sh, dh);
+    a.px = sw / gcd(sw, dw);
+    a.K = (uint32_t)(Bn * Ho * Wo);
+    return FP8A_OK;
+}
+
+// dense spans [p, p + n) and [q, q + m) that meet
+static bool gconv_meet(const float *p, int64_t n, const float *q, int64_t m) { return p < q + m && q < p + n; }
+
+int fp8a_grad_conv2d_dgrad(const float *dy, const float *w, float *dx, int64_t Bn, int64_t Cin, int64_t H, int64_t W,
+                           int64_t Cout, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw, int groups,
+                           fp8a_stream_t stream) {
+    const char *const who = "fp8a_grad_conv2d_dgrad";
+    if (!dy || !w || !dx) return fail(FP8A_EINVAL, std::string(who) + ": null pointer");
+    ConvGradArgs a;
+    const int rc = gconv_args(who, Bn, Cin, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, groups, a);
+    if (rc) return rc;
+    const int64_t ndx = Bn * Cin * H * W, ndy = Bn * Cout * a.Ho * a.Wo, nw = Cout * a.Cg * kh * kw;
+    if (gconv_meet(dx, ndx, dy, ndy) || gconv_meet(dx, ndx, w, nw))
+        return fail(FP8A_EINVAL, std::string(who) + ": dx overlaps an operand");
+    // row tiles of class (0, 0), the largest
+    const int64_t rows0 = ((H + sh - 1) / sh) * ((W + sw - 1) / sw);
+    a.num_mt = (int)((rows0 + GR_T - 1) / GR_T);
+    a.num_nt = (a.Cg + GR_T - 1) / GR_T;
+    const int64_t per = (int64_t)a.num_mt * a.num_nt * sh * sw;
+    if (per > 0x7FFFFFFFll / Bn / groups) return fail(FP8A_EINVAL, std::string(who) + ": more than 2^31 - 1 blocks");
+    a.dy = dy; a.op = w; a.out = dx;
+    a.recount = grad_recount_ptr();
+    if (a.recount == nullptr) return fail(FP8A_EHIP, std::string(who) + ": the recomputed-tile counter's address");
+    const int64_t blocks = per * Bn * groups;
+    launch_conv_dgrad(a, (unsigned)blocks, (hipStream_t)stream);
+    ++g_grad_launches;
+    g_grad_tiles += (uint64_t)blocks;
+    return hip_check("fp8a_grad_conv2d_dgrad launch");
+}
+
+// the weight gradient's tiles and split plan; FP8A_OK or the block-count refusal
+static int gconv_wgrad_plan(const char *who, ConvGradArgs &a, int64_t splits, int64_t &per, int64_t &S, int64_t &need) {
+    if (splits < 1) return fail(FP8A_EINVAL, std::string(who) + ": splits below 1");
+    a.num_mt = (a.Og + GR_T - 1) / GR_T;
+    a.num_nt = (int)(((int64_t)a.Cg * a.kh * a.kw + GR_T - 1) / GR_T);
+    grad_split_plan((int64_t)a.K, splits, per, S);
+    const int64_t tiles = (int64_t)a.num_mt * a.num_nt;
+    if (tiles > 0x7FFFFFFFll / a.G / S) return fail(FP8A_EINVAL, std::string(who) + ": more than 2^31 - 1 blocks");
+    need = S > 1 ? S * a.G * tiles * (GR_T * GR_T) * (int64_t)sizeof(float) : 0;
+    return FP8A_OK;
+}
+
+int fp8a_grad_conv2d_wgrad_workspace_size(int64_t Bn, int64_t Cin, int64_t H, int64_t W, int64_t Cout, int kh, int kw,
+                                          int sh, int sw, int ph, int pw, int dh, int dw, int groups, int64_t splits,
+                                          int64_t *eff_splits, int64_t *bytes) {
+    const char *const who = "fp8a_grad_conv2d_wgrad_workspace_size";
+    if (!eff_splits || !bytes) return fail(FP8A_EINVAL, std::string(who) + ": null pointer");
+    ConvGradArgs a;
+    int rc = gconv_args(who, Bn, Cin, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, groups, a);
+    if (rc) return rc;
+    int64_t per, S, need;
+    rc = gconv_wgrad_plan(who, a, splits, per, S, need);
+    if (rc) return rc;
+    *eff_splits = S;
+    *bytes = need;
+    return FP8A_OK;
+}
+
+int fp8a_grad_conv2d_wgrad(const float *dy, const float *x, float *dwgt, int64_t Bn, int64_t Cin, int64_t H, int64_t W,
+                           int64_t Cout, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw, int groups,
+                           int64_t splits, void *workspace, int64_t workspace_bytes, fp8a_stream_t stream) {
+    const char *const who = "fp8a_grad_conv2d_wgrad";
+    if (!dy || !x || !dwgt) return fail(FP8A_EINVAL, std::string(who) + ": null pointer");
+    ConvGradArgs a;
+    int rc = gconv_args(who, Bn, Cin, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, groups, a);
+    if (rc) return rc;
+    int64_t per, S, need;
+    rc = gconv_wgrad_plan(who, a, splits, per, S, need);
+    if (rc) return rc;
+    const int64_t nx = Bn * Cin * H * W, ndy = Bn * Cout * a.Ho * a.Wo, nw = Cout * a.Cg * kh * kw;
+    if (gconv_meet(dwgt, nw, dy, ndy) || gconv_meet(dwgt, nw, x, nx))
+        return fail(FP8A_EINVAL, std::string(who) + ": dw overlaps an operand");
+    if (S > 1) {
+        if (!workspace) return fail(FP8A_EINVAL, std::string(who) + ": null workspace");
+        if (workspace_bytes < need)
+            return fail(FP8A_EINVAL, std::string(who) + ": workspace of " + std::to_string(workspace_bytes) + " bytes, " +
+                                         std::to_string(need) + " needed");
+        if (((uintptr_t)workspace & 15u) != 0) return fail(FP8A_EINVAL, std::string(who) + ": workspace not 16-byte aligned");
+        const float *const Wk = (const float *)workspace;
+        const int64_t ew = need / (int64_t)sizeof(float);
+        if (gconv_meet(Wk, ew, dy, ndy) || gconv_meet(Wk, ew, x, nx) || gconv_meet(Wk, ew, dwgt, nw))
+            return fail(FP8A_EINVAL, std::string(who) + ": the workspace overlaps dy, x or dw");
+    }
+    a.dy = dy; a.op = x; a.out = dwgt;
+    a.recount = grad_recount_ptr();
+    if (a.recount == nullptr) return fail(FP8A_EHIP, std::string(who) + ": the recomputed-tile counter's address");
+    GradArgs r;  // dW [G][Og][Cg kh kw] as the reduce pass's C
+    memset(&r, 0, sizeof(r));
+    r.C = dwgt; r.M = a.Og; r.N = (int64_t)a.Cg * kh * kw;
+    r.sc_i = r.M * r.N; r.sc_m = r.N; r.sc_n = 1;
+    r.num_mt = a.num_mt; r.tiles = (int64_t)a.num_mt * a.num_nt;
+    launch_conv_wgrad(a, r, S, per, (float *)workspace, (hipStream_t)stream);
+    ++g_grad_launches;
+    g_grad_tiles += (uint64_t)(r.tiles * groups * S);
+    return hip_check("fp8a_grad_conv2d_wgrad launch");
 }
 
 int fp8a_grad_stats(uint64_t out[3], int reset) {

@@ -47,6 +47,8 @@ void launch_grad(const GradArgs &a, dim3 grid, hipStream_t s);
 // the split along K: gemm_grad_split_kernel over tiles nb S blocks into ws (S dense [nb][tiles][64][64] fp32
 // images), then grad_reduce_kernel over (tiles nb, 16) blocks; per: stages per part
 void launch_grad_split(const GradArgs &a, int64_t nb, int64_t S, int64_t per, float *ws, hipStream_t s);
+// the reduce pass alone, over a workspace another product pass filled in the same layout (gemm_grad_conv.h)
+void launch_grad_reduce(const GradArgs &a, int64_t nb, int64_t S, const float *ws, hipStream_t s);
 unsigned long long *grad_recount_ptr();  // nullptr: the address query failed
 int grad_recount_read(unsigned long long *v, bool reset);
 
@@ -54,7 +56,8 @@ constexpr int GR_T = 64;          // tile edge
 constexpr int GR_BK = 32;         // k per stage = one MFMA K-step
 constexpr int GR_RS = 2 * GR_BK + 16;  // LDS row stride, bytes (bf16 rows of k)
 
-#if FP8A_OWN_GRAD
+// (the fragment types and the two operand tests are shared with gemm_grad_conv.h; the kernels below are k_grad.hip's)
+#if FP8A_OWN_GRAD || FP8A_OWN_GRAD_CONV
 typedef __bf16 gr_v8bf __attribute__((ext_vector_type(8)));
 typedef float gr_v4f __attribute__((ext_vector_type(4)));
 
@@ -76,7 +79,9 @@ __device__ __forceinline__ bool gr_split(float x, uint32_t &h0, uint32_t &h1, ui
     h2 = __float_as_uint(r2) >> 16;
     return ok;
 }
+#endif  // FP8A_OWN_GRAD || FP8A_OWN_GRAD_CONV
 
+#if FP8A_OWN_GRAD
 // One workgroup's work, shared by the two product kernels.  SPLIT = false is gemm_grad_kernel: block = (tile,
 // item), the k range [0, K), the tile stored through C's strides.  SPLIT = true is gemm_grad_split_kernel: block =
 // (tile, item, part), part slowest; part s owns the stages [s per, (s + 1) per) -- kper = 32 per flat k -- runs the

@@ -36,4 +36,8 @@ void launch_grad_split(const GradArgs &a, int64_t nb, int64_t S, int64_t per, fl
     grad_reduce_kernel<<<dim3((unsigned)(a.tiles * nb), GR_T / 4), 256, 0, s>>>(a, ws, nb, (int)S);
 }
 
+void launch_grad_reduce(const GradArgs &a, int64_t nb, int64_t S, const float *ws, hipStream_t s) {
+    grad_reduce_kernel<<<dim3((unsigned)(a.tiles * nb), GR_T / 4), 256, 0, s>>>(a, ws, nb, (int)S);
+}
+
 }  // namespace fp8a

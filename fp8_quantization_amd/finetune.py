@@ -4,7 +4,8 @@ quantizer masks, the exact product's gradients on the gradient GEMM fp8a_grad_bm
 
     python -m fp8_quantization_amd.finetune --synthetic 64 --arch resnet18|mobilenet_v2|vit_b16 \
         --steps 10 --lr 1e-3 [--batch-size 64] [--momentum 0.9] [--approx-attention] \
-        [--learn-ranges [--range-lr 1e-4]] [--grad-split-k N|auto] [--seed 0]
+        [--learn-ranges [--range-lr 1e-4]] [--grad-split-k N|auto] [--conv-backward im2col|implicit]
+        [--seed 0]
 
 A driver, not a trainer (no schedule, checkpoints or augmentation): it calibrates and fixes the FP8 ranges as
 the validation driver does (imagenet.py: estimate_ranges over --num-est-batches batches, fix_ranges), keeps the
@@ -22,6 +23,8 @@ clamp a range: a maxval that is not finite or not positive after a step ends the
 --grad-split-k: every gradient GEMM of the backward splits its reduction along K into N parts, or into what
 approx_ops.grad_split_auto picks per product ("auto"), and adds the parts in a fixed order:
 custom_approx_params["grad_split_k"]; default 1, off.  grad_gemm_ms then includes the reduce passes.
+--conv-backward implicit: the convolutions' backward on the implicit-GEMM kernels:
+custom_approx_params["conv_backward"]; no im2col image and no fold, so im2col_fold_ms stays 0; default im2col.
 Data: --synthetic N random images and labels, or <images-dir>/train as imagenet.py reads it.
 """
 import argparse
@@ -72,6 +75,8 @@ def parse(argv=None):
     ap.add_argument("--range-lr", type=float, default=None, help="learning rate of the maxvals (default: --lr)")
     ap.add_argument("--grad-split-k", type=_split_k, default=1, metavar="{N,auto}",
                     help="split the gradient GEMMs' reductions along K: a part count, or auto (default 1: off)")
+    ap.add_argument("--conv-backward", default="im2col", choices=list(approx_ops.CONV_BACKWARDS),
+                    help="the convolutions' backward: the im2col image + fold, or the implicit-GEMM kernels")
     ap.add_argument("--output", default=None, help="also write the step records (a JSON list) here")
     return ap.parse_args(argv)
 
@@ -85,6 +90,8 @@ def approx_cfg(args):
         cfg["learn_maxval"] = True
     if getattr(args, "grad_split_k", 1) != 1:
         cfg["grad_split_k"] = args.grad_split_k
+    if getattr(args, "conv_backward", "im2col") != "im2col":
+        cfg["conv_backward"] = args.conv_backward
     return cfg
 
 

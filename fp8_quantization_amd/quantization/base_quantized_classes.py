@@ -74,6 +74,15 @@ def grad_split_k(module):
                          "custom_approx_params['grad_split_k']")
 
 
+def conv_backward(module):
+    """custom_approx_params['conv_backward'] of a layer: the path of a convolution's straight-through backward
+    (approx_ops.ste_conv2d's backward).  Absent or "im2col": the im2col image, grad_bmm and F.fold; "implicit": the
+    implicit-GEMM kernels; anything else raises ValueError (at construction too).  Nothing without ste_backward."""
+    from ..approx_ops import check_conv_backward
+    return check_conv_backward((getattr(module, "custom_approx_params", None) or {}).get("conv_backward", "im2col"),
+                               "custom_approx_params['conv_backward']")
+
+
 def _version5(module):
     return (getattr(module, "custom_approx_params", None) or {}).get("approx_version", 9) == 5
 
@@ -90,6 +99,7 @@ class QuantizedModule(nn.Module):
         kwargs.pop("act_quant_dict", None)
         self.custom_approx_params = kwargs.pop("custom_approx_params", None)
         grad_split_k(self)  # (a value the backward cannot take raises here, not in the first backward)
+        conv_backward(self)
         self.run_method = kwargs.pop("run_method", None) or dict(_DEFAULT_RUN_METHOD)
         self.approx_flag = self.run_method["approx_flag"]
         self.quantize_after_mult_and_add = self.run_method["quantize_after_mult_and_add"]

@@ -368,6 +368,39 @@ int fp8a_grad_bmm_split(const float *A, const float *B, float *C,
                         int64_t splits, void *workspace, int64_t workspace_bytes, fp8a_stream_t stream);
 
 /*
+ * The implicit-GEMM convolution backward: the straight-through backward's two gradients of
+ * y = conv2d(x, w) read from dense fp32 NCHW / OIHW tensors where they lie -- no im2col image, no fold -- with
+ * the arithmetic of fp8a_grad_bmm: dy is the three-piece operand, the saved forward operand (w or x, bf16-exact
+ * on its FP8 grid) the truncated one, a workgroup that staged a lost element recomputes its own tile (or tile
+ * and part) in fp32 in the same k order.  The geometry is fp8a_im2col's, then Cout and groups; dy is
+ * [Bn, Cout, Ho, Wo] with Ho = (H + 2 ph - dh (kh - 1) - 1) / sh + 1 (Wo likewise).
+ *   dx[b, g Cg + c, iy, ix]  = sum_{o, ky, kx} dy[b, g Og + o, oy, ox] w[g Og + o, c, ky, kx],
+ *                              oy = (iy + ph - ky dh) / sh where exact and in range (ox likewise); k order (ky, kx, o)
+ *   dw[g Og + o, c, ky, kx] = sum_{b, oy, ox} dy[b, g Og + o, oy, ox] x[b, g Cg + c, oy sh - ph + ky dh, ox sw - pw + kx dw];
+ *                              k order (b, oy, ox)
+ * Padding positions and taps that reach no output contribute nothing (they are not 0 * w).  fp8a_grad_conv2d_dgrad
+ * is one launch for any groups and writes every element of dx (+0 where nothing contributes).
+ * fp8a_grad_conv2d_wgrad splits K = Bn Ho Wo by fp8a_grad_bmm_split's plan into S parts, stored dense in the
+ * workspace (S groups tiles 4096 4 bytes, fp8a_grad_conv2d_wgrad_workspace_size; no HIP call) and added in index
+ * order by the same reduce pass; S == 1 is one launch and takes no workspace.  Deterministic: a fixed k order per
+ * output, no float atomics.  Every argument check runs before any HIP call: null pointers, non-positive sizes,
+ * groups not dividing both channel counts, an empty output, tensors or padded planes beyond the 32-bit in-tile
+ * index arithmetic (2^31 - 1 elements), the output over an operand, and the workspace null, too small, not
+ * 16-byte aligned or over a tensor.  fp8a_grad_stats counts a call of either entry as one launch and its
+ * product-pass workgroups as tiles.
+ */
+int fp8a_grad_conv2d_dgrad(const float *dy, const float *w, float *dx, int64_t Bn, int64_t Cin, int64_t H,
+                           int64_t W, int64_t Cout, int kh, int kw, int sh, int sw, int ph, int pw,
+                           int dh, int dw, int groups, fp8a_stream_t stream);
+int fp8a_grad_conv2d_wgrad_workspace_size(int64_t Bn, int64_t Cin, int64_t H, int64_t W, int64_t Cout,
+                                          int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw,
+                                          int groups, int64_t splits, int64_t *eff_splits, int64_t *bytes);
+int fp8a_grad_conv2d_wgrad(const float *dy, const float *x, float *dwgt, int64_t Bn, int64_t Cin, int64_t H,
+                           int64_t W, int64_t Cout, int kh, int kw, int sh, int sw, int ph, int pw,
+                           int dh, int dw, int groups, int64_t splits, void *workspace,
+                           int64_t workspace_bytes, fp8a_stream_t stream);
+
+/*
  * Per-product terms (debug / parity): T[m, k, n] = the value the reference sums at v9:113.
  * Same arguments as fp8a_matmul; T is dense [M][K][N].
  */

@@ -13,6 +13,10 @@ Without --split-k the run and its lines are as they always were (the eight shape
 shapes then also hold the weight gradients of ResNet-18's conv1 (64 x 147, K = 64 x 12544) and layer4.1.conv2
 (512 x 4608, K = 64 x 49), and there is one line per shape and value, with the splits "auto" resolved to, the
 product pass's workgroups and the time relative to the latest split_k = 1 of the same shape.
+--conv: the convolution backward instead, at batch 64 and split_k = auto: per layer the
+implicit-GEMM data and weight gradients (grad_conv2d_input / grad_conv2d_weight) against the default path's two
+halves on the same operands -- fp8a_im2col + grad_bmm for dW, grad_bmm + F.fold for dX, as _Conv2dSTE.backward
+issues them -- with the largest |difference| between the two paths over the largest |value|.
 """
 import argparse
 import json
@@ -86,6 +90,53 @@ def shapes(sweep=False):
         yield wgrad("r18.layer4.1.conv2 wgrad", 512, 4608, 49)
 
 
+# (name, Cin, H, Cout, k, stride, pad, groups) at batch 64
+CONV_LAYERS = [("r18.conv1", 3, 224, 64, 7, 2, 3, 1), ("r18.layer1.0.conv1", 64, 56, 64, 3, 1, 1, 1),
+               ("r18.layer2.0.conv1", 64, 56, 128, 3, 2, 1, 1), ("r18.layer2.0.downsample", 64, 56, 128, 1, 2, 0, 1),
+               ("r18.layer2.conv2", 128, 28, 128, 3, 1, 1, 1), ("r18.layer4.1.conv2", 512, 7, 512, 3, 1, 1, 1),
+               ("mbv2.dw3x3 s1", 144, 56, 144, 3, 1, 1, 144), ("mbv2.dw3x3 s2", 144, 56, 144, 3, 2, 1, 144)]
+
+
+def conv_mode(a):
+    import torch.nn.functional as F
+    from fp8_quantization_amd.approx_ops import _Conv2dSTE, grad_conv2d_input, grad_conv2d_weight
+
+    class Ctx:  # _Conv2dSTE.backward's context: one half of the default backward per call
+        split_k = "auto"
+
+    g = torch.Generator(device=DEV).manual_seed(0)
+    lines = []
+    for name, cin, hw, cout, k, s, pad, groups in CONV_LAYERS:
+        x = bf16_exact(torch.randn((64, cin, hw, hw), device=DEV, generator=g))
+        w = bf16_exact(torch.randn((cout, cin // groups, k, k), device=DEV, generator=g))
+        geo = ((s, s), (pad, pad), (1, 1), groups)
+        dy = torch.randn(F.conv2d(x, w, None, *geo).shape, device=DEV, generator=g)
+
+        def default(which):
+            ctx = Ctx()
+            ctx.saved_tensors, ctx.geo = (x, w), geo
+            ctx.needs_input_grad = (which == 0, which == 1)
+            return _Conv2dSTE.backward(ctx, dy)[which]
+        calls = {"dgrad": (lambda: grad_conv2d_input(dy, w, x.shape, *geo), lambda: default(0)),
+                 "wgrad": (lambda: grad_conv2d_weight(dy, x, w.shape, *geo, split_k="auto"), lambda: default(1))}
+        rec = dict(layer=name, batch=64)
+        for what, (new, old) in calls.items():
+            _lib.grad_stats(reset=True)
+            got, ref = new(), old()
+            rec[what + "_recomputed"] = _lib.grad_stats(reset=True)["recomputed"]
+            rec[what + "_max_diff_over_max"] = float((got - ref).abs().max() / ref.abs().max())
+            del got, ref
+            rec[what + "_implicit_ms"] = med_ms(new, a.iters, a.warmup)
+            rec[what + "_im2col_ms"] = med_ms(old, a.iters, a.warmup)
+        rec["implicit_ms"] = rec["dgrad_implicit_ms"] + rec["wgrad_implicit_ms"]
+        rec["im2col_ms"] = rec["dgrad_im2col_ms"] + rec["wgrad_im2col_ms"]
+        lines.append(rec)
+        print(json.dumps(rec), flush=True)
+        del x, w, dy
+        torch.cuda.empty_cache()
+    return lines
+
+
 def split_list(v):
     out = [x if x == "auto" else int(x) for x in v.split(",")]
     if not out or any(x != "auto" and x < 1 for x in out):
@@ -98,11 +149,12 @@ def main():
     ap.add_argument("--iters", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--split-k", type=split_list, default=None, help="grad_bmm's split_k: one value or a comma list")
+    ap.add_argument("--conv", action="store_true", help="the convolution backward: implicit GEMM against im2col + fold")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     torch.backends.cuda.matmul.allow_tf32 = False
-    lines = []
-    for name, ours, theirs, macs, (nb, M, N, K) in shapes(sweep=a.split_k is not None):
+    lines = conv_mode(a) if a.conv else []
+    for name, ours, theirs, macs, (nb, M, N, K) in ([] if a.conv else shapes(sweep=a.split_k is not None)):
         t_torch = t_one = None
         for sk in a.split_k or [1]:
             _lib.grad_stats(reset=True)
