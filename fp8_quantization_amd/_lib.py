@@ -32,6 +32,7 @@ SYMBOLS = ("fp8a_version", "fp8a_last_error", "fp8a_fallback_stats", "fp8a_path_
            "fp8a_bmm_check_workspace_size", "fp8a_bmm_check", "fp8a_grad_bmm", "fp8a_grad_stats",
            "fp8a_grad_bmm_split_workspace_size", "fp8a_grad_bmm_split",
            "fp8a_grad_conv2d_dgrad", "fp8a_grad_conv2d_wgrad_workspace_size", "fp8a_grad_conv2d_wgrad",
+           "fp8a_grad_dwconv2d_dgrad", "fp8a_grad_dwconv2d_wgrad_workspace_size", "fp8a_grad_dwconv2d_wgrad",
            "fp8a_fq_train_workspace_size", "fp8a_fq_train_forward", "fp8a_fq_train_backward")
 
 _lib = None
@@ -130,6 +131,9 @@ def load():
         "fp8a_grad_conv2d_dgrad": ([P, P, P] + [I64] * 5 + [I] * 9 + [P], I),
         "fp8a_grad_conv2d_wgrad_workspace_size": ([I64] * 5 + [I] * 9 + [I64, P, P], I),
         "fp8a_grad_conv2d_wgrad": ([P, P, P] + [I64] * 5 + [I] * 9 + [I64, P, I64, P], I),
+        "fp8a_grad_dwconv2d_dgrad": ([P, P, P] + [I64] * 4 + [I] * 8 + [P], I),
+        "fp8a_grad_dwconv2d_wgrad_workspace_size": ([I64] * 4 + [I] * 8 + [I64, P, P], I),
+        "fp8a_grad_dwconv2d_wgrad": ([P, P, P] + [I64] * 4 + [I] * 8 + [I64, P, I64, P], I),
         "fp8a_fq_train_workspace_size": ([I64, I64], SZ),
         "fp8a_fq_train_forward": ([P, I64, I64, P, I, I, I, P, P, P, P, P], I),
         "fp8a_fq_train_backward": ([P, P, I64, I64, I, P, P, P, SZ, P], I),
@@ -300,6 +304,17 @@ def grad_conv_wgrad_plan(geo, splits):
     S, nbytes = ctypes.c_int64(0), ctypes.c_int64(0)
     check(L.fp8a_grad_conv2d_wgrad_workspace_size(*geo, splits, ctypes.byref(S), ctypes.byref(nbytes)),
           "fp8a_grad_conv2d_wgrad_workspace_size")
+    return int(S.value), int(nbytes.value)
+
+
+def grad_dwconv_wgrad_plan(geo, splits):
+    """fp8a_grad_dwconv2d_wgrad_workspace_size: (S, bytes) of the depthwise weight gradient of the geometry geo =
+    (Bn, C, H, W, kh, kw, sh, sw, ph, pw, dh, dw) split into `splits` parts along its Bn Ho output rows.  No device
+    call."""
+    L = load()
+    S, nbytes = ctypes.c_int64(0), ctypes.c_int64(0)
+    check(L.fp8a_grad_dwconv2d_wgrad_workspace_size(*geo, splits, ctypes.byref(S), ctypes.byref(nbytes)),
+          "fp8a_grad_dwconv2d_wgrad_workspace_size")
     return int(S.value), int(nbytes.value)
 
 

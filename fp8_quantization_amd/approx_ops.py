@@ -26,7 +26,7 @@ __all__ = ["custom_matmul_vectorize", "approx_matmul", "approx_bmm", "approx_mat
            "make_flags", "make_flags_v5", "fp8_fake_quantize", "bn_act_epilogue", "dense_format", "dense_matmul",
            "dense_conv2d", "grouped_conv2d", "dense_conv2d_fused", "approx_matmul_check", "approx_conv2d_check", "approx_bmm_check",
            "CheckStats", "format_self_check", "SELF_CHECK_LABELS", "fp8_mse_losses", "bn_train", "grad_bmm", "grad_split_auto",
-           "grad_conv2d_input", "grad_conv2d_weight",
+           "grad_conv2d_input", "grad_conv2d_weight", "grad_dwconv2d_input", "grad_dwconv2d_weight",
            "ste_linear", "ste_bmm", "ste_conv2d", "fp8_fake_quantize_train", "fp8_fake_quantize_backward"]
 
 
@@ -1598,12 +1598,14 @@ class _BmmSTE(torch.autograd.Function):
         return da, db, None, None
 
 
-CONV_BACKWARDS = ("im2col", "implicit")
+CONV_BACKWARDS = ("im2col", "implicit", "depthwise")
 
 
 def check_conv_backward(value, what="backward"):
-    """A convolution's backward path: "im2col" (fp8a_im2col + grad_bmm + F.fold) or "implicit" (the implicit-GEMM
-    kernels, grad_conv2d_input / grad_conv2d_weight); anything else is a ValueError naming `what`."""
+    """A convolution's backward path: "im2col" (fp8a_im2col + grad_bmm + F.fold), "implicit" (the implicit-GEMM
+    kernels, grad_conv2d_input / grad_conv2d_weight) or "depthwise" (implicit, with the direct kernels
+    grad_dwconv2d_input / grad_dwconv2d_weight where groups == Cin == Cout); anything else is a ValueError naming
+    `what`."""
     if isinstance(value, str) and value in CONV_BACKWARDS:
         return value
     raise ValueError(f"{what} must be one of {CONV_BACKWARDS}, got {value!r}")
@@ -1695,6 +1697,98 @@ class _Conv2dImplicitSTE(torch.autograd.Function):
         return dx, dw, None, None, None, None, None, None
 
 
+# grad_dw_split_auto's rule: the depthwise weight gradient has one workgroup per (channel, part);
+# split its Bn Ho output rows until C S reaches GRAD_SPLIT_BLOCKS_PER_CU workgroups per compute unit, never below
+# GRAD_DW_MIN_ROWS rows per part.  From profiles/dw_backward/split_sweep.jsonl (tools/grad_bench.py --conv --dw-splits
+# 1,2,4,...,256,auto on one MI355X, 256 CUs, batch 64, median of 15; ms at split 1 -> the best fixed split, rows per part
+# there):
+#   3 x 3 s1, 144 ch, 56 x 56 (3584 rows)   0.939 -> 0.163 at 32 (112 rows; 64: 0.166; 256, 14 rows: 0.224)
+#   3 x 3 s2, 144 ch, 56 x 56 (1792 rows)   0.461 -> 0.108 at 64 (28 rows; 128, 14 rows: 0.128; 256, 7 rows: 0.180)
+#   3 x 3 s1, 576 ch, 14 x 14 (896 rows)    0.164 -> 0.099 at 16 (56 rows; 32, 28 rows: 0.111; 64, 14 rows: 0.144)
+#   3 x 3 s1, 960 ch, 7 x 7 (448 rows)      0.095 -> 0.082 at 4 (112 rows; 8: 0.082; 16, 28 rows: 0.094; 32: 0.118)
+# Every shape is within 15 % of its best down to 28 rows per part and loses 20 - 45 % at 14: 32 is the floor.  At
+# these four shapes the workgroup target binds first (auto = 15, 15, 4, 3 parts: 0.191, 0.143, 0.108, 0.090 ms, 10 -
+# 33 % above the best fixed split): this kernel's small workgroups keep gaining past 8 per compute unit, and a target
+# of its own is what would close that; the floor is what keeps a short reduction (few images, small planes) unsplit.
+GRAD_DW_MIN_ROWS = 32
+
+
+def grad_dw_split_auto(C, rows, device):
+    """The number of parts grad_dwconv2d_weight(..., split_k="auto") asks for on C channels of `rows` = Bn Ho output
+    rows: 1 when C workgroups already reach GRAD_SPLIT_BLOCKS_PER_CU per compute unit of `device`; else as many as
+    reach it, with at least GRAD_DW_MIN_ROWS rows per part."""
+    target = GRAD_SPLIT_BLOCKS_PER_CU * torch.cuda.get_device_properties(device).multi_processor_count
+    if C <= 0 or C >= target:
+        return 1
+    return max(1, min(-(-target // C), rows // GRAD_DW_MIN_ROWS))
+
+
+def _dwconv_geo(xshape, wshape, stride, padding, dilation, who):
+    """The depthwise entries' geometry (Bn, C, H, W, kh, kw, sh, sw, ph, pw, dh, dw) and dy's shape."""
+    if len(wshape) != 4 or int(wshape[0]) != int(xshape[1]) or int(wshape[1]) != 1:
+        raise AssertionError(f"{who}: weight {tuple(wshape)} is not [C, 1, kh, kw] for input {tuple(xshape)}")
+    geo, dyshape = _conv_geo(xshape, wshape, stride, padding, dilation, int(xshape[1]))
+    return geo[:4] + geo[5:13], dyshape
+
+
+def grad_dwconv2d_input(dy, wq, input_shape, stride, padding, dilation, out=None):
+    """The data gradient of a depthwise y = conv2d(x, wq, groups=C) by the direct kernel (fp8a_grad_dwconv2d_dgrad,
+    csrc/gemm_grad_dw.h): dX [input_shape] from dy [Bn, C, Ho, Wo] and wq [C, 1, kh, kw], any float32, one fp32 fma
+    per term.  One launch; every element of dX is written (+0 where no window reaches); padding contributes nothing."""
+    geo, dyshape = _dwconv_geo(input_shape, wq.shape, stride, padding, dilation, "grad_dwconv2d_input")
+    dy, w, out = _conv_operands(dy, wq, dyshape, wq.shape, out, input_shape, "grad_dwconv2d_input")
+    L = _lib.load()
+    with _ste_timed("grad_gemm"):
+        rc = L.fp8a_grad_dwconv2d_dgrad(_lib.dev_ptr(dy), _lib.dev_ptr(w), _lib.dev_ptr(out), *geo,
+                                        _lib.stream_ptr(dy.device))
+    _lib.check(rc, "fp8a_grad_dwconv2d_dgrad")
+    return out
+
+
+def grad_dwconv2d_weight(dy, xq, weight_shape, stride, padding, dilation, split_k=1, out=None):
+    """The weight gradient of a depthwise y = conv2d(xq, w, groups=C) by the direct kernel
+    (fp8a_grad_dwconv2d_wgrad): dW [C, 1, kh, kw] from dy and the saved input xq [Bn, C, H, W], reduced over (image,
+    output pixel).  split_k: 1, an int >= 2 or "auto" (grad_dw_split_auto): the Bn Ho output rows in that many parts,
+    each part's sums stored in a per-call workspace from the caching allocator and added in index order;
+    deterministic."""
+    check_split_k(split_k)
+    geo, dyshape = _dwconv_geo(xq.shape, weight_shape, stride, padding, dilation, "grad_dwconv2d_weight")
+    dy, x, out = _conv_operands(dy, xq, dyshape, xq.shape, out, weight_shape, "grad_dwconv2d_weight")
+    if split_k == "auto":
+        split_k = grad_dw_split_auto(geo[1], dyshape[0] * dyshape[2], dy.device)
+    _, nbytes = _lib.grad_dwconv_wgrad_plan(geo, split_k)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dy.device) if nbytes else None
+    L = _lib.load()
+    with _ste_timed("grad_gemm"):
+        rc = L.fp8a_grad_dwconv2d_wgrad(_lib.dev_ptr(dy), _lib.dev_ptr(x), _lib.dev_ptr(out), *geo, split_k,
+                                        _lib.dev_ptr(ws) if nbytes else None, nbytes, _lib.stream_ptr(dy.device))
+    _lib.check(rc, "fp8a_grad_dwconv2d_wgrad")
+    return out
+
+
+class _Conv2dDepthwiseSTE(torch.autograd.Function):
+    """_Conv2dSTE's forward with the direct depthwise backward (groups == Cin == Cout): grad_dwconv2d_weight and
+    grad_dwconv2d_input on the saved operands where they lie."""
+
+    @staticmethod
+    def forward(ctx, xq, wq, launch, stride, padding, dilation, groups, split_k):
+        ctx.save_for_backward(xq, wq)
+        ctx.split_k = split_k
+        ctx.geo = (tuple(stride), tuple(padding), tuple(dilation))
+        return launch(xq, wq)
+
+    @staticmethod
+    def backward(ctx, dy):
+        xq, wq = ctx.saved_tensors
+        dy = _as_f32(dy).contiguous()  # (once for both gradients)
+        dx = dw = None
+        if ctx.needs_input_grad[1]:
+            dw = grad_dwconv2d_weight(dy, xq, wq.shape, *ctx.geo, split_k=ctx.split_k)
+        if ctx.needs_input_grad[0]:
+            dx = grad_dwconv2d_input(dy, wq, xq.shape, *ctx.geo)
+        return dx, dw, None, None, None, None, None, None
+
+
 class _Conv2dSTE(torch.autograd.Function):
     """y = launch(xq, wq) (the approx convolution, unchanged); backward the exact convolution's gradients on
     the gradient GEMM.  The saved input goes through fp8a_im2col once ([Bn L, Cin kh kw], L = Ho Wo);
@@ -1762,6 +1856,12 @@ def ste_conv2d(xq, wq, launch, stride=(1, 1), padding=(0, 0), dilation=(1, 1), g
                backward="im2col"):
     """launch(xq, wq) -> NCHW y with the straight-through backward (quantized NCHW input and weights).
     backward: "im2col" (the default: fp8a_im2col, grad_bmm and F.fold) or "implicit" (the implicit-GEMM kernels:
-    no im2col image and no fold, one launch per gradient for any groups)."""
-    fn = _Conv2dImplicitSTE if check_conv_backward(backward) == "implicit" else _Conv2dSTE
+    no im2col image and no fold, one launch per gradient for any groups) or "depthwise" (the direct depthwise
+    kernels where groups == Cin == Cout, "implicit" for every other geometry)."""
+    backward = check_conv_backward(backward)
+    fn = _Conv2dSTE
+    if backward == "depthwise" and int(groups) == xq.shape[1] == wq.shape[0]:
+        fn = _Conv2dDepthwiseSTE
+    elif backward != "im2col":
+        fn = _Conv2dImplicitSTE
     return fn.apply(xq, wq, launch, stride, padding, dilation, groups, check_split_k(split_k))

@@ -10,6 +10,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <climits>
 #include <atomic>
 #include <cmath>
 #include <cstdlib>
@@ -35,6 +36,7 @@
 #include "gemm_bmm.h"
 #include "gemm_grad.h"
 #include "gemm_grad_conv.h"
+#include "gemm_grad_dw.h"
 
 // (defined with C linkage below; run_gemm launches it too)
 extern "C" __global__ void fq_bias_kernel(fp8a::FqIn fq, float *bias_out, int32_t *ibias_out);
@@ -2342,6 +2344,165 @@ int fp8a_grad_conv2d_wgrad(const float *dy, const float *x, float *dwgt, int64_t
     ++g_grad_launches;
     g_grad_tiles += (uint64_t)(r.tiles * groups * S);
     return hip_check("fp8a_grad_conv2d_wgrad launch");
+}
+
+// ---- the depthwise convolution backward (gemm_grad_dw.h)
+// What the three entries check alike in a geometry, under the entry's own name, and the kernels' arguments.
+static int dwconv_args(const char *who, int64_t Bn, int64_t C, int64_t H, int64_t W, int kh, int kw, int sh, int sw,
+                       int ph, int pw, int dh, int dw, DwGradArgs &a) {
+    const std::string w = std::string(who) + ": ";
+    if (Bn <= 0 || C <= 0 || H <= 0 || W <= 0 || kh <= 0 || kw <= 0 || sh <= 0 || sw <= 0 || dh <= 0 || dw <= 0)
+        return fail(FP8A_EINVAL, w + "non-positive size");
+    if (ph < 0 || pw < 0) return fail(FP8A_EINVAL, w + "negative padding");
+    const int64_t lim = 0x7FFFFFFFll;
+    if (Bn > lim || C > lim || H > lim || W > lim || sh > (1 << 15) || sw > (1 << 15) || dh > (1 << 15) ||
+        dw > (1 << 15) || ph > (1 << 20) || pw > (1 << 20))
+        return fail(FP8A_EINVAL, w + "index range beyond the 32-bit in-tile arithmetic");
+    if (kh > DWG_KMAX || kw > DWG_KMAX || (int64_t)(kh - 1) * dh > DWG_EXT || (int64_t)(kw - 1) * dw > DWG_EXT)
+        return fail(FP8A_EINVAL, w + "a kernel beyond the runtime-geometry instance (kh, kw <= 7, (k - 1) d <= 32)");
+    if (H + 2 * (int64_t)ph < (int64_t)dh * (kh - 1) + 1 || W + 2 * (int64_t)pw < (int64_t)dw * (kw - 1) + 1)
+        return fail(FP8A_EINVAL, w + "empty output");
+    const int64_t Ho = (H + 2 * (int64_t)ph - (int64_t)dh * (kh - 1) - 1) / sh + 1;
+    const int64_t Wo = (W + 2 * (int64_t)pw - (int64_t)dw * (kw - 1) - 1) / sw + 1;
+    // the padded plane and the tensors' element counts hold in an int, with room for a tile past the end
+    if (H * W > lim / C / Bn || Ho * Wo > lim / C / Bn || (int64_t)kh * kw > lim / C ||
+        (H + 2 * (int64_t)ph + (int64_t)dh * kh) * (W + 2 * (int64_t)pw + (int64_t)dw * kw) > lim / 2)
+        return fail(FP8A_EINVAL, w + "index range beyond the 32-bit in-tile arithmetic");
+    memset(&a, 0, sizeof(a));
+    a.Bn = (int)Bn; a.C = (int)C; a.H = (int)H; a.W = (int)W; a.Ho = (int)Ho; a.Wo = (int)Wo;
+    a.kh = kh; a.kw = kw; a.sh = sh; a.sw = sw; a.ph = ph; a.pw = pw; a.dh = dh; a.dw = dw;
+    a.planes = Bn * C;
+    a.ndy = Bn * C * Ho * Wo;
+    a.R = (int)(Bn * Ho);
+    return FP8A_OK;
+}
+
+// the smallest and largest live offset e = (r + p - k d) / s over the classes r < s and the taps k
+static void dwconv_live(int n, int k, int s, int p, int d, int &e0, int &e1) {
+    e0 = INT_MAX;
+    e1 = INT_MIN;
+    for (int r = 0; r < std::min(s, n); ++r)
+        for (int t = 0; t < k; ++t) {
+            const int v = r + p - t * d;
+            if (v % s != 0) continue;
+            e0 = std::min(e0, v / s);
+            e1 = std::max(e1, v / s);
+        }
+    if (e0 > e1) e0 = e1 = 0;  // (no live tap in range: nothing is read)
+}
+
+int fp8a_grad_dwconv2d_dgrad(const float *dy, const float *w, float *dx, int64_t Bn, int64_t C, int64_t H, int64_t W,
+                             int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw, fp8a_stream_t stream) {
+    const char *const who = "fp8a_grad_dwconv2d_dgrad";
+    if (!dy || !w || !dx) return fail(FP8A_EINVAL, std::string(who) + ": null pointer");
+    DwGradArgs a;
+    const int rc = dwconv_args(who, Bn, C, H, W, kh, kw, sh, sw, ph, pw, dh, dw, a);
+    if (rc) return rc;
+    const int64_t ndx = Bn * C * H * W, nw = C * kh * kw;
+    if (gconv_meet(dx, ndx, dy, a.ndy) || gconv_meet(dx, ndx, w, nw))
+        return fail(FP8A_EINVAL, std::string(who) + ": dx overlaps an operand");
+    a.Hq = (int)((H + sh - 1) / sh);
+    a.Wq = (int)((W + sw - 1) / sw);
+    const int64_t HWq = (int64_t)a.Hq * a.Wq, HoWo = (int64_t)a.Ho * a.Wo, khw = (int64_t)kh * kw;
+    int64_t blocks, nimg;
+    // several consecutive planes per workgroup where a plane is at most half the tile and their dY fits
+    const int64_t fit = (DWG_LDS / 4 - 8) / (HoWo + khw);
+    if (2 * HWq <= DWG_PIX && fit >= 1) {
+        a.PB = (int)std::min(std::min((int64_t)DWG_PIX / HWq, fit), a.planes);
+        nimg = (a.PB * HoWo + 8 + 3) & ~(int64_t)3;
+        blocks = (a.planes + a.PB - 1) / a.PB;
+    } else {
+        int ey1, ex1;
+        dwconv_live(a.H, kh, sh, ph, dh, a.ey0, ey1);
+        dwconv_live(a.W, kw, sw, pw, dw, a.ex0, ex1);
+        a.FH = DWG_QH + ey1 - a.ey0;
+        a.FW = DWG_QW + ex1 - a.ex0;
+        a.nty = (a.Hq + DWG_QH - 1) / DWG_QH;
+        a.ntx = (a.Wq + DWG_QW - 1) / DWG_QW;
+        nimg = ((int64_t)a.FH * a.FW + 3) & ~(int64_t)3;
+        if ((int64_t)a.nty * a.ntx > 0x7FFFFFFFll / a.planes)
+            return fail(FP8A_EINVAL, std::string(who) + ": more than 2^31 - 1 blocks");
+        blocks = (int64_t)a.nty * a.ntx * a.planes;
+    }
+    a.nimg = (int)nimg;
+    a.lds = (unsigned)((nimg + std::max(a.PB, 1) * khw) * 4);
+    a.dy = dy; a.op = w; a.out = dx;
+    launch_dw_dgrad(a, (unsigned)blocks, (hipStream_t)stream);
+    ++g_grad_launches;
+    g_grad_tiles += (uint64_t)blocks;
+    return hip_check("fp8a_grad_dwconv2d_dgrad launch");
+}
+
+// the weight gradient's split and chunk plan; FP8A_OK or a refusal
+static int dwconv_wgrad_plan(const char *who, DwGradArgs &a, int64_t splits, int64_t &need) {
+    if (splits < 1) return fail(FP8A_EINVAL, std::string(who) + ": splits below 1");
+    const int64_t per = (a.R + splits - 1) / splits, S = (a.R + per - 1) / per;
+    if (S > 0x7FFFFFFFll / a.C) return fail(FP8A_EINVAL, std::string(who) + ": more than 2^31 - 1 blocks");
+    a.per = (int)per;
+    a.S = (int)S;
+    need = S > 1 ? S * a.C * a.kh * a.kw * (int64_t)sizeof(float) : 0;
+    // chunks of about DWG_CHUNK pixels whose X slabs fit: rows halved first, then columns (1 x 1 always fits)
+    int64_t CW = std::min<int64_t>(a.Wo, 256), CR = std::min<int64_t>(std::max<int64_t>(1, DWG_CHUNK / CW), per);
+    for (;;) {
+        const int64_t FHx = (std::min<int64_t>(CR, a.Ho) - 1) * a.sh + (int64_t)(a.kh - 1) * a.dh + 1;
+        const int64_t FWx = (CW - 1) * a.sw + (int64_t)(a.kw - 1) * a.dw + 1;
+        const int64_t NI = (CR - 1 + a.Ho - 1) / a.Ho + 1;  // the images CR consecutive rows can touch
+        if (NI * FHx * FWx * 4 <= DWG_LDS) {
+            a.CR = (int)CR; a.CW = (int)CW; a.FHx = (int)FHx; a.FWx = (int)FWx;
+            a.lds = (unsigned)std::max<int64_t>(NI * FHx * FWx * 4, 4 * 4 * DWG_KMAX * DWG_KMAX);
+            return FP8A_OK;
+        }
+        if (CR > 1) CR = (CR + 1) / 2;
+        else CW = (CW + 1) / 2;
+    }
+}
+
+int fp8a_grad_dwconv2d_wgrad_workspace_size(int64_t Bn, int64_t C, int64_t H, int64_t W, int kh, int kw, int sh, int sw,
+                                            int ph, int pw, int dh, int dw, int64_t splits, int64_t *eff_splits,
+                                            int64_t *bytes) {
+    const char *const who = "fp8a_grad_dwconv2d_wgrad_workspace_size";
+    if (!eff_splits || !bytes) return fail(FP8A_EINVAL, std::string(who) + ": null pointer");
+    DwGradArgs a;
+    int rc = dwconv_args(who, Bn, C, H, W, kh, kw, sh, sw, ph, pw, dh, dw, a);
+    if (rc) return rc;
+    int64_t need;
+    rc = dwconv_wgrad_plan(who, a, splits, need);
+    if (rc) return rc;
+    *eff_splits = a.S;
+    *bytes = need;
+    return FP8A_OK;
+}
+
+int fp8a_grad_dwconv2d_wgrad(const float *dy, const float *x, float *dwgt, int64_t Bn, int64_t C, int64_t H, int64_t W,
+                             int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw, int64_t splits,
+                             void *workspace, int64_t workspace_bytes, fp8a_stream_t stream) {
+    const char *const who = "fp8a_grad_dwconv2d_wgrad";
+    if (!dy || !x || !dwgt) return fail(FP8A_EINVAL, std::string(who) + ": null pointer");
+    DwGradArgs a;
+    int rc = dwconv_args(who, Bn, C, H, W, kh, kw, sh, sw, ph, pw, dh, dw, a);
+    if (rc) return rc;
+    int64_t need;
+    rc = dwconv_wgrad_plan(who, a, splits, need);
+    if (rc) return rc;
+    const int64_t nx = Bn * C * H * W, nw = C * kh * kw;
+    if (gconv_meet(dwgt, nw, dy, a.ndy) || gconv_meet(dwgt, nw, x, nx))
+        return fail(FP8A_EINVAL, std::string(who) + ": dw overlaps an operand");
+    if (a.S > 1) {
+        if (!workspace) return fail(FP8A_EINVAL, std::string(who) + ": null workspace");
+        if (workspace_bytes < need)
+            return fail(FP8A_EINVAL, std::string(who) + ": workspace of " + std::to_string(workspace_bytes) + " bytes, " +
+                                         std::to_string(need) + " needed");
+        if (((uintptr_t)workspace & 15u) != 0) return fail(FP8A_EINVAL, std::string(who) + ": workspace not 16-byte aligned");
+        const float *const Wk = (const float *)workspace;
+        const int64_t ew = need / (int64_t)sizeof(float);
+        if (gconv_meet(Wk, ew, dy, a.ndy) || gconv_meet(Wk, ew, x, nx) || gconv_meet(Wk, ew, dwgt, nw))
+            return fail(FP8A_EINVAL, std::string(who) + ": the workspace overlaps dy, x or dw");
+    }
+    a.dy = dy; a.op = x; a.out = dwgt;
+    launch_dw_wgrad(a, (float *)workspace, (hipStream_t)stream);
+    ++g_grad_launches;
+    g_grad_tiles += (uint64_t)((int64_t)a.C * a.S);
+    return hip_check("fp8a_grad_dwconv2d_wgrad launch");
 }
 
 int fp8a_grad_stats(uint64_t out[3], int reset) {

@@ -25,6 +25,8 @@ approx_ops.grad_split_auto picks per product ("auto"), and adds the parts in a f
 custom_approx_params["grad_split_k"]; default 1, off.  grad_gemm_ms then includes the reduce passes.
 --conv-backward implicit: the convolutions' backward on the implicit-GEMM kernels:
 custom_approx_params["conv_backward"]; no im2col image and no fold, so im2col_fold_ms stays 0; default im2col.
+--conv-backward depthwise: as implicit, with the depthwise layers (groups == Cin == Cout) on the direct fp32 kernels
+(DESIGN.md §3aj); their launches count in grad_gemm_ms.
 Data: --synthetic N random images and labels, or <images-dir>/train as imagenet.py reads it.
 """
 import argparse
@@ -76,7 +78,8 @@ def parse(argv=None):
     ap.add_argument("--grad-split-k", type=_split_k, default=1, metavar="{N,auto}",
                     help="split the gradient GEMMs' reductions along K: a part count, or auto (default 1: off)")
     ap.add_argument("--conv-backward", default="im2col", choices=list(approx_ops.CONV_BACKWARDS),
-                    help="the convolutions' backward: the im2col image + fold, or the implicit-GEMM kernels")
+                    help="the convolutions' backward: the im2col image + fold, the implicit-GEMM kernels, or those with the "
+                         "direct depthwise kernels")
     ap.add_argument("--output", default=None, help="also write the step records (a JSON list) here")
     return ap.parse_args(argv)
 

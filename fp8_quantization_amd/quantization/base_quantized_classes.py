@@ -77,7 +77,7 @@ def grad_split_k(module):
 def conv_backward(module):
     """custom_approx_params['conv_backward'] of a layer: the path of a convolution's straight-through backward
     (approx_ops.ste_conv2d's backward).  Absent or "im2col": the im2col image, grad_bmm and F.fold; "implicit": the
-    implicit-GEMM kernels; anything else raises ValueError (at construction too).  Nothing without ste_backward."""
+    implicit-GEMM kernels; "depthwise": those, with the direct kernels for depthwise layers; anything else raises ValueError (at construction too).  Nothing without ste_backward."""
     from ..approx_ops import check_conv_backward
     return check_conv_backward((getattr(module, "custom_approx_params", None) or {}).get("conv_backward", "im2col"),
                                "custom_approx_params['conv_backward']")

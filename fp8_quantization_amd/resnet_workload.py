@@ -40,7 +40,7 @@ def approx_qparams(expo_width=4, mant_width=3, dnsmp_factor=3, withComp=False, w
     with a straight-through backward on the gradient GEMM (INTEGRATION.md), nothing else changes;
     grad_split_k (custom_approx_params["grad_split_k"]: an int >= 2 or "auto"; 1 = off): that backward's gradient
     GEMMs split their reduction along K (approx_ops.grad_bmm's split_k), nothing without ste_backward;
-    conv_backward (custom_approx_params["conv_backward"]: "implicit"; "im2col" = off): the convolutions' backward on
+    conv_backward (custom_approx_params["conv_backward"]: "implicit" or "depthwise"; "im2col" = off): the convolutions' backward on
     the implicit-GEMM kernels (approx_ops.ste_conv2d's backward), nothing without ste_backward;
     learn_maxval (the reference's --fp8-learn-maxval): every FP8 quantizer is built so that learn_ranges()
     turns its maxval into a Parameter (needs ste_backward for its gradient).

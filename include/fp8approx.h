@@ -401,6 +401,39 @@ int fp8a_grad_conv2d_wgrad(const float *dy, const float *x, float *dwgt, int64_t
                            int64_t workspace_bytes, fp8a_stream_t stream);
 
 /*
+ * The depthwise convolution backward: the two gradients of y = conv2d(x, w, groups = C) with
+ * w [C, 1, kh, kw], by direct fp32 kernels on dense NCHW tensors -- at one channel per group a matrix-core gradient
+ * tile holds one useful column.  dy is [Bn, C, Ho, Wo], Ho and Wo as above.
+ *   dx[b, c, iy, ix] = sum_{ky, kx} dy[b, c, oy, ox] w[c, 0, ky, kx], oy = (iy + ph - ky dh) / sh where exact and
+ *                      in range (ox likewise)
+ *   dw[c, 0, ky, kx] = sum_{b, oy, ox} dy[b, c, oy, ox] x[b, c, oy sh - ph + ky dh, ox sw - pw + kx dw]
+ * Every term is one fp32 fma on the operands as they are: any float32 operand takes the one path, nothing is split
+ * or recomputed and the recomputed-tile counter is never raised.  Padding positions and taps that reach no output
+ * are neither read nor multiplied (they are not 0 * w).  Every element of the output is written, +0 where nothing
+ * contributes.  3 x 3 kernels with dilation 1, padding 1 and stride (1, 1) or (2, 2) run compile-time instances of
+ * the data gradient, every 3 x 3 one of the weight gradient; any other kernel up to 7 x 7 with (kh - 1) dh <= 32 and
+ * (kw - 1) dw <= 32 the runtime-geometry instances, at any stride and padding.
+ * fp8a_grad_dwconv2d_wgrad splits the reduction by output rows (b, oy): R = Bn Ho, per = ceil(R / splits),
+ * S = ceil(R / per) parts, none empty, part s the rows [per s, min(per (s + 1), R)).  S == 1 is one launch and
+ * takes no workspace; else part s stores its kh kw sums at workspace[(c S + s) kh kw ..] and a second launch adds
+ * P_0 + P_1 + ... in index order.  fp8a_grad_dwconv2d_wgrad_workspace_size: S and the bytes, S C kh kw 4 (0 when
+ * S == 1); no HIP call.  Deterministic: fixed orders within a workgroup and across the parts, no float atomics.
+ * Every argument check runs before any HIP call: null pointers, non-positive sizes, negative padding, an empty
+ * output, a kernel beyond the runtime-geometry instance, tensors or padded planes beyond the 32-bit in-tile index
+ * arithmetic (2^31 - 1 elements), more than 2^31 - 1 blocks, the output over an operand, splits below 1, and the
+ * workspace null, too small, not 16-byte aligned or over a tensor.  fp8a_grad_stats counts a call of either entry
+ * as one launch and its product-pass workgroups as tiles.
+ */
+int fp8a_grad_dwconv2d_dgrad(const float *dy, const float *w, float *dx, int64_t Bn, int64_t C, int64_t H, int64_t W,
+                             int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw, fp8a_stream_t stream);
+int fp8a_grad_dwconv2d_wgrad_workspace_size(int64_t Bn, int64_t C, int64_t H, int64_t W, int kh, int kw, int sh,
+                                            int sw, int ph, int pw, int dh, int dw, int64_t splits,
+                                            int64_t *eff_splits, int64_t *bytes);
+int fp8a_grad_dwconv2d_wgrad(const float *dy, const float *x, float *dwgt, int64_t Bn, int64_t C, int64_t H, int64_t W,
+                             int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw, int64_t splits,
+                             void *workspace, int64_t workspace_bytes, fp8a_stream_t stream);
+
+/*
  * Per-product terms (debug / parity): T[m, k, n] = the value the reference sums at v9:113.
  * Same arguments as fp8a_matmul; T is dense [M][K][N].
  */

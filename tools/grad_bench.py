@@ -16,7 +16,13 @@ product pass's workgroups and the time relative to the latest split_k = 1 of the
 --conv: the convolution backward instead, at batch 64 and split_k = auto: per layer the
 implicit-GEMM data and weight gradients (grad_conv2d_input / grad_conv2d_weight) against the default path's two
 halves on the same operands -- fp8a_im2col + grad_bmm for dW, grad_bmm + F.fold for dX, as _Conv2dSTE.backward
-issues them -- with the largest |difference| between the two paths over the largest |value|.
+issues them -- with the largest |difference| between the two paths over the largest |value|.  The depthwise layers
+(four MobileNetV2 shapes) also run the direct kernels (grad_dwconv2d_input / grad_dwconv2d_weight): the
+three paths alternated, twice over, each gradient's time the smaller of its two medians and "spread" the largest
+relative difference between a path's two medians; per gradient and path the algorithmic bytes (dgrad: dy + dx + w;
+wgrad: dy + x + dw) over the time as GB/s, and for the direct kernels that figure's share of an 8 TB/s HBM peak.
+--dw-only: the depthwise layers alone.  --dw-splits 1,2,4,auto: grad_dwconv2d_weight at each split_k on those layers
+(the sweep behind GRAD_DW_MIN_ROWS), one line per layer.
 """
 import argparse
 import json
@@ -94,12 +100,15 @@ def shapes(sweep=False):
 CONV_LAYERS = [("r18.conv1", 3, 224, 64, 7, 2, 3, 1), ("r18.layer1.0.conv1", 64, 56, 64, 3, 1, 1, 1),
                ("r18.layer2.0.conv1", 64, 56, 128, 3, 2, 1, 1), ("r18.layer2.0.downsample", 64, 56, 128, 1, 2, 0, 1),
                ("r18.layer2.conv2", 128, 28, 128, 3, 1, 1, 1), ("r18.layer4.1.conv2", 512, 7, 512, 3, 1, 1, 1),
-               ("mbv2.dw3x3 s1", 144, 56, 144, 3, 1, 1, 144), ("mbv2.dw3x3 s2", 144, 56, 144, 3, 2, 1, 144)]
+               ("mbv2.dw3x3 s1", 144, 56, 144, 3, 1, 1, 144), ("mbv2.dw3x3 s2", 144, 56, 144, 3, 2, 1, 144),
+               ("mbv2.dw3x3 14x14x576", 576, 14, 576, 3, 1, 1, 576), ("mbv2.dw3x3 7x7x960", 960, 7, 960, 3, 1, 1, 960)]
+HBM_PEAK_GBS = 8000.0
 
 
 def conv_mode(a):
     import torch.nn.functional as F
-    from fp8_quantization_amd.approx_ops import _Conv2dSTE, grad_conv2d_input, grad_conv2d_weight
+    from fp8_quantization_amd.approx_ops import (_Conv2dSTE, grad_conv2d_input, grad_conv2d_weight, grad_dw_split_auto,
+                                                 grad_dwconv2d_input, grad_dwconv2d_weight)
 
     class Ctx:  # _Conv2dSTE.backward's context: one half of the default backward per call
         split_k = "auto"
@@ -107,6 +116,9 @@ def conv_mode(a):
     g = torch.Generator(device=DEV).manual_seed(0)
     lines = []
     for name, cin, hw, cout, k, s, pad, groups in CONV_LAYERS:
+        dwl = groups == cin == cout
+        if (a.dw_only or a.dw_splits) and not dwl:
+            continue
         x = bf16_exact(torch.randn((64, cin, hw, hw), device=DEV, generator=g))
         w = bf16_exact(torch.randn((cout, cin // groups, k, k), device=DEV, generator=g))
         geo = ((s, s), (pad, pad), (1, 1), groups)
@@ -120,6 +132,39 @@ def conv_mode(a):
         calls = {"dgrad": (lambda: grad_conv2d_input(dy, w, x.shape, *geo), lambda: default(0)),
                  "wgrad": (lambda: grad_conv2d_weight(dy, x, w.shape, *geo, split_k="auto"), lambda: default(1))}
         rec = dict(layer=name, batch=64)
+        if a.dw_splits:
+            rows = dy.shape[0] * dy.shape[2]
+            for sk in a.dw_splits:
+                key = f"wgrad_ms_split_{sk}" + (f"={grad_dw_split_auto(cin, rows, DEV)}" if sk == "auto" else "")
+                rec[key] = med_ms(lambda: grad_dwconv2d_weight(dy, x, w.shape, *geo[:3], split_k=sk), a.iters, a.warmup)
+            lines.append(rec)
+            print(json.dumps(rec), flush=True)
+            continue
+        if dwl:
+            direct = {"dgrad": lambda: grad_dwconv2d_input(dy, w, x.shape, *geo[:3]),
+                      "wgrad": lambda: grad_dwconv2d_weight(dy, x, w.shape, *geo[:3], split_k="auto")}
+            nbytes = {"dgrad": 4 * (dy.numel() + x.numel() + w.numel()), "wgrad": 4 * (dy.numel() + x.numel() + w.numel())}
+            spread = 0.0
+            for what, (new, old) in calls.items():
+                ref = old()
+                rec[what + "_depthwise_max_diff_over_max"] = float((direct[what]() - ref).abs().max() / ref.abs().max())
+                del ref
+                t = {"depthwise": [], "implicit": [], "im2col": []}
+                for _ in range(2):  # the three paths alternated, twice
+                    for path, fn in (("depthwise", direct[what]), ("implicit", new), ("im2col", old)):
+                        t[path].append(med_ms(fn, a.iters, a.warmup))
+                for path, v in t.items():
+                    rec[f"{what}_{path}_ms"] = min(v)
+                    rec[f"{what}_{path}_GBs"] = nbytes[what] / min(v) * 1e-6
+                    spread = max(spread, abs(v[0] - v[1]) / min(v))
+                rec[what + "_depthwise_share_of_8TBs_peak"] = rec[f"{what}_depthwise_GBs"] / HBM_PEAK_GBS
+            rec["spread"] = spread
+            rec["recomputed"] = _lib.grad_stats(reset=True)["recomputed"]
+            lines.append(rec)
+            print(json.dumps(rec), flush=True)
+            del x, w, dy
+            torch.cuda.empty_cache()
+            continue
         for what, (new, old) in calls.items():
             _lib.grad_stats(reset=True)
             got, ref = new(), old()
@@ -150,6 +195,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--split-k", type=split_list, default=None, help="grad_bmm's split_k: one value or a comma list")
     ap.add_argument("--conv", action="store_true", help="the convolution backward: implicit GEMM against im2col + fold")
+    ap.add_argument("--dw-only", action="store_true", help="with --conv: the depthwise layers alone")
+    ap.add_argument("--dw-splits", type=split_list, default=None, help="with --conv: grad_dwconv2d_weight's split_k sweep")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     torch.backends.cuda.matmul.allow_tf32 = False

@@ -6,7 +6,8 @@ library (the AMDGPU metadata note), optionally against a second library.
 
 Host-only: unbundles .hip_fatbin (tests/test_abi_cpu.py's ELF reader) and runs llvm-readobj
 --notes on each code object.  Prints one line per kernel: VGPR, AGPR, SGPR, VGPR / SGPR spills,
-scratch bytes, LDS bytes; with --vs, only the kernels whose figures differ.
+scratch bytes, LDS bytes; with --vs, only the kernels whose figures differ.  --grep dwconv: the depthwise backward's
+kernels (csrc/gemm_grad_dw.h; their LDS is dynamic, sized by the host plan, so the static figure is 0).
 """
 import argparse
 import os
