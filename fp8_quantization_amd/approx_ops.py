@@ -25,7 +25,7 @@ __all__ = ["custom_matmul_vectorize", "approx_matmul", "approx_bmm", "approx_mat
            "quant_to_fp_any_vectorize_torch", "float_to_fpany_absint_torch", "get_error_table_NN",
            "make_flags", "make_flags_v5", "fp8_fake_quantize", "bn_act_epilogue", "dense_format", "dense_matmul",
            "dense_conv2d", "grouped_conv2d", "dense_conv2d_fused", "approx_matmul_check", "approx_conv2d_check", "approx_bmm_check",
-           "CheckStats", "format_self_check", "SELF_CHECK_LABELS", "fp8_mse_losses", "bn_train", "grad_bmm", "grad_split_auto",
+           "CheckStats", "format_self_check", "SELF_CHECK_LABELS", "fp8_mse_losses", "bn_train", "bn_train_backward", "bn_train_ste", "grad_bmm", "grad_split_auto",
            "grad_conv2d_input", "grad_conv2d_weight", "grad_dwconv2d_input", "grad_dwconv2d_weight",
            "ste_linear", "ste_bmm", "ste_conv2d", "fp8_fake_quantize_train", "fp8_fake_quantize_backward"]
 
@@ -993,6 +993,114 @@ def bn_train(x, gamma, beta, running_mean, running_var, momentum, eps, activatio
     if qb is not None:
         qb._fp8a_i32 = qib
     return y, save_mean, save_var, ss, qb
+
+
+BN_BACKWARDS = ("torch", "fused")
+
+
+def check_bn_backward(value, what="bn_backward"):
+    """A training-mode batch norm's backward path: "torch" (F.batch_norm and its autograd) or "fused"
+    (bn_train_ste: the deterministic kernels of csrc/bn_train.h and csrc/bn_bwd.h); anything else is a ValueError
+    naming `what`."""
+    if isinstance(value, str) and value in BN_BACKWARDS:
+        return value
+    raise ValueError(f"{what} must be one of {BN_BACKWARDS}, got {value!r}")
+
+
+def bn_train_backward(x, dy, gamma, save_mean, save_var, ss, eps, activation=None, out=None):
+    """The backward of bn_train's y = clamp(x * scale + shift) on the deterministic kernels of csrc/bn_bwd.h
+    (fp8a_bn_train_backward): x is the forward's input (the pre-BN product), save_mean / save_var / ss what that
+    forward returned, dy the gradient of y (x's shape).  The clamp's mask is recomputed from x and ss, bit for bit
+    the forward's; sums in double in a fixed order, no atomics: two calls return identical bytes.
+
+    activation: as bn_train (a non-clamp activation returns None).  out: the tensor dx is written to (may be dy).
+
+    Returns (dx, dgamma, dbeta); dgamma is the gradient of gamma whether or not gamma is given (None: 1)."""
+    L = _lib.load()
+    clamp = _clamp_of(activation)
+    if clamp is None:
+        return None
+    act, lo, hi = clamp
+    if not x.is_cuda:
+        raise RuntimeError("fp8approx kernels need HIP device tensors (no CPU fallback)")
+    if x.dim() < 2:
+        raise ValueError(f"bn_train_backward: expected at least 2 dims, got {x.dim()}")
+    if dy.shape != x.shape or dy.device != x.device:
+        raise AssertionError("bn_train_backward: dy must match x")
+    x = _as_f32(x).contiguous()
+    if dy.dtype != torch.float32 or not dy.is_contiguous():
+        if out is dy:
+            raise AssertionError("bn_train_backward: in place needs a contiguous float32 dy")
+        dy = _as_f32(dy).contiguous()
+    dev = x.device
+    N, C = x.shape[0], x.shape[1]
+    inner = x.numel() // max(N * C, 1)
+    if N == 0 or C == 0 or inner == 0:
+        raise AssertionError("bn_train_backward: empty input")
+    if N * inner == 1:
+        raise ValueError(f"Expected more than 1 value per channel when training, got input size {tuple(x.shape)}")
+
+    def par(t, what, numel=C):
+        if t is None:
+            return None
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != numel or t.device != dev:
+            raise AssertionError(f"bn_train_backward: {what} must be a contiguous float32 tensor of {numel} on {dev}")
+        return t.detach()
+    gamma, save_mean, save_var = par(gamma, "gamma"), par(save_mean, "save_mean"), par(save_var, "save_var")
+    ss = par(ss, "ss", 2 * C)
+    if save_mean is None or save_var is None or ss is None:
+        raise AssertionError("bn_train_backward: save_mean, save_var and ss are the forward's, not None")
+    if out is None:
+        dx = torch.empty_like(x)
+    else:
+        if out.shape != x.shape or out.dtype != torch.float32 or not out.is_contiguous() or out.device != dev:
+            raise AssertionError("bn_train_backward: out must match x (contiguous float32)")
+        dx = out
+    dgamma = torch.empty(C, dtype=torch.float32, device=dev)
+    dbeta = torch.empty(C, dtype=torch.float32, device=dev)
+    nbytes = int(L.fp8a_bn_train_backward_workspace_size(N, C, inner))
+    ws = _workspace(dev, nbytes)
+    rc = L.fp8a_bn_train_backward(_lib.dev_ptr(x), _lib.dev_ptr(dy), _lib.dev_ptr(dx), N, C, inner, _lib.dev_ptr(gamma),
+                                  _lib.dev_ptr(save_mean), _lib.dev_ptr(save_var), float(eps), _lib.dev_ptr(ss), act, lo,
+                                  hi, _lib.dev_ptr(dgamma), _lib.dev_ptr(dbeta), _lib.dev_ptr(ws), nbytes,
+                                  _lib.stream_ptr(dev))
+    _lib.check(rc, "fp8a_bn_train_backward")
+    return dx, dgamma, dbeta
+
+
+class _BnTrainSTE(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, gamma, beta, running_mean, running_var, momentum, eps, activation):
+        xc = _as_f32(x.detach()).contiguous()
+        with _ste_timed("bn_forward"):
+            y, save_mean, save_var, ss, _ = bn_train(xc, gamma, beta, running_mean, running_var, momentum, eps,
+                                                     activation=activation)
+        ctx.save_for_backward(xc, gamma, save_mean, save_var, ss)
+        ctx.eps, ctx.activation, ctx.has_beta, ctx.x_dtype = eps, activation, beta is not None, x.dtype
+        return y if x.dtype == torch.float32 else y.to(x.dtype)
+
+    @staticmethod
+    def backward(ctx, dy):
+        xc, gamma, save_mean, save_var, ss = ctx.saved_tensors
+        with _ste_timed("bn_backward"):
+            dx, dgamma, dbeta = bn_train_backward(xc, dy, gamma, save_mean, save_var, ss, ctx.eps,
+                                                  activation=ctx.activation)
+        if ctx.x_dtype != torch.float32:
+            dx = dx.to(ctx.x_dtype)
+        return (dx, dgamma if gamma is not None else None, dbeta if ctx.has_beta else None, None, None, None, None,
+                None)
+
+
+def bn_train_ste(x, gamma, beta, running_mean, running_var, momentum, eps, activation=None):
+    """Training-mode batch norm + a clamp activation that autograd records: the forward is bn_train, out of place
+    and without an output quantizer (the running buffers are updated in place as there), the backward is ONE
+    bn_train_backward call on the saved x, scale / shift, save_mean and save_var -- both on deterministic kernels,
+    so a training step repeats bit for bit.  A non-clamp activation returns None, as bn_train does (the caller
+    then runs this without the activation, and the activation after it).  Under finetune's profile the two
+    directions are timed as "bn_forward" and "bn_backward"."""
+    if _clamp_of(activation) is None:
+        return None
+    return _BnTrainSTE.apply(x, gamma, beta, running_mean, running_var, momentum, eps, activation)
 
 
 # ----------------------------------------------------------------------------------- FP8 fake quant

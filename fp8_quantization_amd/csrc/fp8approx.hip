@@ -33,6 +33,7 @@
 #include "fq_mse.h"
 #include "fq_train.h"
 #include "bn_train.h"
+#include "bn_bwd.h"
 #include "gemm_bmm.h"
 #include "gemm_grad.h"
 #include "gemm_grad_conv.h"
@@ -3584,6 +3585,40 @@ int fp8a_bn_train(const float *x, float *y, int64_t N, int64_t C, int64_t inner,
     a.vec = inner % 4 == 0 && (((uintptr_t)x | (uintptr_t)y) & 15) == 0;
     launch_bn_train(a, (hipStream_t)stream);
     return hip_check("fp8a_bn_train");
+}
+
+// Its backward (bn_bwd.h).  Workspace: the (G, H) double pairs [C][parts], then the coefficient records [C].
+size_t fp8a_bn_train_backward_workspace_size(int64_t N, int64_t C, int64_t inner) {
+    if (!bn_shape_ok(N, C, inner)) return 0;
+    return (size_t)C * ((size_t)bn_parts(N, C, inner) * sizeof(double2) + sizeof(float4));
+}
+
+int fp8a_bn_train_backward(const float *x, const float *dy, float *dx, int64_t N, int64_t C, int64_t inner,
+                           const float *gamma, const float *save_mean, const float *save_var, float eps,
+                           const float *scale_shift, int act, float lo, float hi, float *dgamma, float *dbeta,
+                           void *workspace, size_t workspace_bytes, fp8a_stream_t stream) {
+    if (!bn_shape_ok(N, C, inner)) return fail(FP8A_EINVAL, "bad batch-norm shape");
+    if (N * inner == 1)  // (the forward refuses it: there is nothing to differentiate)
+        return fail(FP8A_EFORMAT, "Expected more than 1 value per channel when training");
+    if (act != 0 && act != 1) return fail(FP8A_EINVAL, "bn_train_backward: act is 0 or 1");
+    if (workspace_bytes < fp8a_bn_train_backward_workspace_size(N, C, inner))
+        return fail(FP8A_EINVAL, "workspace too small");
+    if (x == nullptr || dy == nullptr || dx == nullptr || save_mean == nullptr || save_var == nullptr ||
+        scale_shift == nullptr || workspace == nullptr || ((uintptr_t)workspace & 15) != 0 ||
+        ((uintptr_t)scale_shift & 7) != 0)
+        return fail(FP8A_EINVAL, "null or misaligned pointer");
+    BnBwdArgs a{};
+    a.x = x; a.dy = dy; a.dx = dx; a.N = N; a.C = C; a.inner = inner; a.n = N * inner;
+    a.parts = bn_parts(N, C, inner);
+    a.part = static_cast<double2 *>(workspace);
+    a.coef = reinterpret_cast<float4 *>(a.part + C * a.parts);
+    a.gamma = gamma; a.save_mean = save_mean; a.save_var = save_var; a.eps = eps;
+    a.ss = reinterpret_cast<const float2 *>(scale_shift);
+    a.act = act; a.lo = lo; a.hi = hi;
+    a.dgamma = dgamma; a.dbeta = dbeta;
+    a.vec = inner % 4 == 0 && (((uintptr_t)x | (uintptr_t)dy | (uintptr_t)dx) & 15) == 0;
+    launch_bn_train_backward(a, (hipStream_t)stream);
+    return hip_check("fp8a_bn_train_backward");
 }
 
 // The config-1 layer (approx_flag off) in one launch family: fq_in on the loaded input, the exact

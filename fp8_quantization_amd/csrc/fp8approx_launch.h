@@ -56,6 +56,10 @@ void launch_mse(const MseArgs &a, bool group, hipStream_t s);
 // or along channels), the per-channel finalize and, with a.y, the apply kernel.
 struct BnArgs;
 void launch_bn_train(const BnArgs &a, hipStream_t s);
+// ... and its backward (bn_bwd.h): the register-resident kernel where one workgroup holds a channel, else the
+// reduce kernel (by inner, as above), the per-channel finalize and the apply kernel.
+struct BnBwdArgs;
+void launch_bn_train_backward(const BnBwdArgs &a, hipStream_t s);
 
 // k_fqt.hip: the fake quantizer's training pair (fq_train.h) -- the forward (values, biases, code bytes),
 // and the backward (grad_x, the workgroups' parts of grad_maxval) with its ordered reduction.

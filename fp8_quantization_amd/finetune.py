@@ -5,7 +5,7 @@ quantizer masks, the exact product's gradients on the gradient GEMM fp8a_grad_bm
     python -m fp8_quantization_amd.finetune --synthetic 64 --arch resnet18|mobilenet_v2|vit_b16 \
         --steps 10 --lr 1e-3 [--batch-size 64] [--momentum 0.9] [--approx-attention] \
         [--learn-ranges [--range-lr 1e-4]] [--grad-split-k N|auto] [--conv-backward im2col|implicit]
-        [--seed 0]
+        [--train-bn [--bn-backward torch|fused]] [--seed 0]
 
 A driver, not a trainer (no schedule, checkpoints or augmentation): it calibrates and fixes the FP8 ranges as
 the validation driver does (imagenet.py: estimate_ranges over --num-est-batches batches, fix_ranges), keeps the
@@ -27,6 +27,11 @@ custom_approx_params["grad_split_k"]; default 1, off.  grad_gemm_ms then include
 custom_approx_params["conv_backward"]; no im2col image and no fold, so im2col_fold_ms stays 0; default im2col.
 --conv-backward depthwise: as implicit, with the depthwise layers (groups == Cin == Cout) on the direct fp32 kernels
 (DESIGN.md §3aj); their launches count in grad_gemm_ms.
+--train-bn: after model.eval() every BN-fused layer (the layer alone, not its children) goes to training mode: its
+batch norm normalizes with the batch statistics and updates its running buffers, as the reference's QAT protocol
+does.  --bn-backward fused runs that batch norm on the deterministic kernels in both directions:
+custom_approx_params["bn_backward"]; default torch, F.batch_norm and its autograd.  With either flag each record
+gains bn_ms, the recorded milliseconds of the fused forward + backward calls (0 on the torch path, which records none).
 Data: --synthetic N random images and labels, or <images-dir>/train as imagenet.py reads it.
 """
 import argparse
@@ -80,6 +85,10 @@ def parse(argv=None):
     ap.add_argument("--conv-backward", default="im2col", choices=list(approx_ops.CONV_BACKWARDS),
                     help="the convolutions' backward: the im2col image + fold, the implicit-GEMM kernels, or those with the "
                          "direct depthwise kernels")
+    ap.add_argument("--train-bn", action="store_true",
+                    help="the BN-fused layers train on batch statistics (the rest of the model stays in eval mode)")
+    ap.add_argument("--bn-backward", default="torch", choices=list(approx_ops.BN_BACKWARDS),
+                    help="a recorded training-mode batch norm: F.batch_norm and its autograd, or the deterministic kernels")
     ap.add_argument("--output", default=None, help="also write the step records (a JSON list) here")
     return ap.parse_args(argv)
 
@@ -95,6 +104,8 @@ def approx_cfg(args):
         cfg["grad_split_k"] = args.grad_split_k
     if getattr(args, "conv_backward", "im2col") != "im2col":
         cfg["conv_backward"] = args.conv_backward
+    if getattr(args, "bn_backward", "torch") != "torch":
+        cfg["bn_backward"] = args.bn_backward
     return cfg
 
 
@@ -114,6 +125,11 @@ def finetune(model, data, args, dev):
                 break
     calibrate_on_rank0(model, cal())
     model.eval()  # BN on its running statistics, dropout off: only the products, quantizers and affines train
+    bn_flags = getattr(args, "train_bn", False) or getattr(args, "bn_backward", "torch") != "torch"
+    if getattr(args, "train_bn", False):
+        from .bn_reestimate import bn_fused_layers
+        for _, layer in bn_fused_layers(model):
+            layer.training = True  # (the layer alone: its quantizers stay in eval mode)
     ranges, cal0 = [], None
     if args.learn_ranges:
         from .distributed import quantizers
@@ -153,6 +169,8 @@ def finetune(model, data, args, dev):
                        grad_gemm_launches=st["launches"], recomputed_tiles=st["recomputed"])
             rec.update(learned_ranges=len(ranges), max_range_change=0.0, bad_ranges=0,
                        quantizer_ms=_events_ms(prof.get("fq_forward", ())) + _events_ms(prof.get("fq_backward", ())))
+            if bn_flags:
+                rec.update(bn_ms=_events_ms(prof.get("bn_forward", ())) + _events_ms(prof.get("bn_backward", ())))
             if ranges:
                 now = torch.cat([p.detach().reshape(-1) for p in ranges])
                 rec.update(max_range_change=float(((now - cal0).abs() / cal0.abs()).max()),

@@ -83,6 +83,16 @@ def conv_backward(module):
                                "custom_approx_params['conv_backward']")
 
 
+def bn_backward(module):
+    """custom_approx_params['bn_backward'] of a layer: the path of a training-mode batch norm that autograd records
+    (BNFusedHijacker.forward).  Absent or "torch": F.batch_norm and its autograd; "fused": approx_ops.bn_train_ste, the
+    deterministic kernels in both directions; anything else raises ValueError (at construction too).  Nothing without
+    ste_backward."""
+    from ..approx_ops import check_bn_backward
+    return check_bn_backward((getattr(module, "custom_approx_params", None) or {}).get("bn_backward", "torch"),
+                             "custom_approx_params['bn_backward']")
+
+
 def _version5(module):
     return (getattr(module, "custom_approx_params", None) or {}).get("approx_version", 9) == 5
 
@@ -100,6 +110,7 @@ class QuantizedModule(nn.Module):
         self.custom_approx_params = kwargs.pop("custom_approx_params", None)
         grad_split_k(self)  # (a value the backward cannot take raises here, not in the first backward)
         conv_backward(self)
+        bn_backward(self)
         self.run_method = kwargs.pop("run_method", None) or dict(_DEFAULT_RUN_METHOD)
         self.approx_flag = self.run_method["approx_flag"]
         self.quantize_after_mult_and_add = self.run_method["quantize_after_mult_and_add"]

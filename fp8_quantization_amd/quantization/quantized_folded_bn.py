@@ -19,6 +19,10 @@ Training mode (the BN re-estimation protocol, bn_reestimate.py): the fused store
 (they need the eval statistics); with ``fuse_bn_train`` (default on, FP8A_FUSE_BN_TRAIN=0 turns it
 off) F.batch_norm(training=True), a clamp activation and the layer's own output quantizer run as
 approx_ops.bn_train -- statistics that are identical bit for bit run to run, which MIOpen's are not.
+Those kernels run where autograd does not record.  Where it does, custom_approx_params["bn_backward"] = "fused"
+(with ste_backward) routes F.batch_norm + a clamp activation through approx_ops.bn_train_ste -- the same forward
+kernels and the backward kernels of csrc/bn_bwd.h -- and the output quantizer runs after it on its training path;
+absent or "torch", that forward is F.batch_norm and its autograd as before.
 """
 import os
 
@@ -27,6 +31,7 @@ import torch.nn.functional as F
 from torch import nn
 from torch.nn.modules.conv import _ConvNd
 
+from .base_quantized_classes import bn_backward, ste_switch
 from .hijacker import QuantizationHijacker
 
 
@@ -176,16 +181,36 @@ class BNFusedHijacker(QuantizationHijacker):
             res, qa = self._core(x, epilogue=ep, post=post, chain=chain)
             return self._epilogue(res, qa, activation_done=True)
         res, qa = self._core(x)
+        if self._bn_train_recorded(res):
+            return self._forward_bn_train_ste(res, qa)
         if self._bn_train_fused(res):
             return self._forward_bn_train(res, qa)
         res = F.batch_norm(res, self.running_mean, self.running_var, self.gamma, self.beta, self.training,
                            self.momentum, self.epsilon)
         return self._epilogue(res, qa)
 
+    def _bn_train_recorded(self, res):
+        """Whether the training-mode batch norm of this forward runs on approx_ops.bn_train_ste: the layer's
+        bn_backward key is "fused" under ste_backward, training mode, a HIP tensor, a float momentum, and
+        autograd records this forward."""
+        return (self.training and bn_backward(self) == "fused" and ste_switch(self) and res.is_cuda
+                and isinstance(self.momentum, float) and res.dim() >= 2 and torch.is_grad_enabled()
+                and (res.requires_grad or self.gamma.requires_grad or self.beta.requires_grad))
+
+    def _forward_bn_train_ste(self, res, qa):
+        """F.batch_norm(training) + a clamp activation as bn_train_ste; any other activation runs after it; the
+        layer's output quantizer follows on its own training path."""
+        from ..approx_ops import bn_train_ste
+        args = (res, self.gamma, self.beta, self.running_mean, self.running_var, self.momentum, self.epsilon)
+        y = bn_train_ste(*args, activation=self.activation_function)
+        if y is None:  # not a clamp
+            return self._epilogue(bn_train_ste(*args), qa)
+        return self._epilogue(y, qa, activation_done=True)
+
     def _bn_train_fused(self, res):
         """Whether the training-mode batch norm of this forward runs on approx_ops.bn_train: training
         mode, a HIP tensor, a float momentum (None is torch's cumulative average: not modelled) and no
-        gradient to record (the kernels have no backward)."""
+        gradient to record (that forward is bn_train_ste's, under the layer's bn_backward key)."""
         return (self.fuse_bn_train and self.training and res.is_cuda and isinstance(self.momentum, float)
                 and res.dim() >= 2 and not (torch.is_grad_enabled() and res.requires_grad))
 

@@ -26,7 +26,7 @@ def approx_qparams(expo_width=4, mant_width=3, dnsmp_factor=3, withComp=False, w
                    with_UF_opt=False, weight_range_method="current_minmax", weight_range_options=None,
                    act_range_method="allminmax", act_range_options=None, mse_include_mantissa_bits=False,
                    error_table=None, ste_backward=False, learn_maxval=False, grad_split_k=1,
-                   conv_backward="im2col"):
+                   conv_backward="im2col", bn_backward="torch"):
     """qparams exactly as the reference scripts build them (utils/click_options.py:544-606,
     scripts/generated_scripts.py): per-channel current_minmax weights, allminmax activations,
     quantize_input, FP8 quantizer with set_maxval, approx + res_quantizer run method.
@@ -42,6 +42,9 @@ def approx_qparams(expo_width=4, mant_width=3, dnsmp_factor=3, withComp=False, w
     GEMMs split their reduction along K (approx_ops.grad_bmm's split_k), nothing without ste_backward;
     conv_backward (custom_approx_params["conv_backward"]: "implicit" or "depthwise"; "im2col" = off): the convolutions' backward on
     the implicit-GEMM kernels (approx_ops.ste_conv2d's backward), nothing without ste_backward;
+    bn_backward (custom_approx_params["bn_backward"]: "fused"; "torch" = off): a training-mode batch norm that
+    autograd records runs on the deterministic kernels in both directions (approx_ops.bn_train_ste), nothing without
+    ste_backward;
     learn_maxval (the reference's --fp8-learn-maxval): every FP8 quantizer is built so that learn_ranges()
     turns its maxval into a Parameter (needs ste_backward for its gradient).
 
@@ -71,6 +74,7 @@ def approx_qparams(expo_width=4, mant_width=3, dnsmp_factor=3, withComp=False, w
                                   **({"ste_backward": True} if ste_backward else {}),
                                   **({"grad_split_k": grad_split_k} if grad_split_k != 1 else {}),
                                   **({"conv_backward": conv_backward} if conv_backward != "im2col" else {}),
+                                  **({"bn_backward": bn_backward} if bn_backward != "torch" else {}),
                                   **({"approx_version": 5} if approx_version == 5 else {})),
         run_method=dict(run_method) if run_method else dict(
             approx_flag=True, quantize_after_mult_and_add=False, res_quantizer_flag=True, original_quantize_res=False))

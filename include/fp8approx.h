@@ -838,6 +838,27 @@ int fp8a_bn_train(const float *x, float *y, int64_t N, int64_t C, int64_t inner,
                   int q_n_bits, int q_mbits, int q_sign_bits, float *q_bias, int32_t *q_ibias,
                   void *workspace, size_t workspace_bytes, fp8a_stream_t stream);
 
+/*
+ * The backward of fp8a_bn_train's y = clamp(x * scale + shift) (csrc/bn_bwd.h), from the forward's own
+ * x (the pre-BN product), save_mean, save_var and scale_shift, and dy (fp32, contiguous, x's layout):
+ *   g = dy where act = 0 or lo < fmaf(x, scale, shift) < hi, else 0 (a select: dy = inf there adds nothing);
+ *   invstd = 1 / sqrt(save_var + eps);  G = sum g,  H = sum g (x - save_mean), in double, fixed order;
+ *   dbeta = G, dgamma = H invstd (fp32 [C]; NULL: not written);
+ *   dx = k1 g + k2 (x - save_mean) + k3 with k1 = gamma invstd (gamma NULL: 1), k2 = -k1 invstd^2 H / n,
+ *   k3 = -k1 G / n, each computed in double and rounded to fp32 once; dx may be dy.
+ * No floating-point atomics; the split of a channel over workgroups depends on the shape alone: two
+ * calls return identical bytes.  The error bound of every output is derived in csrc/bn_bwd.h.
+ * Every check runs before any launch, and they are fp8a_bn_train's: FP8A_EFORMAT for n == 1;
+ * FP8A_EINVAL for empty extents, inner >= 2^31 - 4096, act outside {0, 1}, null pointers (gamma, dgamma
+ * and dbeta may be NULL), a workspace that is too small or not 16-byte aligned.
+ * fp8a_bn_train_backward_workspace_size is host-only and returns 0 for bad arguments.
+ */
+size_t fp8a_bn_train_backward_workspace_size(int64_t N, int64_t C, int64_t inner);
+int fp8a_bn_train_backward(const float *x, const float *dy, float *dx, int64_t N, int64_t C, int64_t inner,
+                           const float *gamma, const float *save_mean, const float *save_var, float eps,
+                           const float *scale_shift, int act, float lo, float hi, float *dgamma,
+                           float *dbeta, void *workspace, size_t workspace_bytes, fp8a_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

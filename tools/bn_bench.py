@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Times the BN re-estimation's training-mode forward and the bn_train kernels on one GPU.
 
-    python tools/bn_bench.py [--output profiles/bn_measure.json] [--reps 20]
+    python tools/bn_bench.py [--output profiles/bn_measure.json] [--reps 20] [--backward]
 
   * one re-estimation batch (every BN-fused layer in training mode at momentum 1, as
     bn_reestimate.reestimate_bn_stats runs it) of MobileNetV2 and ResNet-18 at 224 x 224, batch 16
@@ -12,6 +12,10 @@
     (bn_stats_kernel + bn_finalize_kernel; one read of x) and the whole in-place call (+ bn_apply_kernel;
     one more read and one write), against their byte floors at the 6.3 TB/s a float4 copy reaches;
     the apply kernel's own time is the difference of the two calls.
+  * --backward (instead of the above): the backward of one BN + ReLU6 layer, bn_train_backward (csrc/bn_bwd.h)
+    against the autograd of F.batch_norm(training=True) + hardtanh on the same tensors, the two alternating in the
+    timed loop, on the ResNet-18 stem, MobileNetV2 features.2 expand and the 14 x 14 x 576 and 7 x 7 x 960 layers at
+    batch 16 and 64; with the byte floor of the form the shape takes (5 passes general, 3 resident).
 HIP events around each call, warm-up, at least 20 repeats; median, min and max in ms.
 """
 import argparse
@@ -24,7 +28,7 @@ import torch
 from torch import nn
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from fp8_quantization_amd.approx_ops import bn_train  # noqa: E402
+from fp8_quantization_amd.approx_ops import bn_train, bn_train_backward  # noqa: E402
 from fp8_quantization_amd.bn_reestimate import bn_fused_layers  # noqa: E402
 
 DEV = "cuda:0"
@@ -120,16 +124,57 @@ def kernel_rows(reps):
     return rows
 
 
+BACKWARD_LAYERS = (("resnet18 stem", 64, 112), ("mobilenet_v2 features.2 expand", 96, 112),
+                   ("mobilenet_v2 14x14x576", 576, 14), ("mobilenet_v2 7x7x960", 960, 7))
+
+
+def backward_rows(reps):
+    rows = []
+    for name, C, hw in BACKWARD_LAYERS:
+        for batch in (16, 64):
+            x = torch.randn((batch, C, hw, hw), device=DEV)
+            dy = torch.randn_like(x)
+            gamma, beta = torch.rand(C, device=DEV) + 0.5, torch.randn(C, device=DEV)
+            _, sm, sv, ss, _ = bn_train(x, gamma, beta, None, None, 0.1, 1e-5, activation=nn.ReLU6())
+            dx = torch.empty_like(x)
+            xg, gg, bg = (t.clone().requires_grad_() for t in (x, gamma, beta))
+            y = nn.functional.hardtanh(nn.functional.batch_norm(xg, None, None, gg, bg, True, 0.1, 1e-5), 0.0, 6.0)
+            calls = dict(fused=lambda: bn_train_backward(x, dy, gamma, sm, sv, ss, 1e-5, activation=nn.ReLU6(), out=dx),
+                         torch=lambda: torch.autograd.grad(y, (xg, gg, bg), dy, retain_graph=True))
+            for fn in list(calls.values()) * 3:
+                fn()
+            torch.cuda.synchronize()
+            ts = {k: [] for k in calls}
+            for _ in range(reps):
+                for k, fn in calls.items():
+                    ts[k].append(event_ms(fn))
+            resident = batch * hw * hw <= 4096
+            row = dict(layer=name, shape=list(x.shape), form="resident" if resident else "general",
+                       fused=summary(ts["fused"]), torch=summary(ts["torch"]),
+                       floor_ms=(3 if resident else 5) * 4 * x.numel() / HBM * 1e3)
+            row["torch_over_fused"] = row["torch"]["median_ms"] / row["fused"]["median_ms"]
+            row["share_of_floor"] = row["floor_ms"] / row["fused"]["median_ms"]
+            print(json.dumps(row), flush=True)
+            rows.append(row)
+            del x, dy, dx, xg, y
+            torch.cuda.empty_cache()
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--output", default=None)
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--arch", nargs="*", default=["mobilenet_v2", "resnet18"])
+    ap.add_argument("--backward", action="store_true", help="time the backward kernels instead (see above)")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise RuntimeError("bn_bench needs a HIP device")
     reps = max(20, args.reps)
-    out = dict(kernels=kernel_rows(reps), models=[r for a in args.arch for r in model_rows(a, reps)])
+    if args.backward:
+        out = dict(backward=backward_rows(reps))
+    else:
+        out = dict(kernels=kernel_rows(reps), models=[r for a in args.arch for r in model_rows(a, reps)])
     if args.output:
         os.makedirs(os.path.dirname(os.path.abspath(args.output)), exist_ok=True)
         with open(args.output, "w") as f:
