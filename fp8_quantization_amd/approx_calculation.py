@@ -423,13 +423,16 @@ class ApproxMatMulMixin(ApproxOpMixin):
         if (self.custom_approx_params or {}).get("approx_version", 9) == 5:
             raise NotImplementedError(f"{name}: approx_version 5 has no batched product")
 
-    def forward(self, a, b, out=None):
+    def forward(self, a, b, out=None, a_quantized=False):
         """a [..., M, K] @ b [..., K, N] (any views: heads cut from [B, S, H*d], a transposed b); out: None, or
-        the view (unit n stride) that receives the product."""
+        the view (unit n stride) that receives the product.  a_quantized (default off): a already went through
+        ``a_quantizer``'s arithmetic and its custom_bias is set (the fused attention softmax), so
+        that quantizer is skipped; everything after it sees the operand it always saw."""
         self._check_supported()
         self._ste_on()  # (the quantizers below learn the layer's ste_backward switch)
         if self._qa():
-            a = self.a_quantizer(a)
+            if not a_quantized:
+                a = self.a_quantizer(a)
             b = self.b_quantizer(b)
         res = None
         if not self.fix_ranges_flag or self.original_quantize_res:

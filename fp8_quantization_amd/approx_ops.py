@@ -27,7 +27,9 @@ __all__ = ["custom_matmul_vectorize", "approx_matmul", "approx_bmm", "approx_mat
            "dense_conv2d", "grouped_conv2d", "dense_conv2d_fused", "approx_matmul_check", "approx_conv2d_check", "approx_bmm_check",
            "CheckStats", "format_self_check", "SELF_CHECK_LABELS", "fp8_mse_losses", "bn_train", "bn_train_backward", "bn_train_ste", "grad_bmm", "grad_split_auto",
            "grad_conv2d_input", "grad_conv2d_weight", "grad_dwconv2d_input", "grad_dwconv2d_weight",
-           "ste_linear", "ste_bmm", "ste_conv2d", "fp8_fake_quantize_train", "fp8_fake_quantize_backward"]
+           "ste_linear", "ste_bmm", "ste_conv2d", "fp8_fake_quantize_train", "fp8_fake_quantize_backward",
+           "attention_softmax", "attention_softmax_backward", "attention_softmax_ste", "ATTENTION_SOFTMAXES",
+           "check_attention_softmax"]
 
 
 def make_flags(with_approx=True, with_s2nn2s_opt=False, quant_btw_mult_accu=True, golden_clip_OF=False,
@@ -1101,6 +1103,120 @@ def bn_train_ste(x, gamma, beta, running_mean, running_var, momentum, eps, activ
     if _clamp_of(activation) is None:
         return None
     return _BnTrainSTE.apply(x, gamma, beta, running_mean, running_var, momentum, eps, activation)
+
+
+# ----------------------------------------------------------------------------------- attention softmax
+ATTENTION_SOFTMAXES = ("torch", "fused")
+ATTENTION_SOFTMAX_MAX = 4096  # the longest row of csrc/attn_softmax.h
+
+
+def check_attention_softmax(value, what="attention_softmax"):
+    """The path from approximate attention's raw scores to the PV operand: "torch" (the scale, torch.softmax and the
+    operand's fake quantizer, one pass each) or "fused" (attention_softmax: one pass of csrc/attn_softmax.h each
+    way); anything else is a ValueError naming `what`."""
+    if isinstance(value, str) and value in ATTENTION_SOFTMAXES:
+        return value
+    raise ValueError(f"{what} must be one of {ATTENTION_SOFTMAXES}, got {value!r}")
+
+
+def _attn_operands(who, scores, quantizer):
+    if not scores.is_cuda:
+        raise RuntimeError("fp8approx kernels need HIP device tensors (no CPU fallback)")
+    if scores.dim() < 1 or scores.dtype != torch.float32 or not scores.is_contiguous():
+        raise AssertionError(f"{who}: scores must be a contiguous float32 tensor [..., n]")
+    n = scores.shape[-1]
+    if scores.numel() == 0 or n > ATTENTION_SOFTMAX_MAX:
+        raise AssertionError(f"{who}: empty scores or rows longer than {ATTENTION_SOFTMAX_MAX}")
+    mx, nb, mb, sb = (None, 0, 0, 0)
+    if quantizer is not None:
+        with torch.no_grad():
+            mx, nb, mb, sb = _quantizer_args(quantizer)
+            if mx.device != scores.device:
+                mx = mx.to(scores.device)
+    return scores.numel() // n, n, mx, nb, mb, sb
+
+
+def attention_softmax(scores, scale, quantizer=None, out=None):
+    """fake_quantize(softmax(scale * scores, dim=-1)) in one pass (fp8a_attn_softmax, csrc/attn_softmax.h): scores
+    is a contiguous float32 HIP tensor [..., n], n <= 4096; quantizer None or the per-tensor
+    ``(maxval, n_bits, mantissa_bits, sign_bits)``, bit for bit fp8_fake_quantize on the probabilities.  out: the
+    tensor that receives y (not scores: the kernels never write their input).
+
+    Returns (y, the quantizer's float bias as fp8_fake_quantize returns it, or None)."""
+    L = _lib.load()
+    rows, n, mx, nb, mb, sb = _attn_operands("attention_softmax", scores, quantizer)
+    scores = scores.detach()
+    if out is None:
+        y = torch.empty_like(scores)
+    else:
+        if out.shape != scores.shape or out.dtype != torch.float32 or not out.is_contiguous() or \
+                out.device != scores.device or out.data_ptr() == scores.data_ptr():
+            raise AssertionError("attention_softmax: out must match scores (contiguous float32) and not be scores")
+        y = out
+    bias = ibias = None
+    if mx is not None:
+        bias = torch.empty(1, dtype=torch.float32, device=scores.device)
+        ibias = torch.empty(1, dtype=torch.int32, device=scores.device)
+    rc = L.fp8a_attn_softmax(_lib.dev_ptr(scores), rows, n, float(scale), _lib.dev_ptr(mx), nb, mb, sb, _lib.dev_ptr(y),
+                             _lib.dev_ptr(bias), _lib.dev_ptr(ibias), _lib.stream_ptr(scores.device))
+    _lib.check(rc, "fp8a_attn_softmax")
+    if bias is not None:
+        bias._fp8a_i32 = ibias
+    return y, bias
+
+
+def attention_softmax_backward(scores, g, scale, quantizer=None, out=None):
+    """The backward of attention_softmax in one pass (fp8a_attn_softmax_backward): from the forward's scores and g,
+    the gradient of its output, the gradient of the scores -- the probabilities recomputed bit for bit, the
+    quantizer's clamp weight (fp8_fake_quantize_backward's: 1 inside, 1/2 on a bound, 0 outside), the softmax's
+    Jacobian with its row sum in double in a fixed order.  out: the tensor that receives it (may be g)."""
+    L = _lib.load()
+    rows, n, mx, nb, mb, sb = _attn_operands("attention_softmax_backward", scores, quantizer)
+    if g.shape != scores.shape or g.device != scores.device:
+        raise AssertionError("attention_softmax_backward: g must match scores")
+    if g.dtype != torch.float32 or not g.is_contiguous():
+        if out is g:
+            raise AssertionError("attention_softmax_backward: in place needs a contiguous float32 g")
+        g = _as_f32(g).contiguous()
+    if out is None:
+        ds = torch.empty_like(scores)
+    else:
+        if out.shape != scores.shape or out.dtype != torch.float32 or not out.is_contiguous() or \
+                out.device != scores.device:
+            raise AssertionError("attention_softmax_backward: out must match scores (contiguous float32)")
+        ds = out
+    rc = L.fp8a_attn_softmax_backward(_lib.dev_ptr(scores.detach()), _lib.dev_ptr(g.detach()), rows, n, float(scale),
+                                      _lib.dev_ptr(mx), nb, mb, sb, _lib.dev_ptr(ds), _lib.stream_ptr(scores.device))
+    _lib.check(rc, "fp8a_attn_softmax_backward")
+    return ds
+
+
+class _AttentionSoftmaxSTE(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, scores, scale, quantizer, bias_box):
+        with _ste_timed("attn_softmax_forward"):
+            y, bias = attention_softmax(scores, scale, quantizer)
+        bias_box.append(bias)
+        ctx.save_for_backward(scores)  # (a reference: nothing else is kept)
+        ctx.scale, ctx.quantizer = scale, quantizer
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        (scores,) = ctx.saved_tensors
+        with _ste_timed("attn_softmax_backward"):
+            ds = attention_softmax_backward(scores, g, ctx.scale, ctx.quantizer)
+        return ds, None, None, None
+
+
+def attention_softmax_ste(scores, scale, quantizer=None):
+    """attention_softmax for a forward that autograd records: saves the scores alone (no probabilities, no code
+    bytes), and its backward is ONE attention_softmax_backward call.  The quantizer's maxval is a constant here (a
+    learned range keeps the torch path).  Under finetune's profile the two directions are timed as
+    "attn_softmax_forward" and "attn_softmax_backward".  Returns (y, bias or None) as attention_softmax."""
+    box = []
+    y = _AttentionSoftmaxSTE.apply(scores, float(scale), quantizer, box)
+    return y, box[0]
 
 
 # ----------------------------------------------------------------------------------- FP8 fake quant

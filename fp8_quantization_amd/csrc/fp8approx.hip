@@ -34,6 +34,7 @@
 #include "fq_train.h"
 #include "bn_train.h"
 #include "bn_bwd.h"
+#include "attn_softmax.h"
 #include "gemm_bmm.h"
 #include "gemm_grad.h"
 #include "gemm_grad_conv.h"
@@ -3619,6 +3620,46 @@ int fp8a_bn_train_backward(const float *x, const float *dy, float *dx, int64_t N
     a.vec = inner % 4 == 0 && (((uintptr_t)x | (uintptr_t)dy | (uintptr_t)dx) & 15) == 0;
     launch_bn_train_backward(a, (hipStream_t)stream);
     return hip_check("fp8a_bn_train_backward");
+}
+
+// The attention softmax block (attn_softmax.h): no workspace.  Every check is shared by the two directions and
+// runs before the launch; the quantizer's format is read only with a maxval.
+static const char *attn_bad(int64_t rows, int64_t n, const float *maxval, int n_bits, int Mbits, int sign_bits) {
+    if (rows < 0 || rows > INT32_MAX) return "rows must be in [0, 2^31)";
+    if (n < 1 || n > ATTN_MAX) return "the row length n must be in [1, 4096]";
+    if (maxval && (Mbits < 1 || n_bits - sign_bits - Mbits < 1 || sign_bits < 0 || sign_bits > 1))
+        return "bad FP8 quantizer format";
+    return nullptr;
+}
+static AttnArgs attn_args(const float *s, int64_t rows, int64_t n, float scale, const float *maxval, int n_bits,
+                          int Mbits, int sign_bits, float *out) {
+    AttnArgs a{};
+    a.rows = rows; a.n = (int)n; a.scale = scale; a.s = s; a.out = out; a.maxval = maxval;
+    a.E = n_bits - sign_bits - Mbits; a.M = Mbits; a.S = sign_bits; a.fq_fast = opt(OPT_FQ_FAST);
+    return a;
+}
+
+int fp8a_attn_softmax(const float *s, int64_t rows, int64_t n, float scale, const float *maxval, int n_bits,
+                      int Mbits, int sign_bits, float *y, float *bias_out, int32_t *ibias_out, fp8a_stream_t stream) {
+    if (const char *bad = attn_bad(rows, n, maxval, n_bits, Mbits, sign_bits)) return fail(FP8A_EINVAL, bad);
+    if (s == nullptr || y == nullptr) return fail(FP8A_EINVAL, "null pointer");
+    if (rows == 0) return FP8A_OK;
+    AttnArgs a = attn_args(s, rows, n, scale, maxval, n_bits, Mbits, sign_bits, y);
+    a.bias_out = bias_out; a.ibias_out = ibias_out;
+    launch_attn_softmax(a, false, (hipStream_t)stream);
+    return hip_check("fp8a_attn_softmax");
+}
+
+int fp8a_attn_softmax_backward(const float *s, const float *g, int64_t rows, int64_t n, float scale,
+                               const float *maxval, int n_bits, int Mbits, int sign_bits, float *ds,
+                               fp8a_stream_t stream) {
+    if (const char *bad = attn_bad(rows, n, maxval, n_bits, Mbits, sign_bits)) return fail(FP8A_EINVAL, bad);
+    if (s == nullptr || g == nullptr || ds == nullptr) return fail(FP8A_EINVAL, "null pointer");
+    if (rows == 0) return FP8A_OK;
+    AttnArgs a = attn_args(s, rows, n, scale, maxval, n_bits, Mbits, sign_bits, ds);
+    a.g = g;
+    launch_attn_softmax(a, true, (hipStream_t)stream);
+    return hip_check("fp8a_attn_softmax_backward");
 }
 
 // The config-1 layer (approx_flag off) in one launch family: fq_in on the loaded input, the exact

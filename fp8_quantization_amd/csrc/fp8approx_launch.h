@@ -67,4 +67,9 @@ struct FqtArgs;
 void launch_fqt_forward(const FqtArgs &a, hipStream_t s);
 void launch_fqt_backward(const FqtArgs &a, hipStream_t s);
 
+// k_attn.hip: the attention softmax block (attn_softmax.h) -- one launch either way, the wave-per-row kernel of
+// the row length's V or the workgroup-per-row kernel.
+struct AttnArgs;
+void launch_attn_softmax(const AttnArgs &a, bool backward, hipStream_t s);
+
 }  // namespace fp8a

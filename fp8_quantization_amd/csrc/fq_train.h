@@ -87,7 +87,7 @@ static inline int64_t fqt_parts(int64_t rows, int64_t inner, int64_t target) {
 // The ordered reduction's form, by the split alone: a wave per row from this many parts on.
 static inline bool fqt_reduce_by_wave(int64_t parts) { return parts > 16; }
 
-#if FP8A_OWN_FQT
+// (the code and its weights: also attn_softmax.h's clamp weight, so outside the kernels' guard)
 __device__ __forceinline__ uint32_t fqt_code(float x, float lo, float mx, int S) {
     const uint32_t twice = (uint32_t)((x > lo) & (x < mx)) + (uint32_t)((x >= lo) & (x <= mx));
     const uint32_t side = (x >= mx) ? 1u : (S && x <= lo) ? 2u : 0u;
@@ -102,6 +102,7 @@ __device__ __forceinline__ void fqt_weights(uint32_t c, int S, float &wx, float 
     wm = side == 1u ? h : (side == 2u && S) ? -h : 0.0f;
 }
 
+#if FP8A_OWN_FQT
 // The constants of one row's quantizer.
 struct FqtRow {
     float mx, lo, bias;

@@ -11,6 +11,7 @@ the production kernel's distance from the literal check kernel in units of the p
 
     python -m fp8_quantization_amd.error_report --arch resnet18 --batch 16 [--size 224] [--json]
                                                 [--error-table FILE] [--approx-attention]
+                                                [--attention-softmax torch|fused]
 
 builds the synthetic calibrated workload of the benchmark's workload modules (random weights, BN
 statistics estimated on synthetic batches, one calibration batch, fixed ranges) and prints the table.
@@ -160,11 +161,16 @@ def main(argv=None):
                     help="a custom error table (.npy or text rows) in place of the built-in one")
     ap.add_argument("--approx-attention", action="store_true",
                     help="--arch vit_b16: QK^T and PV through the multiplier too (two matmul rows per layer)")
+    ap.add_argument("--attention-softmax", default="torch", choices=("torch", "fused"),
+                    help="with --approx-attention: the softmax block between the two products in torch, or as one "
+                         "kernel pass (DESIGN.md §3al)")
     args = ap.parse_args(argv)
     if args.approx_attention and args.arch != "vit_b16":
         ap.error("--approx-attention needs --arch vit_b16")
     cfg = dict(expo_width=args.expo_width, mant_width=args.mant_width, dnsmp_factor=3, withComp=args.with_comp,
                with_approx=True, with_s2nn2s_opt=not args.no_s2n, quant_btw_mult_accu=True)
+    if args.attention_softmax != "torch":
+        cfg["attention_softmax"] = args.attention_softmax
     digest = None
     if args.error_table:
         from .error_tables import load_error_table, table_digest

@@ -5,7 +5,7 @@ quantizer masks, the exact product's gradients on the gradient GEMM fp8a_grad_bm
     python -m fp8_quantization_amd.finetune --synthetic 64 --arch resnet18|mobilenet_v2|vit_b16 \
         --steps 10 --lr 1e-3 [--batch-size 64] [--momentum 0.9] [--approx-attention] \
         [--learn-ranges [--range-lr 1e-4]] [--grad-split-k N|auto] [--conv-backward im2col|implicit]
-        [--train-bn [--bn-backward torch|fused]] [--seed 0]
+        [--train-bn [--bn-backward torch|fused]] [--attention-softmax torch|fused] [--seed 0]
 
 A driver, not a trainer (no schedule, checkpoints or augmentation): it calibrates and fixes the FP8 ranges as
 the validation driver does (imagenet.py: estimate_ranges over --num-est-batches batches, fix_ranges), keeps the
@@ -32,6 +32,10 @@ batch norm normalizes with the batch statistics and updates its running buffers,
 does.  --bn-backward fused runs that batch norm on the deterministic kernels in both directions:
 custom_approx_params["bn_backward"]; default torch, F.batch_norm and its autograd.  With either flag each record
 gains bn_ms, the recorded milliseconds of the fused forward + backward calls (0 on the torch path, which records none).
+--attention-softmax fused (with --approx-attention): the scale, the softmax and the PV operand's quantizer between the two
+attention products run as one kernel pass forward and one backward: custom_approx_params
+["attention_softmax"]; default torch.  With the flag each record gains attn_softmax_ms, the recorded milliseconds of
+those calls.
 Data: --synthetic N random images and labels, or <images-dir>/train as imagenet.py reads it.
 """
 import argparse
@@ -89,6 +93,9 @@ def parse(argv=None):
                     help="the BN-fused layers train on batch statistics (the rest of the model stays in eval mode)")
     ap.add_argument("--bn-backward", default="torch", choices=list(approx_ops.BN_BACKWARDS),
                     help="a recorded training-mode batch norm: F.batch_norm and its autograd, or the deterministic kernels")
+    ap.add_argument("--attention-softmax", default="torch", choices=list(approx_ops.ATTENTION_SOFTMAXES),
+                    help="with --approx-attention: the scale, softmax and PV operand quantizer in torch, or as one kernel "
+                         "pass each way")
     ap.add_argument("--output", default=None, help="also write the step records (a JSON list) here")
     return ap.parse_args(argv)
 
@@ -106,6 +113,8 @@ def approx_cfg(args):
         cfg["conv_backward"] = args.conv_backward
     if getattr(args, "bn_backward", "torch") != "torch":
         cfg["bn_backward"] = args.bn_backward
+    if getattr(args, "attention_softmax", "torch") != "torch":
+        cfg["attention_softmax"] = args.attention_softmax
     return cfg
 
 
@@ -171,6 +180,9 @@ def finetune(model, data, args, dev):
                        quantizer_ms=_events_ms(prof.get("fq_forward", ())) + _events_ms(prof.get("fq_backward", ())))
             if bn_flags:
                 rec.update(bn_ms=_events_ms(prof.get("bn_forward", ())) + _events_ms(prof.get("bn_backward", ())))
+            if getattr(args, "attention_softmax", "torch") != "torch":
+                rec.update(attn_softmax_ms=_events_ms(prof.get("attn_softmax_forward", ())) +
+                           _events_ms(prof.get("attn_softmax_backward", ())))
             if ranges:
                 now = torch.cat([p.detach().reshape(-1) for p in ranges])
                 rec.update(max_range_change=float(((now - cal0).abs() / cal0.abs()).max()),

@@ -184,6 +184,9 @@ def parse(argv=None):
                          "built-in one: error_tables.load_error_table")
     ap.add_argument("--approx-attention", action="store_true",
                     help="ViT only: QK^T and PV of every attention through the approx multiplier (batched products)")
+    ap.add_argument("--attention-softmax", default="torch", choices=["torch", "fused"],
+                    help="with --approx-attention: the scale, softmax and PV operand quantizer in torch, or as one "
+                         "kernel pass (DESIGN.md §3al)")
     ap.add_argument("--output", default=None, help="also write the result JSON here")
     return ap.parse_args(argv)
 
@@ -293,6 +296,8 @@ def approx_cfg(args):
                                  original_quantize_res=True)
     if getattr(args, "approx_attention", False):
         cfg["approx_attention"] = True
+    if getattr(args, "attention_softmax", "torch") != "torch":
+        cfg["attention_softmax"] = args.attention_softmax
     if getattr(args, "error_table", None):
         from .error_tables import load_error_table
         cfg["error_table"] = load_error_table(args.error_table, args.mant_width)  # read once, here

@@ -93,6 +93,16 @@ def bn_backward(module):
                              "custom_approx_params['bn_backward']")
 
 
+def attention_softmax(module):
+    """custom_approx_params['attention_softmax'] of a module: the path from approximate attention's raw scores to the
+    PV operand (QuantizedViTSelfAttention._approx_attention).  Absent or "torch": the scale, torch.softmax and the
+    operand's quantizer; "fused": approx_ops.attention_softmax, one kernel pass each way; anything else raises
+    ValueError (at construction too).  Nothing without approx_attention."""
+    from ..approx_ops import check_attention_softmax
+    return check_attention_softmax((getattr(module, "custom_approx_params", None) or {}).get("attention_softmax", "torch"),
+                                   "custom_approx_params['attention_softmax']")
+
+
 def _version5(module):
     return (getattr(module, "custom_approx_params", None) or {}).get("approx_version", 9) == 5
 
@@ -111,6 +121,7 @@ class QuantizedModule(nn.Module):
         grad_split_k(self)  # (a value the backward cannot take raises here, not in the first backward)
         conv_backward(self)
         bn_backward(self)
+        attention_softmax(self)
         self.run_method = kwargs.pop("run_method", None) or dict(_DEFAULT_RUN_METHOD)
         self.approx_flag = self.run_method["approx_flag"]
         self.quantize_after_mult_and_add = self.run_method["quantize_after_mult_and_add"]

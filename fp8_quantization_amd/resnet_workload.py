@@ -26,7 +26,7 @@ def approx_qparams(expo_width=4, mant_width=3, dnsmp_factor=3, withComp=False, w
                    with_UF_opt=False, weight_range_method="current_minmax", weight_range_options=None,
                    act_range_method="allminmax", act_range_options=None, mse_include_mantissa_bits=False,
                    error_table=None, ste_backward=False, learn_maxval=False, grad_split_k=1,
-                   conv_backward="im2col", bn_backward="torch"):
+                   conv_backward="im2col", bn_backward="torch", attention_softmax="torch"):
     """qparams exactly as the reference scripts build them (utils/click_options.py:544-606,
     scripts/generated_scripts.py): per-channel current_minmax weights, allminmax activations,
     quantize_input, FP8 quantizer with set_maxval, approx + res_quantizer run method.
@@ -45,6 +45,9 @@ def approx_qparams(expo_width=4, mant_width=3, dnsmp_factor=3, withComp=False, w
     bn_backward (custom_approx_params["bn_backward"]: "fused"; "torch" = off): a training-mode batch norm that
     autograd records runs on the deterministic kernels in both directions (approx_ops.bn_train_ste), nothing without
     ste_backward;
+    attention_softmax (custom_approx_params["attention_softmax"]: "fused"; "torch" = off): approximate attention's
+    scale, softmax and PV operand quantizer as one kernel pass each way (approx_ops.attention_softmax), nothing
+    without the ViT's approx_attention;
     learn_maxval (the reference's --fp8-learn-maxval): every FP8 quantizer is built so that learn_ranges()
     turns its maxval into a Parameter (needs ste_backward for its gradient).
 
@@ -75,6 +78,7 @@ def approx_qparams(expo_width=4, mant_width=3, dnsmp_factor=3, withComp=False, w
                                   **({"grad_split_k": grad_split_k} if grad_split_k != 1 else {}),
                                   **({"conv_backward": conv_backward} if conv_backward != "im2col" else {}),
                                   **({"bn_backward": bn_backward} if bn_backward != "torch" else {}),
+                                  **({"attention_softmax": attention_softmax} if attention_softmax != "torch" else {}),
                                   **({"approx_version": 5} if approx_version == 5 else {})),
         run_method=dict(run_method) if run_method else dict(
             approx_flag=True, quantize_after_mult_and_add=False, res_quantizer_flag=True, original_quantize_res=False))

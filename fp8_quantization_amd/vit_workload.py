@@ -27,9 +27,12 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
+from . import approx_ops
 from .approx_calculation import QCustomLinearTorch, QCustomMatMul
 from .model_wrap import QuantizedModel, fused_linear_tail, quantize_model
-from .quantization.base_quantized_classes import QuantizedActivation
+from .quantization.base_quantized_classes import QuantizedActivation, attention_softmax
+from .quantization.fp8_quantizer import FPQuantizer
+from .quantization.quantization_manager import Qstates
 
 
 # ------------------------------------------------------------------------- float ViT (HF layout)
@@ -292,13 +295,46 @@ class QuantizedViTSelfAttention(QuantizedActivation):
             return t.view(t.shape[:-1] + (H, d)).permute(0, 2, 1, 3)
         q, k, v = heads(self.query(x)), heads(self.key(x)), heads(self.value(x))
         scores = self.qk_matmul(q, k.transpose(-1, -2))
+        ctx = torch.empty(x.shape[:-1] + (H, d), dtype=torch.float32, device=x.device)
+        probs = self._fused_probs(scores, d ** -0.5)
+        if probs is not None:  # already pv_matmul's quantized A operand
+            self.pv_matmul(probs, v, out=ctx.permute(0, 2, 1, 3), a_quantized=True)
+            return ctx.view(x.shape[:-1] + (self.all_head_size,))
         probs = torch.softmax(scores * d ** -0.5, dim=-1)
         p = self.attention_probs_dropout_prob
         if self.training and p > 0:
             probs = F.dropout(probs, p, True)
-        ctx = torch.empty(x.shape[:-1] + (H, d), dtype=torch.float32, device=x.device)
         self.pv_matmul(probs, v, out=ctx.permute(0, 2, 1, 3))
         return ctx.view(x.shape[:-1] + (self.all_head_size,))
+
+    def _fused_probs(self, scores, scale):
+        """custom_approx_params['attention_softmax'] = "fused": the scale, the softmax and pv_matmul's a_quantizer as
+        one kernel pass (approx_ops.attention_softmax; under ste_backward attention_softmax_ste, one pass back too).
+        Returns the quantized operand, with the quantizer's custom_bias set, or None where the torch lines run: the
+        key absent or "torch", scores that are not a contiguous fp32 HIP tensor with rows of at most 4096, active
+        attention dropout, or an a_quantizer that is not a per-tensor FP8 quantizer in the fixed-range state with a
+        constant maxval (range estimation, MSE search and learned ranges read or train on the probabilities)."""
+        if attention_softmax(self) != "fused":
+            return None
+        if not (scores.is_cuda and scores.dtype == torch.float32 and scores.is_contiguous() and scores.numel() > 0
+                and scores.shape[-1] <= approx_ops.ATTENTION_SOFTMAX_MAX):
+            return None
+        if self.training and self.attention_probs_dropout_prob > 0:
+            return None
+        pv, q, quantizer = self.pv_matmul, None, None
+        if pv._qa():
+            q = pv.a_quantizer.quantizer
+            if not (pv.a_quantizer.state == Qstates.fix_ranges and isinstance(q, FPQuantizer) and not q.per_channel
+                    and q.maxval.numel() == 1 and not q.maxval.requires_grad):
+                return None
+            if q.maxval.device != scores.device:  # (as FPQuantizer.forward)
+                q._assign_maxval(q.maxval.to(scores.device))
+            quantizer = (q.maxval, q.n_bits, q._mbits_int, q.sign_bits)
+        fused = approx_ops.attention_softmax_ste if pv._ste_on() else approx_ops.attention_softmax
+        probs, bias = fused(scores, scale, quantizer)
+        if q is not None:
+            q.custom_bias = bias
+        return probs
 
     def forward(self, x):
         if hasattr(self, "qk_matmul"):

@@ -859,6 +859,27 @@ int fp8a_bn_train_backward(const float *x, const float *dy, float *dx, int64_t N
                            const float *scale_shift, int act, float lo, float hi, float *dgamma,
                            float *dbeta, void *workspace, size_t workspace_bytes, fp8a_stream_t stream);
 
+/*
+ * The softmax block of approximate attention, one launch each way (csrc/attn_softmax.h): s is the raw QK^T scores,
+ * fp32 [rows][n] contiguous, 1 <= n <= 4096.
+ *   forward   p = softmax(scale * s) along n in fp32 (max subtracted, expf, IEEE division);
+ *             y = the per-tensor FP8 fake quantizer (maxval [1] on the device, n_bits, Mbits, sign_bits) of p, bit
+ *             for bit fp8a_fp8_quantize on p, and its float / int32 bias (bias_out / ibias_out [1], NULL: not
+ *             written); maxval NULL: y = p, the format arguments are not read and no bias is written.
+ *   backward  from s and g = the gradient of y: p recomputed bit for bit; gq = g w with the quantizer's clamp weight
+ *             w (1 inside (lo, maxval), 1/2 on a bound, 0 outside; 1 without a quantizer);
+ *             ds = scale * (p * (gq - (float)sum_j (double)(gq_j p_j))).  ds may be g.
+ * Sums run in a fixed order that depends on n alone, without floating-point atomics or a workspace: two calls
+ * return identical bytes.  Every check runs before the launch, and every refusal is FP8A_EINVAL: rows outside
+ * [0, 2^31), n outside [1, 4096], with a maxval a format fp8a_fq_train_forward refuses (Mbits < 1, no exponent
+ * bit, sign_bits outside {0, 1}), a null s, y, g or ds.  rows == 0 is success without a launch.
+ */
+int fp8a_attn_softmax(const float *s, int64_t rows, int64_t n, float scale, const float *maxval, int n_bits,
+                      int Mbits, int sign_bits, float *y, float *bias_out, int32_t *ibias_out, fp8a_stream_t stream);
+int fp8a_attn_softmax_backward(const float *s, const float *g, int64_t rows, int64_t n, float scale,
+                               const float *maxval, int n_bits, int Mbits, int sign_bits, float *ds,
+                               fp8a_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
