@@ -35,7 +35,8 @@ SYMBOLS = ("fp8a_version", "fp8a_last_error", "fp8a_fallback_stats", "fp8a_path_
            "fp8a_grad_dwconv2d_dgrad", "fp8a_grad_dwconv2d_wgrad_workspace_size", "fp8a_grad_dwconv2d_wgrad",
            "fp8a_fq_train_workspace_size", "fp8a_fq_train_forward", "fp8a_fq_train_backward",
            "fp8a_bn_train_backward_workspace_size", "fp8a_bn_train_backward",
-           "fp8a_attn_softmax", "fp8a_attn_softmax_backward")
+           "fp8a_attn_softmax", "fp8a_attn_softmax_backward",
+           "fp8a_layer_norm", "fp8a_layer_norm_backward_workspace_size", "fp8a_layer_norm_backward")
 
 _lib = None
 
@@ -143,6 +144,9 @@ def load():
         "fp8a_bn_train_backward": ([P, P, P, I64, I64, I64, P, P, P, F, P, I, F, F, P, P, P, SZ, P], I),
         "fp8a_attn_softmax": ([P, I64, I64, F, P, I, I, I, P, P, P, P], I),
         "fp8a_attn_softmax_backward": ([P, P, I64, I64, F, P, I, I, I, P, P], I),
+        "fp8a_layer_norm": ([P, I64, I64, P, P, F, P, I, I, I, P, P, P, P, P, P], I),
+        "fp8a_layer_norm_backward_workspace_size": ([I64, I64], SZ),
+        "fp8a_layer_norm_backward": ([P, P, I64, I64, P, P, P, P, I, I, I, P, P, P, P, SZ, P], I),
     }
     for name, (args, res) in sig.items():
         f = getattr(L, name)

@@ -29,7 +29,8 @@ __all__ = ["custom_matmul_vectorize", "approx_matmul", "approx_bmm", "approx_mat
            "grad_conv2d_input", "grad_conv2d_weight", "grad_dwconv2d_input", "grad_dwconv2d_weight",
            "ste_linear", "ste_bmm", "ste_conv2d", "fp8_fake_quantize_train", "fp8_fake_quantize_backward",
            "attention_softmax", "attention_softmax_backward", "attention_softmax_ste", "ATTENTION_SOFTMAXES",
-           "check_attention_softmax"]
+           "check_attention_softmax", "layer_norm", "layer_norm_backward", "layer_norm_ste", "LAYER_NORMS",
+           "check_layer_norm"]
 
 
 def make_flags(with_approx=True, with_s2nn2s_opt=False, quant_btw_mult_accu=True, golden_clip_OF=False,
@@ -1216,6 +1217,136 @@ def attention_softmax_ste(scores, scale, quantizer=None):
     "attn_softmax_forward" and "attn_softmax_backward".  Returns (y, bias or None) as attention_softmax."""
     box = []
     y = _AttentionSoftmaxSTE.apply(scores, float(scale), quantizer, box)
+    return y, box[0]
+
+
+# ----------------------------------------------------------------------------------- layer norm
+LAYER_NORMS = ("torch", "fused")
+LAYER_NORM_MAX = 4096  # the longest row of csrc/layer_norm.h
+
+
+def check_layer_norm(value, what="layer_norm"):
+    """QuantLayerNorm's path: "torch" (the input's fake quantizer, then F.layer_norm, one pass each) or "fused"
+    (layer_norm: one pass of csrc/layer_norm.h each way); anything else is a ValueError naming `what`."""
+    if isinstance(value, str) and value in LAYER_NORMS:
+        return value
+    raise ValueError(f"{what} must be one of {LAYER_NORMS}, got {value!r}")
+
+
+def _ln_operands(who, x, gamma, quantizer, **per_column):
+    if not x.is_cuda:
+        raise RuntimeError("fp8approx kernels need HIP device tensors (no CPU fallback)")
+    if x.dim() < 1 or x.dtype != torch.float32 or not x.is_contiguous():
+        raise AssertionError(f"{who}: x must be a contiguous float32 tensor [..., n]")
+    n = x.shape[-1]
+    if x.numel() == 0 or n > LAYER_NORM_MAX:
+        raise AssertionError(f"{who}: empty x or rows longer than {LAYER_NORM_MAX}")
+    cols = []
+    for name, t in dict(gamma=gamma, **per_column).items():
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != n or t.device != x.device:
+            raise AssertionError(f"{who}: {name} must be a contiguous float32 tensor of {n} on {x.device}")
+        cols.append(t.detach())
+    mx, nb, mb, sb = (None, 0, 0, 0)
+    if quantizer is not None:
+        with torch.no_grad():
+            mx, nb, mb, sb = _quantizer_args(quantizer)
+            if mx.device != x.device:
+                mx = mx.to(x.device)
+    return x.numel() // n, n, cols, mx, nb, mb, sb
+
+
+def _ln_out(who, out, x):
+    if out is None:
+        return torch.empty_like(x)
+    if out.shape != x.shape or out.dtype != torch.float32 or not out.is_contiguous() or out.device != x.device:
+        raise AssertionError(f"{who}: out must match x (contiguous float32)")
+    return out
+
+
+def layer_norm(x, gamma, beta, eps, quantizer=None, out=None):
+    """layer_norm(fake_quantize(x)) over the last dimension with the affine map, in one pass (fp8a_layer_norm,
+    csrc/layer_norm.h): x is a contiguous float32 HIP tensor [..., n], n <= 4096; gamma and beta float32 [n]
+    (gamma as the caller's weight quantizer left it); quantizer None or the per-tensor ``(maxval, n_bits,
+    mantissa_bits, sign_bits)``, bit for bit fp8_fake_quantize on x.  out: the tensor that receives y (not x).
+
+    Returns (y, mean [rows], rstd [rows], the quantizer's float bias as fp8_fake_quantize returns it, or None)."""
+    L = _lib.load()
+    rows, n, (gamma, beta), mx, nb, mb, sb = _ln_operands("layer_norm", x, gamma, quantizer, beta=beta)
+    x = x.detach()
+    y = _ln_out("layer_norm", out, x)
+    if y.data_ptr() == x.data_ptr():
+        raise AssertionError("layer_norm: out must not be x")
+    mean = torch.empty(rows, dtype=torch.float32, device=x.device)
+    rstd = torch.empty(rows, dtype=torch.float32, device=x.device)
+    bias = ibias = None
+    if mx is not None:
+        bias = torch.empty(1, dtype=torch.float32, device=x.device)
+        ibias = torch.empty(1, dtype=torch.int32, device=x.device)
+    rc = L.fp8a_layer_norm(_lib.dev_ptr(x), rows, n, _lib.dev_ptr(gamma), _lib.dev_ptr(beta), float(eps),
+                           _lib.dev_ptr(mx), nb, mb, sb, _lib.dev_ptr(y), _lib.dev_ptr(mean), _lib.dev_ptr(rstd),
+                           _lib.dev_ptr(bias), _lib.dev_ptr(ibias), _lib.stream_ptr(x.device))
+    _lib.check(rc, "fp8a_layer_norm")
+    if bias is not None:
+        bias._fp8a_i32 = ibias
+    return y, mean, rstd, bias
+
+
+def layer_norm_backward(x, g, gamma, mean, rstd, quantizer=None, out=None):
+    """The backward of layer_norm in one pass over the activation plus a small combine (fp8a_layer_norm_backward):
+    from the forward's x, mean and rstd and g, the gradient of its output, the gradients of x (through the
+    quantizer's clamp weight: 1 inside, 1/2 on a bound, 0 outside), gamma and beta.  xhat is recomputed bit for bit;
+    every sum is in double in a fixed order, without atomics.  out: the tensor that receives dx (may be g).
+
+    Returns (dx, dgamma, dbeta)."""
+    L = _lib.load()
+    rows, n, (gamma,), mx, nb, mb, sb = _ln_operands("layer_norm_backward", x, gamma, quantizer)
+    if g.shape != x.shape or g.device != x.device:
+        raise AssertionError("layer_norm_backward: g must match x")
+    if g.dtype != torch.float32 or not g.is_contiguous():
+        if out is g:
+            raise AssertionError("layer_norm_backward: in place needs a contiguous float32 g")
+        g = _as_f32(g).contiguous()
+    for name, t in (("mean", mean), ("rstd", rstd)):
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != rows or t.device != x.device:
+            raise AssertionError(f"layer_norm_backward: {name} must be the forward's ({rows} float32 on {x.device})")
+    dx = _ln_out("layer_norm_backward", out, x)
+    dgamma = torch.empty(n, dtype=torch.float32, device=x.device)
+    dbeta = torch.empty(n, dtype=torch.float32, device=x.device)
+    nbytes = int(L.fp8a_layer_norm_backward_workspace_size(rows, n))
+    ws = _workspace(x.device, nbytes)
+    rc = L.fp8a_layer_norm_backward(_lib.dev_ptr(x.detach()), _lib.dev_ptr(g.detach()), rows, n, _lib.dev_ptr(gamma),
+                                    _lib.dev_ptr(mean.detach()), _lib.dev_ptr(rstd.detach()), _lib.dev_ptr(mx), nb, mb,
+                                    sb, _lib.dev_ptr(dx), _lib.dev_ptr(dgamma), _lib.dev_ptr(dbeta), _lib.dev_ptr(ws),
+                                    nbytes, _lib.stream_ptr(x.device))
+    _lib.check(rc, "fp8a_layer_norm_backward")
+    return dx, dgamma, dbeta
+
+
+class _LayerNormSTE(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, gamma, beta, eps, quantizer, bias_box):
+        with _ste_timed("layer_norm_forward"):
+            y, mean, rstd, bias = layer_norm(x, gamma, beta, eps, quantizer)
+        bias_box.append(bias)
+        ctx.save_for_backward(x, gamma, mean, rstd)  # (x and gamma by reference: no quantized copy, no code bytes)
+        ctx.quantizer = quantizer
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        x, gamma, mean, rstd = ctx.saved_tensors
+        with _ste_timed("layer_norm_backward"):
+            dx, dgamma, dbeta = layer_norm_backward(x, g, gamma, mean, rstd, ctx.quantizer)
+        return dx, dgamma.view(gamma.shape), dbeta.view(gamma.shape), None, None, None
+
+
+def layer_norm_ste(x, gamma, beta, eps, quantizer=None):
+    """layer_norm for a forward that autograd records: saves x by reference plus mean and rstd, and its backward is
+    ONE layer_norm_backward call, which returns the gradients of x, gamma and beta.  The quantizer's maxval is a
+    constant here (a learned range keeps the torch path).  Under finetune's profile the two directions are timed as
+    "layer_norm_forward" and "layer_norm_backward".  Returns (y, bias or None)."""
+    box = []
+    y = _LayerNormSTE.apply(x, gamma, beta, float(eps), quantizer, box)
     return y, box[0]
 
 

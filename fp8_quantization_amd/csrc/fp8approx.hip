@@ -35,6 +35,7 @@
 #include "bn_train.h"
 #include "bn_bwd.h"
 #include "attn_softmax.h"
+#include "layer_norm.h"
 #include "gemm_bmm.h"
 #include "gemm_grad.h"
 #include "gemm_grad_conv.h"
@@ -3660,6 +3661,70 @@ int fp8a_attn_softmax_backward(const float *s, const float *g, int64_t rows, int
     a.g = g;
     launch_attn_softmax(a, true, (hipStream_t)stream);
     return hip_check("fp8a_attn_softmax_backward");
+}
+
+// The layer norm block (layer_norm.h).  Every check is shared by the two directions and runs before the launch; the
+// quantizer's format is read only with a maxval.  The float4 form: n % 4 == 0 and every tensor the call moves as
+// rows or per column on 16 bytes.
+static const char *ln_bad(int64_t rows, int64_t n, const float *maxval, int n_bits, int Mbits, int sign_bits) {
+    if (rows < 0 || rows > INT32_MAX) return "rows must be in [0, 2^31)";
+    if (n < 1 || n > LN_MAX) return "the row length n must be in [1, 4096]";
+    if (maxval && (Mbits < 1 || n_bits - sign_bits - Mbits < 1 || sign_bits < 0 || sign_bits > 1))
+        return "bad FP8 quantizer format";
+    return nullptr;
+}
+static LnArgs ln_args(const float *x, int64_t rows, int64_t n, const float *gamma, const float *maxval, int n_bits,
+                      int Mbits, int sign_bits, float *out) {
+    LnArgs a{};
+    a.rows = rows; a.n = (int)n; a.run = ln_run(rows); a.parts = (int)ln_parts(rows);
+    a.x = x; a.gamma = gamma; a.out = out; a.maxval = maxval;
+    a.E = n_bits - sign_bits - Mbits; a.M = Mbits; a.S = sign_bits; a.fq_fast = opt(OPT_FQ_FAST);
+    return a;
+}
+static bool ln_vec(int64_t n, std::initializer_list<const void *> ptrs) {
+    uintptr_t bits = (uintptr_t)(n & 3);
+    for (const void *p : ptrs) bits |= (uintptr_t)p & 15;
+    return bits == 0;
+}
+
+int fp8a_layer_norm(const float *x, int64_t rows, int64_t n, const float *gamma, const float *beta, float eps,
+                    const float *maxval, int n_bits, int Mbits, int sign_bits, float *y, float *mean, float *rstd,
+                    float *bias_out, int32_t *ibias_out, fp8a_stream_t stream) {
+    if (const char *bad = ln_bad(rows, n, maxval, n_bits, Mbits, sign_bits)) return fail(FP8A_EINVAL, bad);
+    if (x == nullptr || gamma == nullptr || beta == nullptr || y == nullptr || mean == nullptr || rstd == nullptr)
+        return fail(FP8A_EINVAL, "null pointer");
+    if (rows == 0) return FP8A_OK;
+    LnArgs a = ln_args(x, rows, n, gamma, maxval, n_bits, Mbits, sign_bits, y);
+    a.beta = beta; a.eps = eps; a.mean_out = mean; a.rstd_out = rstd;
+    a.bias_out = bias_out; a.ibias_out = ibias_out;
+    a.vec = ln_vec(n, {x, y, gamma, beta});
+    launch_layer_norm(a, false, (hipStream_t)stream);
+    return hip_check("fp8a_layer_norm");
+}
+
+size_t fp8a_layer_norm_backward_workspace_size(int64_t rows, int64_t n) {
+    if (rows < 0 || rows > INT32_MAX || n < 1 || n > LN_MAX) return 0;
+    return (size_t)ln_parts(rows) * (size_t)n * 2 * sizeof(double);
+}
+
+int fp8a_layer_norm_backward(const float *x, const float *g, int64_t rows, int64_t n, const float *gamma,
+                             const float *mean, const float *rstd, const float *maxval, int n_bits, int Mbits,
+                             int sign_bits, float *dx, float *dgamma, float *dbeta, void *workspace,
+                             size_t workspace_bytes, fp8a_stream_t stream) {
+    if (const char *bad = ln_bad(rows, n, maxval, n_bits, Mbits, sign_bits)) return fail(FP8A_EINVAL, bad);
+    if (x == nullptr || g == nullptr || gamma == nullptr || mean == nullptr || rstd == nullptr || dx == nullptr ||
+        dgamma == nullptr || dbeta == nullptr)
+        return fail(FP8A_EINVAL, "null pointer");
+    if (rows == 0) return FP8A_OK;
+    if (workspace_bytes < fp8a_layer_norm_backward_workspace_size(rows, n))
+        return fail(FP8A_EINVAL, "workspace too small");
+    if (workspace == nullptr || ((uintptr_t)workspace & 15) != 0) return fail(FP8A_EINVAL, "null or misaligned workspace");
+    LnArgs a = ln_args(x, rows, n, gamma, maxval, n_bits, Mbits, sign_bits, dx);
+    a.g = g; a.mean = mean; a.rstd = rstd; a.dgamma = dgamma; a.dbeta = dbeta;
+    a.part = static_cast<double *>(workspace);
+    a.vec = ln_vec(n, {x, g, dx, gamma});
+    launch_layer_norm(a, true, (hipStream_t)stream);
+    return hip_check("fp8a_layer_norm_backward");
 }
 
 // The config-1 layer (approx_flag off) in one launch family: fq_in on the loaded input, the exact

@@ -72,4 +72,9 @@ void launch_fqt_backward(const FqtArgs &a, hipStream_t s);
 struct AttnArgs;
 void launch_attn_softmax(const AttnArgs &a, bool backward, hipStream_t s);
 
+// k_ln.hip: the layer norm block (layer_norm.h) -- forward: one launch, the wave-per-row kernel of the row length's V
+// (float4 or scalar) or the workgroup-per-row kernel; backward: the same choice, then ln_combine_kernel.
+struct LnArgs;
+void launch_layer_norm(const LnArgs &a, bool backward, hipStream_t s);
+
 }  // namespace fp8a

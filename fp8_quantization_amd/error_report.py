@@ -11,7 +11,7 @@ the production kernel's distance from the literal check kernel in units of the p
 
     python -m fp8_quantization_amd.error_report --arch resnet18 --batch 16 [--size 224] [--json]
                                                 [--error-table FILE] [--approx-attention]
-                                                [--attention-softmax torch|fused]
+                                                [--attention-softmax torch|fused] [--layer-norm torch|fused]
 
 builds the synthetic calibrated workload of the benchmark's workload modules (random weights, BN
 statistics estimated on synthetic batches, one calibration batch, fixed ranges) and prints the table.
@@ -164,6 +164,9 @@ def main(argv=None):
     ap.add_argument("--attention-softmax", default="torch", choices=("torch", "fused"),
                     help="with --approx-attention: the softmax block between the two products in torch, or as one "
                          "kernel pass (DESIGN.md §3al)")
+    ap.add_argument("--layer-norm", default="torch", choices=("torch", "fused"),
+                    help="--arch vit_b16: the layer norms' input quantizer + norm in torch, or as one kernel pass "
+                         "(DESIGN.md §3am)")
     args = ap.parse_args(argv)
     if args.approx_attention and args.arch != "vit_b16":
         ap.error("--approx-attention needs --arch vit_b16")
@@ -171,6 +174,8 @@ def main(argv=None):
                with_approx=True, with_s2nn2s_opt=not args.no_s2n, quant_btw_mult_accu=True)
     if args.attention_softmax != "torch":
         cfg["attention_softmax"] = args.attention_softmax
+    if args.layer_norm != "torch":
+        cfg["layer_norm"] = args.layer_norm
     digest = None
     if args.error_table:
         from .error_tables import load_error_table, table_digest

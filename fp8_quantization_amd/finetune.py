@@ -5,7 +5,8 @@ quantizer masks, the exact product's gradients on the gradient GEMM fp8a_grad_bm
     python -m fp8_quantization_amd.finetune --synthetic 64 --arch resnet18|mobilenet_v2|vit_b16 \
         --steps 10 --lr 1e-3 [--batch-size 64] [--momentum 0.9] [--approx-attention] \
         [--learn-ranges [--range-lr 1e-4]] [--grad-split-k N|auto] [--conv-backward im2col|implicit]
-        [--train-bn [--bn-backward torch|fused]] [--attention-softmax torch|fused] [--seed 0]
+        [--train-bn [--bn-backward torch|fused]] [--attention-softmax torch|fused] [--layer-norm torch|fused]
+        [--seed 0]
 
 A driver, not a trainer (no schedule, checkpoints or augmentation): it calibrates and fixes the FP8 ranges as
 the validation driver does (imagenet.py: estimate_ranges over --num-est-batches batches, fix_ranges), keeps the
@@ -36,6 +37,10 @@ gains bn_ms, the recorded milliseconds of the fused forward + backward calls (0 
 attention products run as one kernel pass forward and one backward: custom_approx_params
 ["attention_softmax"]; default torch.  With the flag each record gains attn_softmax_ms, the recorded milliseconds of
 those calls.
+--layer-norm fused (--arch vit_b16): every QuantLayerNorm's input quantizer, norm and affine map run as one kernel pass
+forward and one backward plus a small combine: custom_approx_params["layer_norm"]; default torch.  With
+the flag (either value) each record gains layer_norm_ms, the recorded milliseconds of those calls (0 on the torch path,
+which records none).
 Data: --synthetic N random images and labels, or <images-dir>/train as imagenet.py reads it.
 """
 import argparse
@@ -96,6 +101,8 @@ def parse(argv=None):
     ap.add_argument("--attention-softmax", default="torch", choices=list(approx_ops.ATTENTION_SOFTMAXES),
                     help="with --approx-attention: the scale, softmax and PV operand quantizer in torch, or as one kernel "
                          "pass each way")
+    ap.add_argument("--layer-norm", default=None, choices=list(approx_ops.LAYER_NORMS),
+                    help="the layer norms' input quantizer + norm in torch, or as one kernel pass each way")
     ap.add_argument("--output", default=None, help="also write the step records (a JSON list) here")
     return ap.parse_args(argv)
 
@@ -115,6 +122,8 @@ def approx_cfg(args):
         cfg["bn_backward"] = args.bn_backward
     if getattr(args, "attention_softmax", "torch") != "torch":
         cfg["attention_softmax"] = args.attention_softmax
+    if (getattr(args, "layer_norm", None) or "torch") != "torch":
+        cfg["layer_norm"] = args.layer_norm
     return cfg
 
 
@@ -183,6 +192,9 @@ def finetune(model, data, args, dev):
             if getattr(args, "attention_softmax", "torch") != "torch":
                 rec.update(attn_softmax_ms=_events_ms(prof.get("attn_softmax_forward", ())) +
                            _events_ms(prof.get("attn_softmax_backward", ())))
+            if getattr(args, "layer_norm", None) is not None:
+                rec.update(layer_norm_ms=_events_ms(prof.get("layer_norm_forward", ())) +
+                           _events_ms(prof.get("layer_norm_backward", ())))
             if ranges:
                 now = torch.cat([p.detach().reshape(-1) for p in ranges])
                 rec.update(max_range_change=float(((now - cal0).abs() / cal0.abs()).max()),

@@ -187,6 +187,8 @@ def parse(argv=None):
     ap.add_argument("--attention-softmax", default="torch", choices=["torch", "fused"],
                     help="with --approx-attention: the scale, softmax and PV operand quantizer in torch, or as one "
                          "kernel pass (DESIGN.md §3al)")
+    ap.add_argument("--layer-norm", default="torch", choices=["torch", "fused"],
+                    help="ViT: the layer norms' input quantizer + norm in torch, or as one kernel pass (DESIGN.md §3am)")
     ap.add_argument("--output", default=None, help="also write the result JSON here")
     return ap.parse_args(argv)
 
@@ -298,6 +300,8 @@ def approx_cfg(args):
         cfg["approx_attention"] = True
     if getattr(args, "attention_softmax", "torch") != "torch":
         cfg["attention_softmax"] = args.attention_softmax
+    if getattr(args, "layer_norm", "torch") != "torch":
+        cfg["layer_norm"] = args.layer_norm
     if getattr(args, "error_table", None):
         from .error_tables import load_error_table
         cfg["error_table"] = load_error_table(args.error_table, args.mant_width)  # read once, here

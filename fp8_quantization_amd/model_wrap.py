@@ -24,13 +24,14 @@ from torch import nn
 from torch.nn.modules.conv import _ConvNd
 from torch.nn.modules.pooling import _AdaptiveAvgPoolNd, _AvgPoolNd
 
-from . import chain
+from . import approx_ops, chain
 from .approx_calculation import QCustomBNConv2dTorch, QCustomConv2dTorch, QCustomLinearTorch
 from .quantization.base_quantized_classes import (QuantizedActivation, QuantizedModule, _set_layer_approx_calculation,
                                                   _set_layer_estimate_ranges, _set_layer_fix_ranges,
-                                                  _set_layer_learn_ranges, sync_ste)
+                                                  _set_layer_learn_ranges, layer_norm, sync_ste)
+from .quantization.fp8_quantizer import FPQuantizer
 from .quantization.hijacker import QuantizationHijacker, activations_set
-from .quantization.quantization_manager import QuantizationManager
+from .quantization.quantization_manager import QuantizationManager, Qstates
 
 __all__ = ["QuantizedModel", "QuantizedActivationWrapper", "Flattener", "QuantLayerNorm", "fold_bn",
            "quantize_sequential", "quantize_model", "non_bn_module_map", "bn_module_map"]
@@ -41,8 +42,51 @@ class QuantLayerNorm(QuantizationHijacker, nn.LayerNorm):
     """autoquant_utils.py:166-174: FP8-quantized input and (per-channel) weight, then a plain
     fp32 layer norm -- not an approx product."""
 
-    def run_forward(self, x, weight, bias, offsets=None):
-        return F.layer_norm(x.contiguous(), self.normalized_shape, weight.contiguous(), bias.contiguous(), self.eps)
+    def _fused_plan(self):
+        """custom_approx_params['layer_norm'] = "fused" (DESIGN.md §3am): (True, the input FPQuantizer the kernel
+        applies, or None where the input quantizer is off) when this forward's one run_forward may run as
+        approx_ops.layer_norm; (False, None) where the torch lines run: the key absent or "torch", range estimation
+        or a second run_forward (original_quantize_res, quantize_after_mult_and_add), a normalized_shape that is not
+        1-D of at most 4096 with weight and bias, or an input quantizer that is not a per-tensor FP8 quantizer in the
+        fixed-range state with a constant maxval (the MSE search and learned ranges read or train on the input)."""
+        if layer_norm(self) != "fused":
+            return False, None
+        if not (self.fix_ranges_flag and not self.original_quantize_res and self.res_quantizer_flag and self.approx_flag
+                and not self.quantize_after_mult_and_add):
+            return False, None
+        if len(self.normalized_shape) != 1 or self.normalized_shape[0] > approx_ops.LAYER_NORM_MAX or \
+                self.weight is None or self.bias is None:
+            return False, None
+        if not (self.quantize_input and self._qa()):
+            return True, None
+        mgr = self.activation_quantizer
+        q = getattr(mgr, "quantizer", None)
+        if not (getattr(mgr, "state", None) == Qstates.fix_ranges and isinstance(q, FPQuantizer) and not q.per_channel
+                and q.maxval.numel() == 1 and not q.maxval.requires_grad):
+            return False, None
+        return True, q
+
+    def _fused_input_quantizer(self, qa):
+        return self._fused_plan()[1]
+
+    def run_forward(self, x, weight, bias, offsets=None, qin=None):
+        """qin: the input FPQuantizer of _fused_plan -- x is unquantized, the kernel applies the quantizer and
+        its custom_bias is set as its own forward would."""
+        fused = self._fused_plan()[0] and x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and x.numel() > 0
+        if not fused:
+            if qin is not None:  # (a CPU, strided or non-fp32 input: the quantizer's own pass, as without the key)
+                x = self.activation_quantizer(x)
+            return F.layer_norm(x.contiguous(), self.normalized_shape, weight.contiguous(), bias.contiguous(), self.eps)
+        quantizer = None
+        if qin is not None:
+            if qin.maxval.device != x.device:  # (as FPQuantizer.forward)
+                qin._assign_maxval(qin.maxval.to(x.device))
+            quantizer = (qin.maxval, qin.n_bits, qin._mbits_int, qin.sign_bits)
+        op = approx_ops.layer_norm_ste if sync_ste(self) else approx_ops.layer_norm
+        res = op(x, weight.contiguous(), bias.contiguous(), self.eps, quantizer)
+        if qin is not None:
+            qin.custom_bias = res[-1]
+        return res[0]
 
 
 non_bn_module_map = {nn.Conv2d: QCustomConv2dTorch, nn.Linear: QCustomLinearTorch, nn.LayerNorm: QuantLayerNorm}

@@ -103,6 +103,15 @@ def attention_softmax(module):
                                    "custom_approx_params['attention_softmax']")
 
 
+def layer_norm(module):
+    """custom_approx_params['layer_norm'] of a module: QuantLayerNorm's path (model_wrap.QuantLayerNorm).  Absent or
+    "torch": the input's quantizer pass, then F.layer_norm; "fused": approx_ops.layer_norm, one kernel pass each way;
+    anything else raises ValueError (at construction too).  Nothing on other layers."""
+    from ..approx_ops import check_layer_norm
+    return check_layer_norm((getattr(module, "custom_approx_params", None) or {}).get("layer_norm", "torch"),
+                            "custom_approx_params['layer_norm']")
+
+
 def _version5(module):
     return (getattr(module, "custom_approx_params", None) or {}).get("approx_version", 9) == 5
 
@@ -122,6 +131,7 @@ class QuantizedModule(nn.Module):
         conv_backward(self)
         bn_backward(self)
         attention_softmax(self)
+        layer_norm(self)
         self.run_method = kwargs.pop("run_method", None) or dict(_DEFAULT_RUN_METHOD)
         self.approx_flag = self.run_method["approx_flag"]
         self.quantize_after_mult_and_add = self.run_method["quantize_after_mult_and_add"]

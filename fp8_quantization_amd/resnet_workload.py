@@ -26,7 +26,7 @@ def approx_qparams(expo_width=4, mant_width=3, dnsmp_factor=3, withComp=False, w
                    with_UF_opt=False, weight_range_method="current_minmax", weight_range_options=None,
                    act_range_method="allminmax", act_range_options=None, mse_include_mantissa_bits=False,
                    error_table=None, ste_backward=False, learn_maxval=False, grad_split_k=1,
-                   conv_backward="im2col", bn_backward="torch", attention_softmax="torch"):
+                   conv_backward="im2col", bn_backward="torch", attention_softmax="torch", layer_norm="torch"):
     """qparams exactly as the reference scripts build them (utils/click_options.py:544-606,
     scripts/generated_scripts.py): per-channel current_minmax weights, allminmax activations,
     quantize_input, FP8 quantizer with set_maxval, approx + res_quantizer run method.
@@ -48,6 +48,8 @@ def approx_qparams(expo_width=4, mant_width=3, dnsmp_factor=3, withComp=False, w
     attention_softmax (custom_approx_params["attention_softmax"]: "fused"; "torch" = off): approximate attention's
     scale, softmax and PV operand quantizer as one kernel pass each way (approx_ops.attention_softmax), nothing
     without the ViT's approx_attention;
+    layer_norm (custom_approx_params["layer_norm"]: "fused"; "torch" = off): a QuantLayerNorm's input quantizer, norm
+    and affine map as one kernel pass each way (approx_ops.layer_norm), nothing on other layers;
     learn_maxval (the reference's --fp8-learn-maxval): every FP8 quantizer is built so that learn_ranges()
     turns its maxval into a Parameter (needs ste_backward for its gradient).
 
@@ -79,6 +81,7 @@ def approx_qparams(expo_width=4, mant_width=3, dnsmp_factor=3, withComp=False, w
                                   **({"conv_backward": conv_backward} if conv_backward != "im2col" else {}),
                                   **({"bn_backward": bn_backward} if bn_backward != "torch" else {}),
                                   **({"attention_softmax": attention_softmax} if attention_softmax != "torch" else {}),
+                                  **({"layer_norm": layer_norm} if layer_norm != "torch" else {}),
                                   **({"approx_version": 5} if approx_version == 5 else {})),
         run_method=dict(run_method) if run_method else dict(
             approx_flag=True, quantize_after_mult_and_add=False, res_quantizer_flag=True, original_quantize_res=False))

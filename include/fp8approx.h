@@ -880,6 +880,35 @@ int fp8a_attn_softmax_backward(const float *s, const float *g, int64_t rows, int
                                const float *maxval, int n_bits, int Mbits, int sign_bits, float *ds,
                                fp8a_stream_t stream);
 
+/*
+ * The layer norm block, one pass over the activation each way (csrc/layer_norm.h): x is fp32 [rows][n] contiguous,
+ * 1 <= n <= 4096; gamma and beta fp32 [n].
+ *   forward   q = the per-tensor FP8 fake quantizer (maxval [1] on the device, n_bits, Mbits, sign_bits) of x, bit for
+ *             bit fp8a_fp8_quantize, and its float / int32 bias (bias_out / ibias_out [1], NULL: not written); maxval
+ *             NULL: q = x, the format arguments are not read and no bias is written.
+ *             mean = sum q / n and var = sum (q - mean)^2 / n with the sums in double, each rounded to fp32 once;
+ *             rstd = 1 / sqrtf(var + eps); y = fmaf((q - mean) * rstd, gamma, beta); mean and rstd [rows] are written.
+ *   backward  from x, g = the gradient of y, gamma and the forward's mean and rstd: xhat recomputed bit for bit;
+ *             gy = g gamma; c1 = sum gy / n, c2 = sum gy xhat / n (double sums, kept in double); dx = w *
+ *             (rstd * (float)((gy - c1) - xhat c2)), the bracket in double and rounded to fp32 once, with the quantizer's clamp weight w (1 inside (lo, maxval), 1/2 on a bound, 0 outside; without a
+ *             quantizer dx is the product's second factor); dbeta = sum over rows of g, dgamma = of g xhat (double
+ *             sums, rounded once).  dx may be g.  workspace: fp8a_layer_norm_backward_workspace_size(rows, n) bytes on
+ *             the device, 16-byte aligned (the workgroups' partial column sums; it need not be cleared).
+ * Sums run in a fixed order that depends on rows, n and the pointers' 16-byte alignment alone, without floating-point
+ * atomics: two calls return identical bytes.  Every check runs before the launch, and every refusal is FP8A_EINVAL:
+ * rows outside [0, 2^31), n outside [1, 4096], with a maxval a format fp8a_fq_train_forward refuses, a null tensor
+ * pointer, a null, misaligned or short workspace.  rows == 0 is success without a launch.  Both calls are
+ * asynchronous on the stream and may be captured into a graph.
+ */
+int fp8a_layer_norm(const float *x, int64_t rows, int64_t n, const float *gamma, const float *beta, float eps,
+                    const float *maxval, int n_bits, int Mbits, int sign_bits, float *y, float *mean, float *rstd,
+                    float *bias_out, int32_t *ibias_out, fp8a_stream_t stream);
+size_t fp8a_layer_norm_backward_workspace_size(int64_t rows, int64_t n);
+int fp8a_layer_norm_backward(const float *x, const float *g, int64_t rows, int64_t n, const float *gamma,
+                             const float *mean, const float *rstd, const float *maxval, int n_bits, int Mbits,
+                             int sign_bits, float *dx, float *dgamma, float *dbeta, void *workspace,
+                             size_t workspace_bytes, fp8a_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
